@@ -13,6 +13,12 @@ latitude slabs (strong scaling, the north star's 1/2/4/8-GPU figure; `--scaling 
 1440×560 slab instead).  Without torchrun's environment `--gpus N` starts the N ranks itself.
 
 Prints ONE JSON line on rank 0.
+
+A plain run (`--gpus 1 --steps K --warmup W`) does what its headline figure needs: set up, settle the clocks, W warm-up
+steps, exactly K timed steps of the named solver path, the line.  `--full` adds what takes runs of its own: repetitions
+of the K steps (median reported), the certified path timed beside the exact one, the event-bracketed per-kernel pass,
+stage times and rooflines, the device copy, the CPU baseline and the parity checks against the CPU oracle.
+`--dump-outputs DIR` writes the fields the last timed step returned as DIR/<group>.<field>.npy (float64).
 """
 import argparse
 import json
@@ -35,14 +41,24 @@ FP64_ISSUE_PEAK = 256 * 4 * 2.4e9 / 4  # wave-instructions/s: 1024 SIMDs, one FP
 BYTES_INTERP = 18.3 + 64.0             # JRA55 window amortised + 8 exchange fields written
 BYTES_NET = 88.0 + 40.0
 SNAPSHOT_INTERVAL, DT = 3 * 3600.0, 20 * 60.0   # JRA55 is 3-hourly; Δt = 20 min (README.md:76)
+DUMP_SEED = 20240611   # --dump-outputs: the row sample of a surface over the size budget
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 1000, median of 5 repetitions)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 1000)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default 50)")
-    ap.add_argument("--repetitions", type=int, default=None, help="timed repetitions of K steps; the median is reported")
+    ap.add_argument("--repetitions", type=int, default=None,
+                    help="timed repetitions of K steps; the median is reported (default 1; with --full 5 without --steps, else 3-9)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: repetitions of the K steps, the certified path timed beside the exact "
+                         "one (N = 1), the event-bracketed per-kernel pass, stage times and rooflines, the device copy, the CPU baseline "
+                         "and the parity checks against the CPU oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the fields the last timed step of the named solver path returned (interior "
+                         "cells of the flux and net-flux fields, with --config sea_ice also the sea-ice ones; float64) as "
+                         "DIR/<group>.<field>.npy; beyond 64 MB in all, the same seeded sample of rows of every field")
     ap.add_argument("--latency-layout", choices=("auto", "never", "always"), default="auto",
                     help="CF_OPT_LATENCY_LAYOUT: the exact path's kernels for one or two waves per SIMD (auto: chunk plans of at most two workgroups per CU)")
     ap.add_argument("--ao-chunk", type=int, default=0, help="CF_OPT_AO_CHUNK (0 = the library's plan): wet cells per solver workgroup — an experiment "
@@ -369,6 +385,8 @@ def long_run(a, ctx, params, nx, ny, h, tripolar, ocean_np, w_np, states, w, atm
 
 def main():
     a = parse()
+    if a.dump_outputs is not None and (a.days is not None or a.selftest):
+        raise SystemExit("bench.py --dump-outputs: the throughput run only (not with --days or --selftest)")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         launch_ranks(a)
     import numpy as np
@@ -403,10 +421,15 @@ def main():
     default_protocol = a.steps is None
     steps = a.steps if a.steps is not None else 1000
     warmup = a.warmup if a.warmup is not None else 50
-    # --steps K: at least 3 repetitions of exactly K steps, more while they stay inside ≈ 30 ms per solver path (K = 20: 9
-    # regions of 1.7 ms) — a short region is exposed to whatever the host does for a few hundred microseconds (one evidence run
-    # read 0.085, 0.095, 0.096 ms per step in three consecutive 20-step regions whose kernels ran at their usual 76 µs)
-    reps = a.repetitions if a.repetitions is not None else (5 if default_protocol else (max(3, min(9, int(0.030 / (steps * 0.085e-3)))) | 1))   # (odd: the median is one of the samples)
+    if a.repetitions is not None:
+        reps = a.repetitions
+    elif not a.full:
+        reps = 1    # a plain run times exactly --steps steps, once
+    else:
+        # --full --steps K: at least 3 repetitions of exactly K steps, more while they stay inside ≈ 30 ms per solver path (K = 20: 9
+        # regions of 1.7 ms) — a short region is exposed to whatever the host does for a few hundred microseconds (one evidence run
+        # read 0.085, 0.095, 0.096 ms per step in three consecutive 20-step regions whose kernels ran at their usual 76 µs)
+        reps = 5 if default_protocol else (max(3, min(9, int(0.030 / (steps * 0.085e-3)))) | 1)   # (odd: the median is one of the samples)
 
     h = a.halo
     if a.scaling == "weak":
@@ -490,7 +513,7 @@ def main():
     # the ABI's three radiation diagnostics are optional outputs and off unless asked for
     net = ctx.field_set(NET_NAMES if a.net_diagnostics else NET_NAMES[:5])
 
-    ice = ice_state = ai = net_ice = None
+    ice = ice_state = ai = net_ice = skin0 = None
     if a.config == "sea_ice":
         ice_cfg = ic.corrected_atmosphere_sea_ice_fluxes() if a.flux_configuration != "ncar" else ic.ncar_atmosphere_sea_ice_fluxes()
         ctx.set_sea_ice_formulation(ic.flux_params(ice_cfg))
@@ -507,6 +530,7 @@ def main():
         # first guess (atmosphere.jl:34-39; coflux/models.py::update_state): one buffer for both, as in a coupled run
         ai["temperature"].copy_(ice_state["top_temperature"])
         ice_state["top_temperature"] = ai["temperature"]
+        skin0 = ai["temperature"].clone()   # (the first guess the timed loop starts from again after the settle steps)
 
     if a.days is not None:
         out = long_run(a, ctx, params, nx, ny, h, tripolar, ocean_np, w_np, states, w, atmos_sets, fl, net, pipeline, mode)
@@ -751,6 +775,37 @@ def main():
 
     PATH_CODE = {"exact": abi.SOLVER_PATH_EXACT, "certified": abi.SOLVER_PATH_CERTIFIED}
     SWITCH_STEPS = 4   # untimed steps after a change of CF_OPT_SOLVER_PATH inside the repetition loop
+    captured = {}      # --dump-outputs: halo backend → (step, interior copies of the fields its last timed step returned)
+
+    def output_fields():
+        """What a caller of the timed step receives: `<group>.<field>` → the field (rows and columns with halos)."""
+        groups = [("fluxes", fl), ("net", net)]
+        if a.config == "sea_ice":
+            groups += [("sea_ice_fluxes", ai), ("net_sea_ice", net_ice)]
+        return {f"{g}.{k}": t for g, fields in groups for k, t in fields.items()}
+
+    def write_outputs(step, fields):
+        """--dump-outputs: the interior of every field (slabs gathered in rank order) as float64 DIR/<group>.<field>.npy, written
+        by rank 0.  Over 64 MB in all, every field keeps the same rows: a sorted sample drawn with a fixed seed."""
+        arrays = {}
+        for k in sorted(fields):
+            mine = fields[k].cpu().numpy()
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, mine)
+                mine = np.concatenate(parts, axis=0)
+            arrays[k] = np.ascontiguousarray(mine, dtype=np.float64)
+        if rank != 0:
+            return None
+        rows_total, cols = next(iter(arrays.values())).shape
+        budget = 64 * 10 ** 6 - 4096 * len(arrays)    # (less room for the .npy headers)
+        keep = min(rows_total, budget // (8 * cols * len(arrays)))
+        rows = None if keep == rows_total else np.sort(np.random.default_rng(DUMP_SEED).choice(rows_total, size=keep, replace=False))
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for k, v in arrays.items():
+            np.save(os.path.join(a.dump_outputs, k + ".npy"), v if rows is None else np.ascontiguousarray(v[rows]))
+        return dict(dir=a.dump_outputs, step=step, fields=sorted(arrays), dtype="f64", shape=[int(keep), int(cols)],
+                    rows=("all interior rows" if rows is None else f"{keep} of {rows_total} interior rows, sorted sample, seed {DUMP_SEED}"))
 
     def timed(name, paths):
         """Times `steps` steps `reps` times for every solver path in `paths` on halo backend `name`.  With two paths the
@@ -777,11 +832,18 @@ def main():
             if enough:
                 break
         settle[name] = done
-        run_steps(name, sched, done, warmup)
-        first = done + warmup
+        # The settle steps only bring the clocks up, and how many ran depends on the time they took.  The warm-up and the timed
+        # steps start again at step 0 (the requested-ahead atmosphere state dropped, the carried sea-ice skin temperature back at
+        # its first guess), so every timed step's inputs, and what --dump-outputs writes, depend on the arguments alone
+        ctx.sync()
+        ctx.discard_prefetched_atmosphere_state()
+        if skin0 is not None:
+            ai["temperature"].copy_(skin0)
+        run_steps(name, sched, 0, warmup)
+        first = warmup
         samples, by_rank = {q: [] for q in paths}, {q: [] for q in paths}
         switches = 0
-        for _ in range(reps):
+        for rep in range(reps):
             for q in paths:
                 if len(paths) > 1:
                     ctx.set_option(abi.OPT_SOLVER_PATH, PATH_CODE[q])
@@ -800,6 +862,10 @@ def main():
                     dt = max(by_rank[q][-1])           # the MAX over ranks is the step time of the job
                 samples[q].append(dt)
                 first += steps
+                if a.dump_outputs is not None and q == paths[0] and rep == reps - 1:
+                    # device copies of what the last timed step of the named path returned, before anything else runs
+                    captured[name] = (first - 1, {k: t[h:h + ny, h:h + nx].clone() for k, t in output_fields().items()})
+                    torch.cuda.synchronize()
         switch_steps[name] = switches * SWITCH_STEPS
         out = {}
         for q in paths:
@@ -810,7 +876,7 @@ def main():
 
     # ---- the two solver paths (CF_OPT_SOLVER_PATH) ---------------------------------------------------------------------
     # `value` is the path the command line names — exact unless --solver-path certified — on every verified halo backend.
-    # With auto at N = 1 the certified path is timed beside it (interleaved repetition by repetition on the same schedule),
+    # With --full and auto at N = 1 the certified path is timed beside it (interleaved repetition by repetition on the same schedule),
     # checked against the CPU oracle, and reported as `value_certified`: a second number, never the number of record
     # (VERDICT r5 / ADVICE r5: the library and ComponentInterfaces default to the exact path, so that is what `value` measures;
     # at N > 1 one path only, so that the points of a scaling series are the same algorithm).
@@ -819,7 +885,7 @@ def main():
     if first_path == "certified" and ctx.solver_iteration_path() != abi.SOLVER_PATH_CERTIFIED:
         first_path = "exact"    # (the option does not apply to this formulation / geometry: the exact path ran)
     paths = [first_path]
-    if a.solver_path == "auto" and a.config == "ocean" and world == 1:
+    if a.full and a.solver_path == "auto" and a.config == "ocean" and world == 1:
         ctx.set_option(abi.OPT_SOLVER_PATH, abi.SOLVER_PATH_CERTIFIED)
         if ctx.solver_iteration_path() == abi.SOLVER_PATH_CERTIFIED:
             paths.append("certified")
@@ -834,6 +900,7 @@ def main():
     for name in results:
         per_rank[name] = results[name][first_path][4]
     results = {name: results[name][first_path][:4] for name in results}   # (halo_paths_ms_per_step reads these)
+    dumped = write_outputs(*captured[best]) if a.dump_outputs is not None else None
     path_parity, chosen = {}, first_path
     if "certified" in paths and first_path == "exact":
         ctx.set_option(abi.OPT_SOLVER_PATH, abi.SOLVER_PATH_CERTIFIED)
@@ -873,11 +940,49 @@ def main():
     n_prof = min(max(steps, 20), 200)
     # CF_OPT_TRIP_HINTS: 2 = the library's default (what the timed region ran), 1 = every solver orders its batches by
     # the previous call's trip counts (round 2's default; reported beside it)
-    prof = instrumented(n_prof, a.trip_hints) if a.config == "ocean" and best != "torch" else None
+    prof = instrumented(n_prof, a.trip_hints) if a.full and a.config == "ocean" and best != "torch" else None
     prof_sorted = instrumented(n_prof, 1) if prof and not a.no_sorted_pass else None
     ctx.set_option(abi.OPT_TRIP_HINTS, a.trip_hints)
 
     if rank == 0:
+        grid_name = (f"TripolarGrid surface {nx}x{a.ny} (synthetic mesh with the real fold; general weights + wind rotation)" if tripolar
+                     else f"1/4-degree LatitudeLongitudeGrid surface {nx}x{a.ny}")
+        workload = (f"{grid_name} per {'GPU' if a.scaling == 'weak' else 'job'}"
+                    f"{' sharded into ' + str(world) + ' latitude slabs' if world > 1 and a.scaling == 'strong' else ''}, "
+                    f"JRA55 640x320 f32 atmosphere ({n_levels}-snapshot window, clock advancing 20 min per step), "
+                    f"SimilarityTheoryFluxes(:{a.flux_configuration}) + Radiation"
+                    f"{' + sea-ice interface and partition (config 3)' if a.config == 'sea_ice' else ''}, halo {h}, ring 1")
+        out = dict(metric="flux-kernel surface cells/s (update_state!: JRA55 interp + similarity-theory fluxes + net fluxes)",
+                   value=value, unit="cells/s", n_gpus=world, steps=steps, warmup=warmup,
+                   ms_per_step=elapsed / steps * 1e3, higher_is_better=True, scaling=a.scaling if world > 1 else "strong",
+                   vs_baseline=None, dtype="f64", data="synthetic",
+                   config=dict(workload=workload, global_cells=cells_total, parallelism=f"latitude-slab x{world}",
+                               rows_per_rank=ny, halo_backend=best, halo_verified=(halo_verified if world > 1 else None),
+                               rccl_comm_ranks=rccl_comm_ranks, solver_path=chosen,
+                               ice_free_cells=(a.ice_free_cells if a.config == "sea_ice" else None),
+                               certified_budget=(a.certified_budget * 1e-9 if "certified" in path_results else None),
+                               halo_rows=ring_rows if world > 1 else 0, halo_in_solver_launch=(halo_in_launch if world > 1 else None),
+                               pipelined_interpolation=pipeline,
+                               pipeline_mode=mode,
+                               step_loop="cf_time_steps (C)" if (a.config == "ocean" and best != "torch") else "host"),
+                   settle_steps=settle.get(best), untimed_steps=(settle.get(best) or 0) + warmup + (switch_steps.get(best) or 0),
+                   repetitions=reps,
+                   repetition_order=("interleaved: " + ", ".join(paths) + f" per repetition, {SWITCH_STEPS} untimed steps after each switch"
+                                     if len(paths) > 1 else None),
+                   solver_paths_ms_per_step_samples={k: [t / steps * 1e3 for t in v[1]] for k, v in path_results.items()}, ms_per_step_samples=[s / steps * 1e3 for s in samples],
+                   ms_per_step_spread=[min(samples) / steps * 1e3, max(samples) / steps * 1e3],
+                   ms_per_step_by_rank=([t / steps * 1e3 for t in path_per_rank[chosen]] if path_per_rank.get(chosen) else None),
+                   solver_paths_ms_per_step={k: v[0] / steps * 1e3 for k, v in path_results.items()},
+                   value_exact=(cells_total * steps / path_results["exact"][0] if "exact" in path_results else None),
+                   value_certified=(cells_total * steps / path_results["certified"][0] if "certified" in path_results else None),
+                   solver_path_parity=path_parity or None,
+                   halo_paths_ms_per_step={k: v[0] / steps * 1e3 for k, v in results.items()} if world > 1 else None,
+                   parity="vs reference: unpinned (self-consistent restatements only; see DESIGN.md)")
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if a.share_device:
+            out["rehearsal"] = f"{world} ranks time-sharing ONE device: a test of the N-rank code path, not a scaling number"
+    if rank == 0 and a.full:
         kw = dict(src=src, weights=w, ocean=states[0], atmos=atmos_sets[0], fluxes=fl, net=net, time_fraction=0.37)
         interp_ms = min(ctx.time_stage(abi.STAGE_INTERPOLATE, 50, **kw) for _ in range(3))
         if mode == "on":   # the kernel the pipelined step actually runs on the auxiliary stream
@@ -952,38 +1057,7 @@ def main():
                         bytes_per_cell=nbytes, cells_per_launch=ncells, avg_launch_ms=ms,
                         cells_per_s=ncells / (ms * 1e-3), **extra)
 
-        grid_name = (f"TripolarGrid surface {nx}x{a.ny} (synthetic mesh with the real fold; general weights + wind rotation)" if tripolar
-                     else f"1/4-degree LatitudeLongitudeGrid surface {nx}x{a.ny}")
-        workload = (f"{grid_name} per {'GPU' if a.scaling == 'weak' else 'job'}"
-                    f"{' sharded into ' + str(world) + ' latitude slabs' if world > 1 and a.scaling == 'strong' else ''}, "
-                    f"JRA55 640x320 f32 atmosphere ({n_levels}-snapshot window, clock advancing 20 min per step), "
-                    f"SimilarityTheoryFluxes(:{a.flux_configuration}) + Radiation"
-                    f"{' + sea-ice interface and partition (config 3)' if a.config == 'sea_ice' else ''}, halo {h}, ring 1")
-        out = dict(metric="flux-kernel surface cells/s (update_state!: JRA55 interp + similarity-theory fluxes + net fluxes)",
-                   value=value, unit="cells/s", n_gpus=world, steps=steps, warmup=warmup,
-                   ms_per_step=elapsed / steps * 1e3, higher_is_better=True, scaling=a.scaling if world > 1 else "strong",
-                   vs_baseline=None, dtype="f64", data="synthetic",
-                   config=dict(workload=workload, global_cells=cells_total, parallelism=f"latitude-slab x{world}",
-                               rows_per_rank=ny, halo_backend=best, halo_verified=(halo_verified if world > 1 else None),
-                               rccl_comm_ranks=rccl_comm_ranks, solver_path=chosen,
-                               ice_free_cells=(a.ice_free_cells if a.config == "sea_ice" else None),
-                               certified_budget=(a.certified_budget * 1e-9 if "certified" in path_results else None),
-                               halo_rows=ring_rows if world > 1 else 0, halo_in_solver_launch=(halo_in_launch if world > 1 else None),
-                               pipelined_interpolation=pipeline,
-                               pipeline_mode=mode,
-                               step_loop="cf_time_steps (C)" if (a.config == "ocean" and best != "torch") else "host"),
-                   settle_steps=settle.get(best), untimed_steps=(settle.get(best) or 0) + warmup + (switch_steps.get(best) or 0),
-                   repetitions=reps,
-                   repetition_order=("interleaved: " + ", ".join(paths) + f" per repetition, {SWITCH_STEPS} untimed steps after each switch"
-                                     if len(paths) > 1 else None),
-                   solver_paths_ms_per_step_samples={k: [t / steps * 1e3 for t in v[1]] for k, v in path_results.items()}, ms_per_step_samples=[s / steps * 1e3 for s in samples],
-                   ms_per_step_spread=[min(samples) / steps * 1e3, max(samples) / steps * 1e3],
-                   ms_per_step_by_rank=([t / steps * 1e3 for t in path_per_rank[chosen]] if path_per_rank.get(chosen) else None),
-                   solver_paths_ms_per_step={k: v[0] / steps * 1e3 for k, v in path_results.items()},
-                   value_exact=(cells_total * steps / path_results["exact"][0] if "exact" in path_results else None),
-                   value_certified=(cells_total * steps / path_results["certified"][0] if "certified" in path_results else None),
-                   solver_path_parity=path_parity or None,
-                   halo_paths_ms_per_step={k: v[0] / steps * 1e3 for k, v in results.items()} if world > 1 else None,
+        out.update(
                    # dominant kernel = compute_atmosphere_ocean_fluxes! (SURVEY.md §8d contract figure 128 B/cell)
                    roofline=roof(f"{ao_kernel} ({ao_what})", ao_bytes, cells_rank, ao_ms, traffic_key=ao_key,
                                  launches_timed=nrec,
@@ -1006,8 +1080,7 @@ def main():
                                   interpolate_background_standalone=interp_bg_ms if mode == "on" else None,
                                   ao_fluxes=ao_ms, net_fluxes=net_ms, ao_fluxes_standalone=ao_ms_alone,
                                   net_fluxes_standalone=net_ms_alone),
-                   device_copy_GBs=2 * copy_bytes / (copy_ms * 1e-3) / 1e9,
-                   parity="vs reference: unpinned (self-consistent restatements only; see DESIGN.md)")
+                   device_copy_GBs=2 * copy_bytes / (copy_ms * 1e-3) / 1e9)
         # the ceiling that binds the solver: FP64 VALU issue
         k_sq = sq.get(ao_key)
         if k_sq:
@@ -1036,8 +1109,6 @@ def main():
                     note=sc["note"])
         except Exception:
             pass
-        if a.share_device:
-            out["rehearsal"] = f"{world} ranks time-sharing ONE device: a test of the N-rank code path, not a scaling number"
         if not a.no_cpu_baseline and world == 1:
             case_np = dict(ocean=ocean_np[0], src=src_np, weights=w_np)
             out["cpu_baseline"], ref = cpu_baseline(case_np, params, nx, ny, h, a.cpu_seconds)
@@ -1067,6 +1138,7 @@ def main():
                                               against="oracle/coflux_oracle.c (CPU restatement; parity vs the reference itself: unpinned)")
         else:
             out["cpu_baseline"] = None
+    if rank == 0:
         print(json.dumps(out), flush=True)
     ctx.close()
     if world > 1:

@@ -2,7 +2,7 @@
 import json, subprocess, sys
 if not sys.stdin.isatty() and sys.stdin.read(1):
     sys.exit("bench_brief.py runs bench.py itself: pass bench.py's arguments to it, do not pipe a second bench into it")
-out = subprocess.run([sys.executable, "bench.py"] + sys.argv[1:], capture_output=True, text=True)
+out = subprocess.run([sys.executable, "bench.py", "--full"] + sys.argv[1:], capture_output=True, text=True)
 line = [l for l in out.stdout.splitlines() if l.startswith("{")]
 if not line:
     print(out.stdout[-2000:], out.stderr[-2000:]); sys.exit(1)

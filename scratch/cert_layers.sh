@@ -3,7 +3,7 @@ P="import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); pri
 for budget in ${BUDGETS_SCAN:-800}; do
 for lay in "" 1024,768,512 896,768,640 832,768,704 1152,768,384 1024,896,384; do
   echo "== budget $budget layers ${lay:-plan}"
-  if [ -z "$lay" ]; then python bench.py --no-cpu-baseline --solver-path certified --certified-budget $budget ${EXTRA} 2>/dev/null | python -c "$P"
-  else COFLUX_EXPERIMENTS=1 COFLUX_LAYERS=$lay python bench.py --no-cpu-baseline --solver-path certified --certified-budget $budget ${EXTRA} 2>/dev/null | python -c "$P"; fi
+  if [ -z "$lay" ]; then python bench.py --full --no-cpu-baseline --solver-path certified --certified-budget $budget ${EXTRA} 2>/dev/null | python -c "$P"
+  else COFLUX_EXPERIMENTS=1 COFLUX_LAYERS=$lay python bench.py --full --no-cpu-baseline --solver-path certified --certified-budget $budget ${EXTRA} 2>/dev/null | python -c "$P"; fi
 done; done
-echo "== exact"; python bench.py --no-cpu-baseline 2>/dev/null | python -c "$P"
+echo "== exact"; python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "$P"

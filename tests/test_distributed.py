@@ -1,9 +1,6 @@
 """world_size-2 `gloo` tests of the latitude-slab sharding: slab bounds, the one-row
 halo exchange of the ocean surface state, and that two slabs + exchanged halos reproduce the
 single-domain oracle result row for row (no data-path collective besides the neighbour rows)."""
-import os
-import socket
-
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -18,17 +15,8 @@ from coflux.distributed import exchange_halo_rows_torch, halo_row_slices, slab_b
 NX, NY, H = 48, 20, 3
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _worker(rank, world, port, rows, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _worker(rank, world, init, rows, out):
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         j0, j1 = slab_bounds(NY, rank, world)
         ny = j1 - j0
@@ -68,8 +56,8 @@ def _worker(rank, world, port, rows, out):
 def _run(rows):
     mgr = mp.Manager()
     out = mgr.dict()
-    port = _free_port()
-    mp.spawn(_worker, args=(2, port, rows, out), nprocs=2, join=True)
+    init = util.rendezvous()
+    mp.spawn(_worker, args=(2, init, rows, out), nprocs=2, join=True)
     return dict(out)
 
 
@@ -130,9 +118,8 @@ class _FakeContext:
         self.calls.append(("comm_init", ident, rank, world))
 
 
-def _fallback_worker(rank, world, port, fail_rank, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _fallback_worker(rank, world, init, fail_rank, out):
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         from coflux import distributed, runtime
         runtime.comm_unique_id = lambda: b"unique-id"      # (the real one needs the HIP library)
@@ -149,7 +136,7 @@ def test_peer_backend_falls_back_to_rccl_on_every_rank_together_gloo():
     for fail_rank, want in ((1, "rccl"), (-1, "peer")):
         mgr = mp.Manager()
         out = mgr.dict()
-        mp.spawn(_fallback_worker, args=(2, _free_port(), fail_rank, out), nprocs=2, join=True)
+        mp.spawn(_fallback_worker, args=(2, util.rendezvous(), fail_rank, out), nprocs=2, join=True)
         for rank in (0, 1):
             backend, calls, reason = out[rank]
             assert backend == want, (fail_rank, rank, backend)

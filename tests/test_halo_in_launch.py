@@ -4,7 +4,6 @@ multi-GPU node; the ranks share the test box's one device), 2 and 4 ranks, lat-l
 the stepping loop with the option on must leave the same bits as with the exchange kernel of its own, the exchanges must
 really have ridden, and the halo rows must really have been delivered (they are poisoned before every run)."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import util
 from coflux import abi, interface_computations as ic, synthetic as syn
 from coflux.distributed import slab_bounds
 
@@ -20,14 +20,6 @@ pytestmark = pytest.mark.gpu
 H, NSTEPS = 5, 7
 FIELDS = ("T", "S", "u", "v")
 INC = 1200.0 / 10800.0
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 def _case(grid, rank, world):
@@ -54,11 +46,11 @@ def _case(grid, rank, world):
     return nx, ny, [first, second], dict(separable=True, fi=fi, fj=fj, latitude=phi), syn.jra55_snapshots(4)
 
 
-def _worker(rank, world, port, grid, config, out):
+def _worker(rank, world, init, grid, config, out):
     from coflux.distributed import SlabHaloExchanger
     from coflux.runtime import EXCHANGE_NAMES, FLUX_NAMES, NET_NAMES, FluxContext
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    os.environ.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         fluxes = ic.corrected_atmosphere_ocean_fluxes() if config == "corrected" else ic.SimilarityTheoryFluxes()
         P = ic.flux_params(fluxes, ocean_surface=ic.SurfaceRadiationProperties(0.06, 1.0))
@@ -107,8 +99,8 @@ def _worker(rank, world, port, grid, config, out):
 def test_halo_rows_in_the_solver_launch_leave_the_bits_of_the_exchange_kernel(world, grid, config):
     ctxm = mp.get_context("spawn")
     out = ctxm.Manager().dict()
-    port = _free_port()
-    procs = [ctxm.Process(target=_worker, args=(r, world, port, grid, config, out)) for r in range(world)]
+    init = util.rendezvous()
+    procs = [ctxm.Process(target=_worker, args=(r, world, init, grid, config, out)) for r in range(world)]
     for p in procs:
         p.start()
     for p in procs:

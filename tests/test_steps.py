@@ -4,7 +4,6 @@ loop cf_time_steps, the pipelined interpolation (cf_prefetch_atmosphere_state), 
 tripolar fold.  Everything is compared bit for bit with the host-driven three-launch path / the single-domain
 state, which the parity tests in turn hold against the oracle."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -183,10 +182,10 @@ def test_peer_halo_rows_two_slabs_in_one_process():
     gctx.close()
 
 
-def _peer_worker(rank, world, port, out):
+def _peer_worker(rank, world, init, out):
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    os.environ.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         from coflux.distributed import SlabHaloExchanger
         ctx, states, src, w, _np, j0, j1 = _slab(rank, world, device=0)   # both ranks on the one device of the box
@@ -221,13 +220,10 @@ def test_peer_halo_rows_two_processes_hip_ipc():
     """The same exchange between two PROCESSES (one rank per process, as on a multi-GPU node), mailboxes mapped through
     hipIpcGetMemHandle / hipIpcOpenMemHandle; both ranks share the one device of the test box."""
     import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    init = util.rendezvous()
     ctxm = mp.get_context("spawn")
     out = ctxm.Manager().dict()
-    procs = [ctxm.Process(target=_peer_worker, args=(r, 2, port, out)) for r in range(2)]
+    procs = [ctxm.Process(target=_peer_worker, args=(r, 2, init, out)) for r in range(2)]
     for p in procs:
         p.start()
     for p in procs:
@@ -279,11 +275,11 @@ def test_fused_net_epilogue_is_bitwise_the_three_launch_sequence():
     ctx.close()
 
 
-def _two_device_worker(rank, world, port, backend, out):
+def _two_device_worker(rank, world, init, backend, out):
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    os.environ.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
     torch.cuda.set_device(rank)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         from coflux.distributed import SlabHaloExchanger
         ctx, states, src, w, _np, j0, j1 = _slab(rank, world, device=rank)       # one rank per GPU
@@ -324,13 +320,10 @@ def test_halo_rows_between_two_devices(backend):
     """One rank per GPU: native RCCL grouped send/recv (and its all-reduce in the salinity normaliser), and the peer-direct
     mailboxes over xGMI, against the globally indexed state."""
     import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
+    init = util.rendezvous()
     ctxm = mp.get_context("spawn")
     out = ctxm.Manager().dict()
-    procs = [ctxm.Process(target=_two_device_worker, args=(r, 2, port, backend, out)) for r in range(2)]
+    procs = [ctxm.Process(target=_two_device_worker, args=(r, 2, init, backend, out)) for r in range(2)]
     for p in procs:
         p.start()
     for p in procs:
@@ -348,7 +341,7 @@ def test_bench_n_rank_code_path_rehearsal():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-device", "--steps", "40",
-                        "--warmup", "5", "--nx", "360", "--ny", "120", "--no-cpu-baseline"],
+                        "--warmup", "5", "--nx", "360", "--ny", "120", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -5,7 +5,6 @@ applied locally on the last rank.  CPU: mesh / fold properties 
 GPU: the HIP path on slabs (peer-direct halo rows + cf_fold_north_halo inside cf_time_steps) against the single domain,
 and the single domain against the oracle."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -62,23 +61,14 @@ def test_fold_and_rotation_conventions_are_consistent():
     np.testing.assert_allclose(row, row[::-1], atol=1e-12)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _oracle_fluxes(case):
     g = orc.make_grid(case["nx"], case["ny"], H, H, 1)
     at = orc.interpolate_atmosphere_state(g, case["src"], case["weights"], 0, 1, 0.37)
     return orc.compute_atmosphere_ocean_fluxes(g, ic.flux_params(ic.corrected_atmosphere_ocean_fluxes()), case["ocean"], at)
 
 
-def _gloo_worker(rank, world, port, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _gloo_worker(rank, world, init, out):
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         j0, j1 = slab_bounds(NY, rank, world)
         ny = j1 - j0
@@ -107,7 +97,7 @@ def _gloo_worker(rank, world, port, out):
 def test_one_degree_tripolar_slabs_with_fold_reproduce_the_global_fluxes_gloo(world):
     """BASELINE config 4: 360×180 tripolar, latitude slabs on 2 and 4 ranks, two halo rows per seam, fold on the last rank."""
     out = mp.Manager().dict()
-    mp.spawn(_gloo_worker, args=(world, _free_port(), out), nprocs=world, join=True)
+    mp.spawn(_gloo_worker, args=(world, util.rendezvous(), out), nprocs=world, join=True)
     ref = _oracle_fluxes(syn.tripolar_case(NX, NY, H, H))
     assert np.abs(ref["x_momentum"][H + NY]).max() > 0          # the ring row beyond the fold is really computed
     for rank in range(world):
@@ -127,14 +117,14 @@ def _device_case(ctx, case):
     return ocean, src, w
 
 
-def _hip_worker(rank, world, port, out):
+def _hip_worker(rank, world, init, out):
     """One latitude slab of the 1° tripolar surface per PROCESS (all on the one device of the test box): peer-direct halo
     rows through HIP IPC on the seams, the fold on the last slab, one step of cf_time_steps."""
     from coflux.distributed import SlabHaloExchanger
     from coflux.runtime import EXCHANGE_NAMES, FLUX_NAMES, NET_NAMES, FluxContext
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    os.environ.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
     if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+        dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         P = ic.flux_params(ic.corrected_atmosphere_ocean_fluxes())
         j0, j1 = slab_bounds(NY, rank, world)
@@ -179,8 +169,8 @@ def test_one_degree_tripolar_hip_path_slabs_with_fold(world):
     ref_net = orc.compute_net_ocean_fluxes(g, P, ref_case["ocean"], at, ref, weights=ref_case["weights"])
     ctxm = mp.get_context("spawn")
     out = ctxm.Manager().dict()
-    port = _free_port()
-    procs = [ctxm.Process(target=_hip_worker, args=(r, world, port, out)) for r in range(world)]
+    init = util.rendezvous()
+    procs = [ctxm.Process(target=_hip_worker, args=(r, world, init, out)) for r in range(world)]
     for p in procs:
         p.start()
     for p in procs:

@@ -1,6 +1,11 @@
 """Shared builders for the parity tests: seeded synthetic inputs (coflux.synthetic), the oracle
 run on them, and the comparison metric  |Δ| ≤ tol · max(|ref|, field scale)  (SURVEY.md §7 H4:
 a pure relative error blows up where a flux crosses zero)."""
+import atexit
+import os
+import shutil
+import tempfile
+
 import numpy as np
 
 from coflux import interface_computations as ic
@@ -13,6 +18,14 @@ FIELD_SCALE = dict(sensible_heat=1.0, latent_heat=1.0, water_vapor=1e-6, x_momen
                    downwelling_longwave=1.0, downwelling_shortwave=1.0,
                    p=1.0, q=1e-4, Qs=1.0, Ql=1.0, Mp=1e-6)
 ATMOS_SCALE = dict(u=1.0, v=1.0, T=1.0, p=1.0, q=1e-4, Qs=1.0, Ql=1.0, Mp=1e-6)
+
+
+def rendezvous():
+    """init_method for the ranks of one multi-process test: torch.distributed's store in a fresh file.  A TCP port found
+    free with bind(0) and closed again can be taken by another process before rank 0 listens on it (EADDRINUSE)."""
+    d = tempfile.mkdtemp(prefix="coflux_rdzv_")
+    atexit.register(shutil.rmtree, d, True)
+    return "file://" + os.path.join(d, "store")
 
 CONFIGS = {
     "default": lambda: (ic.SimilarityTheoryFluxes(), None),

@@ -15,7 +15,7 @@ for k, v in raw.items():
     scale = 1 if k.startswith("interpolate") else 2
     kernels[k] = dict(FETCH_SIZE_KB=v["FETCH_SIZE"], WRITE_SIZE_KB=v["WRITE_SIZE"], fetch_scale=scale, launches=v.get("launches"),
                       hbm_bytes_per_launch=(scale * v["FETCH_SIZE"] + v["WRITE_SIZE"]) * 1024.0)
-note = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes (counters only) over `python bench.py --steps 20 --warmup 2 "
+note = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes (counters only) over `python bench.py --full --steps 20 --warmup 2 "
         "--repetitions 1 --no-cpu-baseline` (tools/round_profile.sh %s); KB per launch, averaged over all launches of the run. gfx950 "
         "correction (MI355X_MICROARCH.md §HBM): FETCH_SIZE tallies 128-B requests at 64 B — calibrated in the same run on copy_kernel "
         "(256 MiB copied: FETCH_SIZE %s KB, WRITE_SIZE %s KB) — so fetch bytes = 2 x FETCH_SIZE for 8/16-B-per-lane streams; the "

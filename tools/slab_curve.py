@@ -7,7 +7,7 @@ tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 cfg = sys.argv[2] if len(sys.argv) > 2 else "default"   # flux configuration; "corrected" writes slab_curve_corrected.json
 out = {}
 for ranks, ny in ((1, 560), (2, 280), (4, 140), (8, 70)):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--ny", str(ny), "--no-cpu-baseline", "--no-sorted-pass", "--flux-configuration", cfg], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--ny", str(ny), "--full", "--no-cpu-baseline", "--no-sorted-pass", "--flux-configuration", cfg], capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not line:
         print(ny, "FAILED", r.stderr[-500:]); continue
