@@ -18,6 +18,9 @@
  *        element (i, j), 0-based interior index, lives at
  *        ptr[(j + hy) * (nx + 2*hx) + (i + hx)].
  *    For 3-D ocean fields pass the pointer to the k = Nz level slab.
+ *  - footprints (the "Footprint:" line of each entry point): W is the ring window, cells (i, j) with −ring ≤ i < nx + ring,
+ *    −ring ≤ j < ny + ring; I is the interior (ring 0).  Nothing outside the stated read set is read, nothing outside the
+ *    write set is written, and pointers need only the element type's alignment (tests/test_layout_footprint.py).
  *  - all entry points return 0 on success, <0 on error; cf_last_error() explains.
  *    Nothing throws across the ABI.
  *  - a context is single-threaded; different contexts may be used from different threads.
@@ -499,17 +502,25 @@ int cf_d2h(cf_ctx* ctx, void* h_dst, const void* d_src, size_t bytes);
 /* interpolate_atmosphere_state!(interfaces, atmosphere::JRA55PrescribedAtmosphere, model)
  * (construction site atmosphere.jl:20-29, README.md:74): bilinear in (λ,φ) × linear in time,
  * rain+snow summed, winds rotated to the grid frame.                                           */
+/* Footprint: reads the whole source window, fi / fj at the window's columns / rows (separable) or cells, cos/sin_rot on the
+ * window W (ring window); writes the eight exchange fields on W only.                                                   */
 int cf_interpolate_atmosphere_state(cf_ctx* ctx, const cf_atmos_source* src,
                                     const cf_interp_weights* w, const cf_exchange_fields* out);
 
 /* compute_atmosphere_ocean_fluxes!(coupled_model) with SimilarityTheoryFluxes
  * (omip_simulation.jl:42-49; README.md:75): the per-cell Monin–Obukhov fixed point.            */
+/* Footprint: reads atmosphere u, v, T, p, q (the certified path also Mp) and ocean T, S, mask on W, ocean u also at
+ * i + 1 and v also at j + 1; writes every flux output and `iterations` on W, land cells included, nothing else.       */
 int cf_compute_atmosphere_ocean_fluxes(cf_ctx* ctx, const cf_ocean_surface* ocean,
                                        const cf_exchange_fields* atmos,
                                        const cf_interface_fluxes* out);
 
 /* compute_net_ocean_fluxes!(coupled_model): radiation (atmosphere.jl:41-44) + (1−ℵ) partition +
  * unit conversion → τx, τy, JT, JS (omip_diagnostics.jl:77-80).                                 */
+/* Footprint: interior I only.  Reads S, mask, the cell-local fluxes, Qs, Ql, Mp, the ice fields and latitude at the cell,
+ * ρτx and ℵ also at i − 1, ρτy and ℵ also at j − 1 (ocean T, u, v and atmosphere u, v, T, p, q must be non-NULL but are
+ * not read); writes the net fields on I, land included.  With ring = 0 the flux halo column i = −1 and row j = −1 are
+ * not computed by anyone: the caller fills them (zeros, or a halo exchange) before the face stresses read them.       */
 int cf_compute_net_ocean_fluxes(cf_ctx* ctx, const cf_ocean_surface* ocean,
                                 const cf_exchange_fields* atmos,
                                 const cf_interface_fluxes* fluxes,
@@ -519,6 +530,8 @@ int cf_compute_net_ocean_fluxes(cf_ctx* ctx, const cf_ocean_surface* ocean,
 
 /* update_state!(coupled_model) (NEMOTKE/nemo_tke_compute_closure_fields.jl:7-8): the three
  * stages above back to back on the context's stream (three launches, no host synchronisation).  */
+/* Footprint: the union of the three: writes exchange and flux fields on W, net fields on I (every option of
+ * CF_OPT_FUSED_NET / _MERGED_PREFETCH / _LATENCY_LAYOUT / _SOLVER_PATH alike; cf_time_steps likewise, per step).      */
 int cf_update_state(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
                     const cf_ocean_surface* ocean, const cf_exchange_fields* atmos,
                     const cf_interface_fluxes* fluxes, const cf_sea_ice_fields* ice,
@@ -625,6 +638,7 @@ int cf_default_sea_ice_albedo_params(cf_sea_ice_albedo_params* p);
  * is NULL (params = NULL: back to the constant albedo of cf_sea_ice_params).                                       */
 int cf_set_sea_ice_albedo(cf_ctx* ctx, const cf_sea_ice_albedo_params* params);
 /* The albedo field on its own (diagnostics, tests): d_albedo[k] = SeaIceAlbedo(hᵢ, hₛ, Tₛ) for every ocean-grid cell. */
+/* Footprint: reads and writes every cell of the parent arrays, halos included.                                      */
 int cf_compute_sea_ice_albedo(cf_ctx* ctx, const cf_sea_ice_albedo_params* params, const double* d_ice_thickness,
                               const double* d_snow_thickness /* may be NULL */, const double* d_top_temperature,
                               double* d_albedo);
@@ -666,6 +680,7 @@ typedef struct cf_ice_ocean_fluxes {
     double* frazil_heat;      /* Q_frazil (may be NULL)                           */
     double* friction_velocity;/* u★ (optional diagnostic, may be NULL)           */
 } cf_ice_ocean_fluxes;
+/* Footprint: reads T, S, mask, ℵ on I, x_stress also at i + 1, y_stress also at j + 1; writes its outputs on I only.   */
 int cf_compute_sea_ice_ocean_fluxes(cf_ctx* ctx, const cf_ice_ocean_params* params, const cf_ocean_surface* ocean,
                                     const double* d_concentration, const double* d_x_stress /* u-faces, kinematic */,
                                     const double* d_y_stress /* v-faces */, const cf_ice_ocean_fluxes* out);
@@ -674,6 +689,8 @@ int cf_compute_sea_ice_ocean_fluxes(cf_ctx* ctx, const cf_ice_ocean_params* para
 int cf_set_sea_ice_formulation(cf_ctx* ctx, const cf_flux_params* ice_fluxes, const cf_sea_ice_params* ice);
 /* compute_atmosphere_sea_ice_fluxes!(coupled_model): out.temperature receives the new skin temperature
  * [°C]; latent_heat uses the sublimation enthalpy.  Needs exchange fields Qs, Ql as well. */
+/* Footprint: reads atmosphere u, v, T, p, q, Qs, Ql, the ice state and ocean S, mask on W; writes the interface fluxes and
+ * `iterations` on W; a top_temperature that is out->temperature keeps its input bits outside W.                        */
 int cf_compute_atmosphere_sea_ice_fluxes(cf_ctx* ctx, const cf_sea_ice_state* ice, const cf_ocean_surface* ocean,
                                          const cf_exchange_fields* atmos, const cf_interface_fluxes* out);
 
@@ -687,6 +704,7 @@ typedef struct cf_net_sea_ice_fluxes {
     double* top_heat;     /* ΣQt */
     double* bottom_heat;  /* ΣQb */
 } cf_net_sea_ice_fluxes;
+/* Footprint: reads its inputs and writes top_heat / bottom_heat on I only.                                            */
 int cf_compute_net_sea_ice_fluxes(cf_ctx* ctx, const cf_sea_ice_state* ice, const cf_ocean_surface* ocean,
                                   const cf_exchange_fields* atmos, const cf_interface_fluxes* ai_fluxes,
                                   const double* frazil_heat, const double* interface_heat,
@@ -696,6 +714,7 @@ int cf_compute_net_sea_ice_fluxes(cf_ctx* ctx, const cf_sea_ice_state* ice, cons
  * followed by cf_compute_atmosphere_sea_ice_fluxes and cf_compute_net_sea_ice_fluxes on the same stream — five
  * launches, no host synchronisation.  `ice_partition` (ℵ, ice–ocean fluxes) feeds the ocean partition, `ice_state`
  * the interface solve; `ai_fluxes->temperature` receives the new skin temperature. */
+/* Footprint: cf_update_state's, then the interface solve's (W) and the net sea-ice fluxes' (I).                         */
 int cf_update_state_sea_ice(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
                             const cf_ocean_surface* ocean, const cf_exchange_fields* atmos,
                             const cf_interface_fluxes* ao_fluxes, const cf_sea_ice_fields* ice_partition,
@@ -717,6 +736,7 @@ typedef struct cf_land_source {
     int32_t ns_x, ns_y, n_levels, level1, level2, reserved;
     double time_fraction;
 } cf_land_source;
+/* Footprint (cf_interpolate_land_freshwater): reads both sources in full and fi / fj as the atmosphere does; writes d_out on W. */
 int cf_interpolate_land_freshwater(cf_ctx* ctx, const cf_land_source* src, const cf_interp_weights* w, double* d_out);
 int cf_set_land_freshwater(cf_ctx* ctx, const double* d_land_freshwater /* ocean-grid field, kg m⁻² s⁻¹, or NULL */);
 
@@ -725,6 +745,7 @@ int cf_set_land_freshwater(cf_ctx* ctx, const double* d_land_freshwater /* ocean
  * 507-523): `_materialize_top_flux!` evaluates it into a 2-D buffer, J_add = v_p (Sₒ − S★) on wet cells (positive = salt
  * leaves where the surface is saltier than the target).  The buffer is what cf_normalize_salinity_flux takes as
  * d_additional; the ocean applies flux_field + additional.                                                      */
+/* Footprint: reads S★, S, mask on I; writes d_buffer on I only (0 on land).                                           */
 int cf_materialize_salinity_restoring(cf_ctx* ctx, double piston_velocity /* m/s */, const double* d_target_salinity,
                                       const cf_ocean_surface* ocean, double* d_buffer);
 
@@ -736,6 +757,7 @@ int cf_materialize_salinity_restoring(cf_ctx* ctx, double piston_velocity /* m/s
  * flux (SurfaceFluxRestoring …) or NULL.  With an initialised communicator (cf_comm_init) the two sums
  * are all-reduced over the ranks (one RCCL all-reduce of two doubles) so that every slab subtracts the
  * same global mean.  The mean is also written to d_mean_out (device double, may be NULL).            */
+/* Footprint: reads flux, additional, area, mask on I; writes EVERY cell of d_flux (halos: input − mean) and *d_mean_out. */
 int cf_normalize_salinity_flux(cf_ctx* ctx, double* d_flux, const double* d_additional, const double* d_area,
                                const void* d_mask, double* d_mean_out);
 
@@ -804,6 +826,8 @@ int cf_halo_exchange_rows(cf_ctx* ctx, double* const* d_fields, int nfields, int
 #define CF_PEER_HANDLE_BYTES 64
 int cf_peer_halo_export(cf_ctx* ctx, int max_fields, int max_rows, void* handle_out);
 int cf_peer_halo_connect(cf_ctx* ctx, const void* south_handle, const void* north_handle, int rank, int nranks);
+/* Footprint: sends the `rows` boundary rows, full width nx + 2hx, and writes the `rows` halo rows next to each neighbour,
+ * full width; no other cell.                                                                                            */
 int cf_halo_exchange_rows_peer(cf_ctx* ctx, double* const* d_fields, int nfields, int rows);
 /* How many peer-direct exchanges this context has issued, and how many of them rode in a solver launch
  * (CF_OPT_HALO_IN_SOLVER_LAUNCH) instead of the exchange kernel of their own.  A measurement / test aid.      */
@@ -824,6 +848,8 @@ int cf_peer_halo_stats(cf_ctx* ctx, unsigned long long* exchanges, unsigned long
 #define CF_FOLD_X_FACE 1
 #define CF_FOLD_Y_FACE 2
 /* `nfields` fields in one launch: locations[f] ∈ CF_FOLD_*, signs[f] = ±1. */
+/* Footprint: reads rows ny − 1 − rows … ny − 1 at interior columns; writes north halo rows ny … ny + rows − 1 over the full
+ * width nx + 2hx; no other cell.                                                                                       */
 int cf_fold_north_halo(cf_ctx* ctx, double* const* d_fields, const int* locations, const double* signs, int nfields,
                        int rows);
 

@@ -182,3 +182,55 @@ def compare_ice_fluxes(got, ref, tol_converged, tol_unconverged=None, maxiter=10
                 {k.split(".")[1]: "%.1e" % v for k, v in worst.items() if str(k).startswith("abandoned_sum_bias")}, worst["abandoned_outliers"],
                 {k.split(".")[1]: "%.2g" % v for k, v in worst.items() if str(k).startswith("abandoned_outlier_max_abs")}))
     return worst
+
+
+# ---------------------------------------------------------------------------------------------
+# Memory the way a caller lays it out: views that start at odd offsets inside larger buffers, and the k = top level slab
+# of a 3-D array (tests/test_layout_footprint.py).  Both are contiguous, so the runtime's is_contiguous() checks pass them.
+# ---------------------------------------------------------------------------------------------
+SENTINEL64 = 0x7FF8DEADBEEF5A5A   # a quiet NaN with a payload: what an untouched f64 output cell must still hold
+SENTINEL32 = 0x7EADBEEF           # the same for the int32 `iterations`
+
+_BITS = {"float64": "int64", "float32": "int32", "int32": "int32", "uint8": "uint8"}
+
+
+def bits_dtype(dtype):
+    """The integer dtype that reads the bits of a `dtype` tensor (torch dtypes)."""
+    import torch
+    return getattr(torch, _BITS[str(dtype).replace("torch.", "")])
+
+
+def _fill(t, fill):
+    """fill a tensor with a value, or (an int for a floating-point tensor) with that bit pattern."""
+    if t.dtype.is_floating_point and isinstance(fill, (int, np.integer)) and not isinstance(fill, bool):
+        signed = np.array([fill], dtype=np.uint64 if t.element_size() == 8 else np.uint32).view(np.int64 if t.element_size() == 8 else np.int32)
+        t.view(bits_dtype(t.dtype)).fill_(int(signed[0]))
+    else:
+        t.fill_(fill)
+    return t
+
+
+def guarded(shape, dtype, *, offset, guard, fill, device="cuda"):
+    """A contiguous device view of `shape` that starts `offset + guard` elements into a fresh buffer: `offset` shifts its
+    alignment (1 double = 8 bytes off the allocation's 256-byte alignment, 1–3 bytes for uint8), and at least `guard`
+    elements of `fill` lie before and after it (buffer_of(view) gives the whole buffer)."""
+    import torch
+    n = int(np.prod(shape))
+    buf = _fill(torch.empty(offset + guard + n + guard, dtype=dtype, device=device), fill)
+    return buf[offset + guard:offset + guard + n].view(shape)
+
+
+def top_slab(nx, ny, hx, hy, *, nz, hz, dtype, fill, device="cuda"):
+    """The k = Nz level of a (Nz + 2Hz, Ny + 2Hy, Nx + 2Hx) array, as models.OceanSimulation hands a 3-D field's surface to
+    the library: its first element sits (Hz + Nz − 1) slabs into the allocation, so with an odd slab size and an odd level
+    the pointer is 8- but not 16-byte aligned.  Every other level is the guard."""
+    import torch
+    full = _fill(torch.empty((nz + 2 * hz, ny + 2 * hy, nx + 2 * hx), dtype=dtype, device=device), fill)
+    return full[hz + nz - 1]
+
+
+def buffer_of(view):
+    """(flat buffer, first element of `view` in it) of a view made by guarded() or top_slab()."""
+    base = view._base if view._base is not None else view
+    return base.reshape(-1), view.storage_offset() - base.storage_offset()
+
