@@ -6,7 +6,7 @@ the value the library reports and that every declared symbol is exported.
 import ctypes as C
 import os
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
 HALO_NONE, HALO_RCCL, HALO_PEER = 0, 1, 2
@@ -29,6 +29,7 @@ OPT_INTERP_TILE_CAP, OPT_AO_CHUNK = 1, 4   # experiment options: the library acc
 OPT_SOLVER_PATH, OPT_CERTIFIED_BUDGET, OPT_ICE_FREE_CELLS, OPT_LATENCY_LAYOUT, OPT_HALO_IN_SOLVER_LAUNCH = 10, 11, 12, 13, 14
 ICE_FREE_ITERATE, ICE_FREE_ZERO = 0, 1
 PIPELINE_WITHIN_CALL, PIPELINE_CONTINUING = 1, 2   # cf_run_schedule.pipeline
+AVERAGE_MAX_FIELDS = 16                            # fields of one time averager (cf_average_create)
 SOLVER_PATH_EXACT, SOLVER_PATH_CERTIFIED = 0, 1      # how the Monin–Obukhov fixed point is reached (include/coflux.h)
 CERTIFIED_EXACT_FLAG = 0x100                         # `iterations` of a cell the certified path solved on the exact path
 SOLVER_TABLES, SOLVER_LIBM = 0, 1
@@ -209,6 +210,7 @@ EXPORTED_SYMBOLS = (
     "cf_window_create", "cf_window_destroy", "cf_window_host_buffer", "cf_window_wait_slot", "cf_window_commit",
     "cf_window_upload", "cf_window_find", "cf_window_source",
     "cf_ensure_chunk_table", "cf_solver_path", "cf_solver_iteration_path", "cf_solver_latency_layout", "cf_comm_count", "cf_build_stamp", "cf_discard_prefetched_atmosphere_state",
+    "cf_average_create", "cf_average_destroy", "cf_average_reset", "cf_average_collect", "cf_average_weight", "cf_attach_average",
 )
 
 PACKAGE_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -342,6 +344,12 @@ def load_library(path=None):
     lib.cf_window_upload.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     lib.cf_window_find.argtypes = [vp, C.c_int64]
     lib.cf_window_source.argtypes = [vp, C.c_int64, C.c_int64, C.c_double, C.POINTER(AtmosSource)]
+    lib.cf_average_create.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.cf_average_destroy.argtypes = [vp]
+    lib.cf_average_reset.argtypes = [vp]
+    lib.cf_average_collect.argtypes = [vp, C.c_double]
+    lib.cf_average_weight.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.cf_attach_average.argtypes = [vp, vp, C.c_int32, C.c_double]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("cf_last_error", "cf_device_alloc", "cf_window_host_buffer", "cf_build_stamp"):

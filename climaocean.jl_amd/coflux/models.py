@@ -630,15 +630,21 @@ class Simulation:
     dt: float = 20 * minutes          # README.md:76
     stop_time: float = float("inf")
     stop_iteration: int = 2 ** 62
+    output_writers: dict = field(default_factory=dict)   # simulation.output_writers[:surface] = … (omip_diagnostics.jl:152-158)
 
 
 def run(simulation):
-    """run!(simulation) — README.md:77."""
+    """run!(simulation) — README.md:77.  After every time_step! each of `simulation.output_writers` is given the clock."""
     m = simulation.model
+    writers = list(simulation.output_writers.values())
+    for writer in writers:
+        writer.initialize(simulation)
     m._pipeline_dt = simulation.dt   # (update_state requests every next atmosphere state: see there)
     try:
         while m.clock.time < simulation.stop_time and m.clock.iteration < simulation.stop_iteration:
             time_step(m, simulation.dt)
+            for writer in writers:
+                writer.write(m.clock)
     finally:
         m._pipeline_dt = None
         itf = m.interfaces
@@ -655,6 +661,98 @@ def run(simulation):
             itf.context.set_option(abi.OPT_MERGED_PREFETCH, 0)
             itf._tail_mode = False
     m.interfaces.context.sync()
+
+
+# ---------------------------------------------------------------------------------------------
+# time-averaged output (Oceananigans' AveragedTimeInterval / WindowedTimeAverage, accumulated on the device)
+# ---------------------------------------------------------------------------------------------
+class AveragedTimeInterval:
+    """AveragedTimeInterval(interval; window = interval, stride = 1) — the schedule of the reference's averaged writers
+    (omip_diagnostics.jl:152-158, examples/latitude_longitude_ocean_sea_ice.jl:60-66).  Window k is (t_k − window, t_k] with
+    t_k = k · interval.  Inside a window a step's sample is taken when iteration % stride == 0, and always at t_k; its
+    weight is the time since the previous sample or since the window opened, t_n − max(t_prev, t_k − window).  The time
+    step must divide `interval`.  Host bookkeeping only: sample() says what to collect, the writer collects it."""
+
+    def __init__(self, interval, window=None, stride=1):
+        window = interval if window is None else window
+        if not (interval > 0) or not (0 < window <= interval):
+            raise ValueError(f"AveragedTimeInterval: interval = {interval}, window = {window} (0 < window ≤ interval)")
+        if int(stride) != stride or stride < 1:
+            raise ValueError(f"AveragedTimeInterval: stride = {stride} (an integer ≥ 1)")
+        self.interval, self.window, self.stride = float(interval), float(window), int(stride)
+        self.k = None             # the open window ends at k · interval
+        self.previous = None      # time of the last sample
+
+    def initialize(self, time, dt):
+        """Checks the time step; the first call also opens the first window that ends after `time` (an open window survives
+        the end of run!, as in Oceananigans)."""
+        ratio = self.interval / dt if dt > 0 else 0.0
+        if round(ratio) < 1 or abs(ratio - round(ratio)) > 1e-9 * ratio:
+            raise ValueError(f"AveragedTimeInterval: the time step {dt} does not divide the interval {self.interval}")
+        self._tol = 1e-6 * dt
+        if self.k is None:
+            self.k = int(np.floor((time + self._tol) / self.interval)) + 1
+            self.previous = float(time)
+
+    def sample(self, time, iteration):
+        """(weight, t_k) for the step that has just reached `time`: weight is None when nothing is collected, t_k is the end
+        of the window that this sample completes (None while it stays open)."""
+        t_k = self.k * self.interval
+        end = time >= t_k - self._tol
+        if end:
+            time = t_k
+        start = t_k - self.window
+        if time <= start + self._tol or (not end and iteration % self.stride != 0):
+            return None, None
+        weight = time - max(self.previous, start)
+        self.previous = time
+        if not end:
+            return weight, None
+        self.k += 1
+        return weight, t_k
+
+
+# the OMIP surface diagnostics (omip_diagnostics.jl:125-130): CMIP name → interface field
+SURFACE_FLUX_OUTPUTS = (("tauuo", "net", "u"), ("tauvo", "net", "v"), ("hfds", "net", "T"), ("wfo", "net", "S"),
+                        ("hfss", "atmosphere_ocean", "sensible_heat"), ("hfls", "atmosphere_ocean", "latent_heat"))
+
+
+class SurfaceFluxAverages:
+    """An averaged output writer for surface fields: SurfaceFluxAverages(model; outputs, schedule = AveragedTimeInterval(5days)).
+    The default outputs are the OMIP set tauuo, tauvo, hfds, wfo (the ocean's net u, v, T, S fluxes) and hfss, hfls (the
+    atmosphere–ocean interface's sensible and latent heat); any dict name → ocean-grid device field works, sea-ice fields
+    included.  The means are accumulated on the device (cf_average_collect: one launch per sample); a completed window is
+    appended to `windows` as (t_k, {name: interior numpy array}) and handed to `on_window(t_k, arrays)`.  No file format."""
+
+    def __init__(self, model, outputs=None, schedule=None, on_window=None):
+        itf = model.interfaces
+        if outputs is None:
+            groups = dict(net=itf.net_fluxes._ocean_fields, atmosphere_ocean=itf.atmosphere_ocean_interface._fields)
+            outputs = {name: groups[group][key] for name, group, key in SURFACE_FLUX_OUTPUTS}
+        self.model, self.outputs = model, dict(outputs)
+        self.schedule = schedule if schedule is not None else AveragedTimeInterval(5 * days)
+        self.on_window = on_window
+        ctx = itf.context
+        self.means = {name: ctx.zeros() for name in self.outputs}
+        self.averager = ctx.average(list(self.outputs.values()), list(self.means.values()))
+        self.windows = []
+        g = model.ocean.grid
+        (self._nx, self._ny, _), (self._hx, self._hy, _) = g.size, g.halo
+
+    def initialize(self, simulation):
+        self.schedule.initialize(self.model.clock.time, simulation.dt)
+
+    def write(self, clock):
+        weight, t_k = self.schedule.sample(clock.time, clock.iteration)
+        if weight is not None:
+            self.averager.collect(weight)
+        if t_k is not None:
+            hx, hy = self._hx, self._hy
+            arrays = {name: m[hy:hy + self._ny, hx:hx + self._nx].to("cpu", copy=True).numpy() for name, m in self.means.items()}
+            self.averager.reset()
+            self.windows.append((t_k, arrays))
+            if self.on_window is not None:
+                self.on_window(t_k, arrays)
 
 
 class JRA55PrescribedLand:

@@ -375,6 +375,19 @@ class FluxContext:
                                            C.byref(f), C.byref(i) if i is not None else None, C.byref(n)),
                     "cf_time_steps")
 
+    # -- time averages ----------------------------------------------------------------------------
+    def average(self, sources, means):
+        """A device-side running mean of `sources` into `means` (cf_average_create): lists of up to abi.AVERAGE_MAX_FIELDS
+        ocean-grid float64 fields; collect(weight) after each sample, read the means, reset() for the next window."""
+        return TimeAverager(self, sources, means)
+
+    def attach_average(self, averager, stride=1, step_weight=1.0):
+        """time_steps() collects `averager` after every step s with (s + 1) % stride == 0, weight stride · step_weight
+        (cf_attach_average); None detaches."""
+        h = averager._h if averager is not None else None
+        self._attached_average = averager
+        self._check(self.lib.cf_attach_average(self._h, h, int(stride), float(step_weight)), "cf_attach_average")
+
     # -- peer-direct halo rows / tripolar fold -----------------------------------------------------
     def peer_halo_export(self, max_fields=4, max_rows=2):
         buf = C.create_string_buffer(abi.PEER_HANDLE_BYTES)
@@ -417,6 +430,54 @@ class FluxContext:
     def halo_exchange_rows(self, tensors, rows=1):
         arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
         self._check(self.lib.cf_halo_exchange_rows(self._h, arr, len(tensors), rows), "cf_halo_exchange_rows")
+
+
+class TimeAverager:
+    """cf_average_*: after collections of weights w₁ … wₙ every `means[k]` holds Σ w f / Σ w of `sources[k]` on the interior
+    (halos untouched), accumulated on the device in one launch per collection.  The library borrows the pointers: the tensors
+    are kept alive here."""
+
+    def __init__(self, ctx, sources, means):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.sources, self.means = list(sources), list(means)
+        if len(self.sources) != len(self.means):
+            raise ValueError(f"{len(self.sources)} sources, {len(self.means)} means")
+        for t in self.sources + self.means:
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == ctx.shape):
+                raise ValueError(f"averaged fields are contiguous float64 device arrays of shape {ctx.shape}")
+        n = len(self.sources)
+        src = (C.c_void_p * n)(*[t.data_ptr() for t in self.sources])
+        dst = (C.c_void_p * n)(*[t.data_ptr() for t in self.means])
+        h = C.c_void_p()
+        ctx._check(self.lib.cf_average_create(ctx._h, n, src, dst, C.byref(h)), "cf_average_create")
+        self._h = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise CofluxError(f"{what} failed ({rc}): {self.lib.cf_last_error(None).decode()}")
+
+    def collect(self, weight):
+        self._check(self.lib.cf_average_collect(self._h, float(weight)), "cf_average_collect")
+
+    def reset(self):
+        self._check(self.lib.cf_average_reset(self._h), "cf_average_reset")
+
+    def weight(self):
+        """(total weight, collections) of the current window."""
+        total, samples = C.c_double(), C.c_int64()
+        self._check(self.lib.cf_average_weight(self._h, C.byref(total), C.byref(samples)), "cf_average_weight")
+        return total.value, samples.value
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self.lib.cf_average_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class SnapshotWindow:

@@ -1,0 +1,112 @@
+// coflux_average.cpp — time averages of surface fields accumulated on the device (include/coflux.h: cf_average_*,
+// cf_attach_average; the kernel is coflux_average.hip).  The host keeps each window's total weight and turns a collection
+// of weight w into the two coefficients of the running mean; the device does one launch per collection.
+#include "coflux_ctx.hpp"
+
+int average_collect(cf_average* a, double weight) {
+    cf_ctx* ctx = a->ctx;
+    const double total = a->total + weight;
+    const bool store = a->samples == 0;
+    const double c_prev = store ? 0.0 : a->total / total;
+    const double c_new = store ? 1.0 : weight / total;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_average(ctx->stream, a->fields, a->nfields, ctx->grid, store, c_prev, c_new));
+    a->total = total;
+    ++a->samples;
+    return CF_OK;
+}
+
+void average_forget_context(cf_ctx* ctx) {
+    for (cf_average* a : ctx->averages) a->ctx = nullptr;
+    ctx->averages.clear();
+    ctx->average = nullptr;
+}
+
+static int live(cf_average* a, const char* what) {
+    if (!a) return fail(nullptr, CF_ERR_INVALID, "%s: averager is NULL", what);
+    if (!a->ctx) return fail(nullptr, CF_ERR_INVALID, "%s: the averager's context has been destroyed", what);
+    return CF_OK;
+}
+
+extern "C" {
+
+int cf_average_create(cf_ctx* ctx, int nfields, const double* const* d_sources, double* const* d_means, cf_average** out) {
+    if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
+    if (!out || !d_sources || !d_means) return fail(ctx, CF_ERR_INVALID, "cf_average_create: NULL argument");
+    *out = nullptr;
+    if (nfields < 1 || nfields > CF_AVERAGE_MAX_FIELDS)
+        return fail(ctx, CF_ERR_INVALID, "cf_average_create: %d fields (1…%d)", nfields, CF_AVERAGE_MAX_FIELDS);
+    const GridDesc& G = ctx->grid;
+    const uintptr_t bytes = (uintptr_t)G.sj * (uintptr_t)(G.ny + 2 * G.hy) * sizeof(double);
+    auto overlap = [&](const void* p, const void* q) {
+        const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
+        return x < y + bytes && y < x + bytes;
+    };
+    for (int f = 0; f < nfields; ++f)
+        if (!d_sources[f] || !d_means[f]) return fail(ctx, CF_ERR_INVALID, "cf_average_create: field %d has a NULL pointer", f);
+    for (int f = 0; f < nfields; ++f)
+        for (int g = 0; g < nfields; ++g) {
+            if (overlap(d_means[f], d_sources[g]))
+                return fail(ctx, CF_ERR_INVALID, "cf_average_create: mean %d overlaps source %d", f, g);
+            if (g != f && overlap(d_means[f], d_means[g]))
+                return fail(ctx, CF_ERR_INVALID, "cf_average_create: means %d and %d overlap", f, g);
+        }
+    cf_average* a = new cf_average();
+    a->ctx = ctx;
+    a->nfields = nfields;
+    for (int f = 0; f < nfields; ++f) {
+        a->fields.src[f] = d_sources[f];
+        a->fields.mean[f] = d_means[f];
+    }
+    ctx->averages.push_back(a);
+    *out = a;
+    return CF_OK;
+}
+
+int cf_average_destroy(cf_average* a) {
+    if (!a) return CF_OK;
+    if (cf_ctx* ctx = a->ctx) {
+        if (ctx->average == a) ctx->average = nullptr;
+        ctx->averages.erase(std::remove(ctx->averages.begin(), ctx->averages.end(), a), ctx->averages.end());
+    }
+    delete a;
+    return CF_OK;
+}
+
+int cf_average_reset(cf_average* a) {
+    CHECK(live(a, "cf_average_reset"));
+    a->total = 0.0;
+    a->samples = 0;
+    return CF_OK;
+}
+
+int cf_average_collect(cf_average* a, double weight) {
+    CHECK(live(a, "cf_average_collect"));
+    if (!(weight > 0.0) || !std::isfinite(weight) || !std::isfinite(a->total + weight))
+        return fail(a->ctx, CF_ERR_INVALID, "cf_average_collect: weight %g (> 0 and finite)", weight);
+    return average_collect(a, weight);
+}
+
+int cf_average_weight(cf_average* a, double* total, int64_t* samples) {
+    CHECK(live(a, "cf_average_weight"));
+    if (total) *total = a->total;
+    if (samples) *samples = a->samples;
+    return CF_OK;
+}
+
+int cf_attach_average(cf_ctx* ctx, cf_average* a, int32_t stride, double step_weight) {
+    if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
+    if (!a) {
+        ctx->average = nullptr;
+        return CF_OK;
+    }
+    if (a->ctx != ctx) return fail(ctx, CF_ERR_INVALID, "cf_attach_average: the averager belongs to another context");
+    if (stride < 1 || !(step_weight > 0.0) || !std::isfinite(step_weight * stride))
+        return fail(ctx, CF_ERR_INVALID, "cf_attach_average: stride %d (≥ 1), step weight %g (> 0 and finite)", stride, step_weight);
+    ctx->average = a;
+    ctx->average_stride = stride;
+    ctx->average_step_weight = step_weight;
+    return CF_OK;
+}
+
+}  // extern "C"

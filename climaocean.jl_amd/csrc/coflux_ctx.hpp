@@ -147,6 +147,20 @@ struct cf_ctx {
     // per-kernel event recorder (cf_profile_enable): 4 events per recorded update_state
     std::vector<hipEvent_t> prof_events;
     int prof_capacity = 0, prof_count = 0;
+    // time averages (coflux_average.cpp): every averager made on this context (cf_destroy orphans them), and the one
+    // cf_time_steps collects (cf_attach_average)
+    std::vector<cf_average*> averages;
+    cf_average* average = nullptr;
+    int32_t average_stride = 1;
+    double average_step_weight = 0.0;
+};
+
+struct cf_average {
+    cf_ctx* ctx = nullptr;   // NULL once the context is destroyed
+    int nfields = 0;
+    AverageFields fields{};
+    double total = 0.0;      // the window's total weight
+    int64_t samples = 0;
 };
 
 // sets the thread-local and the context's last-error text and returns `code`
@@ -168,5 +182,9 @@ int cf_fail(cf_ctx* ctx, int code, const char* fmt, ...);
 
 // coflux_steps.cpp: the stand-alone peer-direct exchange kernel for `F` (counts the exchange in ctx->peer_seq)
 extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows);
+// coflux_average.cpp: one collection of `a` (cf_average_collect without the argument checks of the ABI entry)
+int average_collect(cf_average* a, double weight);
+// coflux_average.cpp: cf_destroy orphans the context's averagers
+void average_forget_context(cf_ctx* ctx);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state)
 extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx);

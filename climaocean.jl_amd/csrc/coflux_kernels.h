@@ -149,5 +149,12 @@ hipError_t launch_peer_halo(hipStream_t st, const PeerMailbox& M, const PeerFiel
                             unsigned long long seq, int* d_status);
 hipError_t launch_fold_north(hipStream_t st, const FoldFields& F, const GridDesc& G, int rows);
 hipError_t launch_copy(hipStream_t st, void* dst, const void* src, size_t bytes);
+// cf_average_collect (coflux_average.hip): every field's interior mean m ← f (store) or m ← (m · c_prev) + (f · c_new), one launch
+struct AverageFields {
+    const double* src[CF_AVERAGE_MAX_FIELDS];
+    double* mean[CF_AVERAGE_MAX_FIELDS];
+};
+hipError_t launch_average(hipStream_t st, const AverageFields& F, int nfields, const GridDesc& G, bool store, double c_prev,
+                          double c_new);
 
 }  // namespace coflux

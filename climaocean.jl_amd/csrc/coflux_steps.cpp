@@ -374,6 +374,10 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
             CHECK(cf_prefetch_atmosphere_state(ctx, &sn, w, &S->atmos[(step + 1) % 2]));
         }
         CHECK(cf_update_state(ctx, &s, w, o, a, fluxes, ice, net));
+        // an attached averager (cf_attach_average) collects on the GLOBAL step index: a run split into several calls collects
+        // the same steps.  Queued behind every launch of the step — the face stresses of the merged and tail forms included
+        if (ctx->average && (step + 1) % ctx->average_stride == 0)
+            CHECK(average_collect(ctx->average, ctx->average_stride * ctx->average_step_weight));
     }
     return CF_OK;
 }

@@ -318,6 +318,33 @@ time_steps!(b, first_step, nsteps, sched::CfRunSchedule, src, w, fluxes, ice, ne
                        (Ptr{Cvoid}, Int64, Cint, Ref{CfRunSchedule}, Ref{CfAtmosSource}, Ref{CfInterpWeights}, Ref{CfInterfaceFluxes},
                         Ptr{CfSeaIceFields}, Ref{CfNetOceanFluxes}), b.ctx, first_step, nsteps, sched, src, w, fluxes, ice, net))
 
+# ---- time averages on the device: AveragedTimeInterval output of surface fields (omip_diagnostics.jl:152-158) -----------
+# An averager keeps running means of up to 16 ocean-grid fields (one launch per collection); the caller reads the means at
+# the end of a window, then reset!s.  attach_average! makes time_steps! collect it every `stride` steps.
+mutable struct CoFluxAverage
+    ptr::Ptr{Cvoid}
+    backend::CoFluxBackend
+    sources::Vector{Ptr{Float64}}; means::Vector{Ptr{Float64}}
+end
+function CoFluxAverage(b::CoFluxBackend, sources::Vector{Ptr{Float64}}, means::Vector{Ptr{Float64}})
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(b.ctx, ccall((:cf_average_create, libcoflux), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ref{Ptr{Cvoid}}),
+                       b.ctx, length(sources), sources, means, out))
+    a = CoFluxAverage(out[], b, sources, means)
+    finalizer(x -> ccall((:cf_average_destroy, libcoflux), Cint, (Ptr{Cvoid},), x.ptr), a)
+    return a
+end
+reset!(a::CoFluxAverage) = check(C_NULL, ccall((:cf_average_reset, libcoflux), Cint, (Ptr{Cvoid},), a.ptr))
+collect!(a::CoFluxAverage, weight) = check(C_NULL, ccall((:cf_average_collect, libcoflux), Cint, (Ptr{Cvoid}, Float64), a.ptr, weight))
+function average_weight(a::CoFluxAverage)
+    total = Ref{Float64}(0); samples = Ref{Int64}(0)
+    check(C_NULL, ccall((:cf_average_weight, libcoflux), Cint, (Ptr{Cvoid}, Ref{Float64}, Ref{Int64}), a.ptr, total, samples))
+    return (total = total[], samples = samples[])
+end
+attach_average!(b, a::Union{Nothing, CoFluxAverage}, stride = 1, step_weight = 1.0) =
+    check(b.ctx, ccall((:cf_attach_average, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64),
+                       b.ctx, isnothing(a) ? C_NULL : a.ptr, stride, step_weight))
+
 # ---- SeaIceAlbedo(hi, hs, Ts) (atmosphere.jl:30-44) and compute_sea_ice_ocean_fluxes! (omip_simulation.jl:71-77) ------
 mutable struct CfSeaIceAlbedoParams
     struct_size::Int32; reserved::Int32

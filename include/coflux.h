@@ -36,9 +36,10 @@
 extern "C" {
 #endif
 
-#define CF_ABI_VERSION 3 /* 2: cf_flux_params.shear_gustiness_coefficient; 3: CF_OPT_MAX_BLOCKS, CF_OPT_PROFILE_STRIDE, CF_OPT_FUSED_INTERP,
+#define CF_ABI_VERSION 4 /* 2: cf_flux_params.shear_gustiness_coefficient; 3: CF_OPT_MAX_BLOCKS, CF_OPT_PROFILE_STRIDE, CF_OPT_FUSED_INTERP,
                           * CF_SOLVER_TABLES_R2(_OUTER) and the 768-thread geometry (CF_OPT_AO_CHUNK = 3072) retired; CF_OPT_AO_CHUNK and
-                          * CF_OPT_INTERP_TILE_CAP are experiment options (COFLUX_EXPERIMENTS=1) */
+                          * CF_OPT_INTERP_TILE_CAP are experiment options (COFLUX_EXPERIMENTS=1); 4: time averages accumulated on the
+                          * device (cf_average_*, cf_attach_average; cf_run_schedule unchanged) */
 
 /* status codes */
 #define CF_OK 0
@@ -894,6 +895,43 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
                   const cf_atmos_source* src /* levels / fraction are overridden per step */,
                   const cf_interp_weights* w, const cf_interface_fluxes* fluxes, const cf_sea_ice_fields* ice,
                   const cf_net_ocean_fluxes* net);
+
+/* ------------------------------------------------------------------------------------------
+ * Time averages of surface fields on the device: the output that every reference configuration writes, e.g. the OMIP
+ * surface diagnostics tauuo, tauvo, hfds, wfo, hfss, hfls as 5-day means (OMIPConfigurations/omip_diagnostics.jl:125-130,
+ * JLD2Writer(…; schedule = AveragedTimeInterval(surface_averaging_interval)) :152-158).  An averager holds up to
+ * CF_AVERAGE_MAX_FIELDS (source, mean) pairs of ocean-grid arrays in the usual halo layout and a window's total weight.
+ * A collection of weight w is ONE launch over the interior I of every field, the running-mean form of Oceananigans'
+ * WindowedTimeAverage / integrate_average! [UPSTREAM-RECALL]:
+ *     first collection of a window:  m = f                       (m is not read: a fresh buffer may hold NaNs)
+ *     every later one:               m = (m · c_prev) + (f · c_new),  c_prev = T_prev / T_cur, c_new = w / T_cur, T_cur = T_prev + w
+ * with c_prev and c_new computed on the host in double and two products and one sum on the device, each rounded (no FMA).
+ * The mean is therefore valid after every collection: Σ w f / Σ w up to rounding.
+ *   cf_average_create   CF_ERR_INVALID if nfields is outside 1…CF_AVERAGE_MAX_FIELDS, a pointer is NULL, or the parent
+ *                       array of a mean ((nx + 2hx)(ny + 2hy) doubles from its pointer) overlaps a source's or another mean's.
+ *   cf_average_destroy  detaches the averager if it is attached; an averager outlived by its context may still be destroyed
+ *                       (every other call on it then fails).
+ *   cf_average_reset    a new window: total weight 0, the next collection stores.  No device work.
+ *   cf_average_collect  one launch on the context's stream; weight > 0 and finite.  No host synchronisation.
+ *   cf_average_weight   the window's total weight and number of collections (either pointer may be NULL).
+ *   cf_attach_average   cf_time_steps collects `a` after the cf_update_state of every step s (global index) with
+ *                       (s + 1) % stride == 0, weight stride · step_weight; NULL detaches.  One averager per context:
+ *                       attaching another replaces it.  Stream order puts the collection behind every write of the step
+ *                       (every CF_OPT_MERGED_PREFETCH / _HALO_IN_SOLVER_LAUNCH / _SOLVER_PATH / _FUSED_NET mode alike), so a
+ *                       run split into CF_PIPELINE_CONTINUING calls collects the same steps as one call.  Window boundaries
+ *                       are call boundaries: the caller reads the means, then calls cf_average_reset.
+ * ---------------------------------------------------------------------------------------- */
+#define CF_AVERAGE_MAX_FIELDS 16
+typedef struct cf_average cf_average;
+int cf_average_create(cf_ctx* ctx, int nfields, const double* const* d_sources, double* const* d_means, cf_average** out);
+int cf_average_destroy(cf_average* a);
+int cf_average_reset(cf_average* a);
+/* Footprint: reads the sources on I; reads and writes the means on I (the first collection of a window only writes them).
+ * Nothing else is read or written, the halos of the means included.                                                    */
+int cf_average_collect(cf_average* a, double weight);
+int cf_average_weight(cf_average* a, double* total, int64_t* samples);
+/* Footprint: cf_time_steps' own, and cf_average_collect's at every collected step.                                     */
+int cf_attach_average(cf_ctx* ctx, cf_average* a, int32_t stride, double step_weight);
 
 /* Builds the flux solver's schedule for `mask` (the cost-balanced chunk table and the wet lists, three tiny kernels and
  * two 4-byte read-backs) ahead of the first step instead of inside it.  Optional: cf_compute_atmosphere_ocean_fluxes,
