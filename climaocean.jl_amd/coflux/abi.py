@@ -6,12 +6,12 @@ the value the library reports and that every declared symbol is exported.
 import ctypes as C
 import os
 
-ABI_VERSION = 4
+ABI_VERSION = 5   # 5: SKIN_LINEARISED
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
 HALO_NONE, HALO_RCCL, HALO_PEER = 0, 1, 2
 FOLD_CENTER, FOLD_X_FACE, FOLD_Y_FACE = 0, 1, 2
-SKIN_EXPLICIT, SKIN_SEMI_IMPLICIT = 0, 1
+SKIN_EXPLICIT, SKIN_SEMI_IMPLICIT, SKIN_LINEARISED = 0, 1, 2
 
 # enums (values from include/coflux.h)
 SIMILARITY_LOGARITHMIC, SIMILARITY_COARE_LOGARITHMIC = 0, 1

@@ -286,7 +286,9 @@ class SeaIceInterfaceProperties:
     albedo: float = 0.7
     emissivity: float = 1.0                      # atmosphere.jl:44
     temperature_offset: float = 273.15
-    skin_temperature_scheme: int = 0             # abi.SKIN_EXPLICIT (as recalled) / abi.SKIN_SEMI_IMPLICIT (damped form)
+    # abi.SKIN_EXPLICIT (as recalled) / abi.SKIN_SEMI_IMPLICIT (damped form) / abi.SKIN_LINEARISED (one Newton step on the
+    # whole surface energy balance per iteration: converges where the other two orbit; include/coflux.h)
+    skin_temperature_scheme: int = 0
 
     def to_params(self):
         import ctypes

@@ -1161,7 +1161,8 @@ int cf_set_sea_ice_formulation(cf_ctx* ctx, const cf_flux_params* ice_fluxes, co
     if (ice->struct_size != (int32_t)sizeof(cf_sea_ice_params))
         return fail(ctx, CF_ERR_INVALID, "cf_sea_ice_params.struct_size = %d, library expects %zu", ice->struct_size,
                     sizeof(cf_sea_ice_params));
-    if (ice->skin_temperature_scheme != CF_SKIN_EXPLICIT && ice->skin_temperature_scheme != CF_SKIN_SEMI_IMPLICIT)
+    if (ice->skin_temperature_scheme != CF_SKIN_EXPLICIT && ice->skin_temperature_scheme != CF_SKIN_SEMI_IMPLICIT &&
+        ice->skin_temperature_scheme != CF_SKIN_LINEARISED)
         return fail(ctx, CF_ERR_INVALID, "Unknown skin_temperature_scheme: %d", ice->skin_temperature_scheme);
     if (!(ice->conductivity > 0) || !(ice->maximum_temperature_change > 0))
         return fail(ctx, CF_ERR_INVALID, "sea-ice conductivity and maximum temperature change must be > 0");
@@ -1192,7 +1193,7 @@ int cf_set_sea_ice_formulation(cf_ctx* ctx, const cf_flux_params* ice_fluxes, co
     K.eps_sigma = ice->emissivity * ice_fluxes->stefan_boltzmann;
     K.albedo = ice->albedo;
     K.T_offset = ice->temperature_offset;
-    K.semi_implicit = ice->skin_temperature_scheme == CF_SKIN_SEMI_IMPLICIT ? 1.0 : 0.0;
+    K.skin_scheme = (double)ice->skin_temperature_scheme;
     K.orbit_shortcut = ctx->ice_orbit_shortcut ? 1.0 : 0.0;
     K.ice_free_zero = ctx->ice_free_zero ? 1.0 : 0.0;
     ctx->ice_kernel = K;

@@ -391,6 +391,14 @@ constexpr int SOLVER_LY = 3;       // CoefficientBasedFluxes: Large & Yeager ite
 constexpr int SOLVER_SEAICE = 4;   // atmosphere–sea-ice interface: skin temperature inside the iteration (ice_iterate)
 constexpr int SOLVER_SEAICE_LEAN = 6;  // SOLVER_SEAICE with constant roughness lengths and U_G,min > 0 on ice_iterate_lean (coflux_lean.hpp)
 constexpr int SOLVER_OCEAN_LEAN = 5;  // SOLVER_OCEAN's configurations on the round-3 iteration body (mo_iterate_lean): the default
+// SOLVER_SEAICE(_LEAN) under CF_SKIN_LINEARISED: a kernel of its own, so that the other schemes' kernels carry none of its state
+constexpr int SOLVER_SEAICE_LIN = 7;
+constexpr int SOLVER_SEAICE_LEAN_LIN = 8;
+constexpr bool seaice_spec(int spec) {
+    return spec == SOLVER_SEAICE || spec == SOLVER_SEAICE_LEAN || spec == SOLVER_SEAICE_LIN || spec == SOLVER_SEAICE_LEAN_LIN;
+}
+constexpr bool seaice_lean_spec(int spec) { return spec == SOLVER_SEAICE_LEAN || spec == SOLVER_SEAICE_LEAN_LIN; }
+constexpr bool seaice_lin_spec(int spec) { return spec == SOLVER_SEAICE_LIN || spec == SOLVER_SEAICE_LEAN_LIN; }
 
 using FastConsts = LoopParams;  // name kept for the launcher signatures
 
@@ -616,7 +624,8 @@ struct IceParams {  // kernarg
     double hk_min;      // consolidation thickness / conductivity
     double inv_k;       // 1 / conductivity
     double dT_max, T_melt, T_fw, liquidus_slope, eps_sigma, emissivity, albedo, T_offset;
-    double semi_implicit;  // 1: upwelling longwave linearised about the previous skin temperature (CF_SKIN_SEMI_IMPLICIT)
+    double skin_scheme;    // CF_SKIN_EXPLICIT (0), CF_SKIN_SEMI_IMPLICIT (1: upwelling longwave linearised about the previous
+                           // skin temperature), CF_SKIN_LINEARISED (2: one Newton step on the whole balance per iteration)
     double orbit_shortcut; // 1 (default): an exact period-2 orbit ends the iteration early (CF_OPT_ICE_ORBIT_SHORTCUT)
     double ice_free_zero;  // 1: cells with ℵ = 0 and hᵢ = 0 get zero_interface_state instead of an iteration (CF_OPT_ICE_FREE_CELLS)
 };
@@ -634,7 +643,7 @@ __device__ __forceinline__ double svp_ice_fast(const DevParams& P, const double*
     return svp_ice_from(P, svp_arg(P, logt, T, inv_T));
 }
 
-template <bool COARE>
+template <bool COARE, bool LIN>  // LIN: CF_SKIN_LINEARISED (I.skin_scheme = 2); otherwise I.skin_scheme picks explicit / semi-implicit
 __device__ __forceinline__ Scales ice_iterate(const DevParams& P, const LoopParams& L, const IceParams& I,
                                               const IceConsts& c, const double* tab, bool active, double& Ts) {
     const double* logt = tab + LOG_OFFSET;
@@ -646,6 +655,10 @@ __device__ __forceinline__ Scales ice_iterate(const DevParams& P, const LoopPara
     // median k = 20 on the synthetic polar surface, 90 % of the cells that never converge).  From there on the
     // remaining iterations up to maxiter are known: the stopped iterate is state(k) or state(k−1) by parity.
     double us_2 = -1.0, ts_2 = 0.0, qq_2 = 0.0, Ts_2 = 0.0;
+    // LIN: the turbulent part of ∂Q/∂Tₛ at the current iterate, ρ u★ (c_p χ_θ + ℒ_s χ_q dq_s/dT), with u★ and the profile
+    // factors χ = κ/D of the last similarity step (0 before the first one).  It is part of the iteration's state (0 otherwise).
+    double gturb = 0.0, gturb_2 = 0.0;
+    const double a1_ice = (P.cp_v - P.cp_i) * P.inv_R_v - 1.0, b_ice = (P.LH_s0 - (P.cp_v - P.cp_i) * P.T_0) * P.inv_R_v;
     int work = 0;
     for (;;) {
         bool go;
@@ -655,12 +668,17 @@ __device__ __forceinline__ Scales ice_iterate(const DevParams& P, const LoopPara
             go = active && ((it == 0) || !(drift < L.tol || it >= L.maxiter));
         if (__ballot(go) == 0ull) break;
         if (go) {
-            const double us_1 = us, ts_1 = ts, qq_1 = qq, Ts_1 = Ts;  // state(it)
+            const double us_1 = us, ts_1 = ts, qq_1 = qq, Ts_1 = Ts, gturb_1 = gturb;  // state(it)
             // skin temperature from the energy balance with the previous scales
             const double T2 = Ts * Ts;
             const double rho_u = c.rho * us;
             double Tstar;
-            if (I.semi_implicit != 0.0) {
+            if constexpr (LIN) {
+                // k (Ti − T★)/h = Q(Ts) + Q'(Ts)(T★ − Ts), Q' = 4εσTs³ + gturb : one Newton step on the balance
+                const double Qnet = -rho_u * c.Ls * qq + I.eps_sigma * T2 * T2 - rho_u * c.cp * ts + c.Qd;
+                const double dQ = __builtin_fma(4.0 * I.eps_sigma, T2 * Ts, gturb);
+                Tstar = __builtin_fma(-__builtin_fma(-dQ, Ts, Qnet), c.hk, c.Ti) * frcp(__builtin_fma(c.hk, dQ, 1.0));
+            } else if (I.skin_scheme != 0.0) {
                 // k (Ti − T★)/h = Q_v + Q_c + Q_d + εσ Ts³ T★ : implicit in one factor of the upwelling longwave
                 const double Qrest = -rho_u * c.Ls * qq - rho_u * c.cp * ts + c.Qd;
                 Tstar = __builtin_fma(-Qrest, c.hk, c.Ti) * frcp(__builtin_fma(c.hk * I.eps_sigma, T2 * Ts, 1.0));
@@ -719,20 +737,26 @@ __device__ __forceinline__ Scales ice_iterate(const DevParams& P, const LoopPara
             Du = fmax(Du, L.profile_floor);
             Dq = fmax(Dq, L.profile_floor);
             Dt = fmax(Dt, L.profile_floor);
-            const double un = L.kappa * frcp1(Du) * U, tn = L.kappa * frcp1(Dt) * dtheta, qn = L.kappa * frcp1(Dq) * dq;
+            const double chi_t = L.kappa * frcp1(Dt), chi_q = L.kappa * frcp1(Dq);
+            const double un = L.kappa * frcp1(Du) * U, tn = chi_t * dtheta, qn = chi_q * dq;
             drift = fabs(un - us) + fabs(tn - ts) + fabs(qn - qq);
             us = un;
             ts = tn;
             qq = qn;
+            if constexpr (LIN) {  // dq_s/dT = q_s ((a − 1)/Ts + b/Ts²) of the saturation formula above, ρ fixed
+                const double dqs = qs * (inv_Ts * __builtin_fma(b_ice, inv_Ts, a1_ice));
+                gturb = (c.rho * un) * __builtin_fma(c.cp, chi_t, (c.Ls * chi_q) * dqs);
+            }
             ++it;
             work = it;
-            if (I.orbit_shortcut != 0.0 && us == us_2 && ts == ts_2 && qq == qq_2 && Ts == Ts_2 && !(drift < L.tol)) {
+            if (I.orbit_shortcut != 0.0 && us == us_2 && ts == ts_2 && qq == qq_2 && Ts == Ts_2 && gturb == gturb_2 && !(drift < L.tol)) {
                 // exact period 2: jump to the last iteration (an odd number of steps left lands on the other state of the orbit)
                 if ((L.maxiter - it) & 1) {
                     us = us_1;
                     ts = ts_1;
                     qq = qq_1;
                     Ts = Ts_1;
+                    gturb = gturb_1;
                 }
                 it = L.maxiter;
             }
@@ -740,6 +764,7 @@ __device__ __forceinline__ Scales ice_iterate(const DevParams& P, const LoopPara
             ts_2 = ts_1;
             qq_2 = qq_1;
             Ts_2 = Ts_1;
+            gturb_2 = gturb_1;
         }
     }
     return Scales{us, ts, qq, it, work};

@@ -384,7 +384,7 @@ struct LeanIceConsts {
     double rho, cp, qav, Ls, Ti, hk, Qd, theta_a, pa, inv_pa, inv_rho_Rv, dU2;
 };
 
-template <bool COARE>
+template <bool COARE, bool LIN>  // LIN: CF_SKIN_LINEARISED (see ice_iterate)
 __device__ __forceinline__ Scales ice_iterate_lean(const DevParams& P, const LoopParams& L, const IceParams& I, const LeanIceConsts& c,
                                                    const double* tab, bool active, double& Ts) {
     const double* logt = tab + LOG_OFFSET;
@@ -393,6 +393,8 @@ __device__ __forceinline__ Scales ice_iterate_lean(const DevParams& P, const Loo
     // the state two iterations ago: an exact period-2 orbit ends the iteration early (see ice_iterate)
     // (1/u★ is part of the state here: the orbit is exact only if it repeats too)
     double us_2 = -1.0, ius_2 = 0.0, ts_2 = 0.0, qq_2 = 0.0, Ts_2 = 0.0;
+    // LIN: ρ u★ (c_p χ_θ + ℒ_s χ_q dq_s/dT) of the last similarity step, part of the state (see ice_iterate; 0 otherwise)
+    double gturb = 0.0, gturb_2 = 0.0;
     // iteration-invariant: log(h/ℓ) of the three constant roughness lengths, the lengths themselves
     const double lgu = L.log_h - L.log_const_m, lgq = L.log_h - L.log_const_q, lgt = L.log_h - L.log_const_t;
     const double lu = L.const_m, lq = fexp(L.log_const_q), lt = fexp(L.log_const_t);
@@ -403,12 +405,16 @@ __device__ __forceinline__ Scales ice_iterate_lean(const DevParams& P, const Loo
         const bool go = active && it < L.maxiter && !(drift < L.tol);
         if (__ballot(go) == 0ull) break;
         if (go) {
-            const double us_1 = us, ius_1 = ius, ts_1 = ts, qq_1 = qq, Ts_1 = Ts;  // state(it)
+            const double us_1 = us, ius_1 = ius, ts_1 = ts, qq_1 = qq, Ts_1 = Ts, gturb_1 = gturb;  // state(it)
             // skin temperature from the energy balance with the previous scales
             const double T2 = Ts * Ts;
             const double rho_u = c.rho * us;
             double Tstar;
-            if (I.semi_implicit != 0.0) {
+            if constexpr (LIN) {  // one Newton step on the balance (see ice_iterate)
+                const double Qnet = -rho_u * c.Ls * qq + I.eps_sigma * T2 * T2 - rho_u * c.cp * ts + c.Qd;
+                const double dQ = __builtin_fma(4.0 * I.eps_sigma, T2 * Ts, gturb);
+                Tstar = __builtin_fma(-__builtin_fma(-dQ, Ts, Qnet), c.hk, c.Ti) * frcp1(__builtin_fma(c.hk, dQ, 1.0));
+            } else if (I.skin_scheme != 0.0) {
                 const double Qrest = -rho_u * c.Ls * qq - rho_u * c.cp * ts + c.Qd;
                 Tstar = __builtin_fma(-Qrest, c.hk, c.Ti) * frcp1(__builtin_fma(c.hk * I.eps_sigma, T2 * Ts, 1.0));
             } else {
@@ -484,15 +490,21 @@ __device__ __forceinline__ Scales ice_iterate_lean(const DevParams& P, const Loo
                 iDq = r * (Du * Dt);
                 iDt = r * (Du * Dq);
             }
-            const double un = (L.kappa * U) * iDu, tn = (L.kappa * iDt) * dtheta, qn = (L.kappa * iDq) * dq;
+            const double chi_t = L.kappa * iDt, chi_q = L.kappa * iDq;
+            const double un = (L.kappa * U) * iDu, tn = chi_t * dtheta, qn = chi_q * dq;
             ius = (Du * rU) * L.two_inv_kappa;
             drift = fabs(un - us) + fabs(tn - ts) + fabs(qn - qq);
             us = un;
             ts = tn;
             qq = qn;
+            if constexpr (LIN) {  // dq_s/dT = q_s ((a − 1)/Ts + b/Ts²), ρ fixed
+                const double dqs = qs * (inv_Ts * __builtin_fma(b_ice, inv_Ts, a_ice - 1.0));
+                gturb = (c.rho * un) * __builtin_fma(c.cp, chi_t, (c.Ls * chi_q) * dqs);
+            }
             ++it;
             work = it;
-            if (I.orbit_shortcut != 0.0 && us == us_2 && ius == ius_2 && ts == ts_2 && qq == qq_2 && Ts == Ts_2 && !(drift < L.tol)) {
+            if (I.orbit_shortcut != 0.0 && us == us_2 && ius == ius_2 && ts == ts_2 && qq == qq_2 && Ts == Ts_2 && gturb == gturb_2 &&
+                !(drift < L.tol)) {
                 // exact period 2: jump to the last iteration (an odd number of steps left lands on the other state of the orbit)
                 if ((L.maxiter - it) & 1) {
                     us = us_1;
@@ -500,6 +512,7 @@ __device__ __forceinline__ Scales ice_iterate_lean(const DevParams& P, const Loo
                     ts = ts_1;
                     qq = qq_1;
                     Ts = Ts_1;
+                    gturb = gturb_1;
                 }
                 it = L.maxiter;
             }
@@ -508,6 +521,7 @@ __device__ __forceinline__ Scales ice_iterate_lean(const DevParams& P, const Loo
             ts_2 = ts_1;
             qq_2 = qq_1;
             Ts_2 = Ts_1;
+            gturb_2 = gturb_1;
         }
     }
     return Scales{us, ts, qq, it, work};

@@ -562,7 +562,7 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
                 const FluxOut F = kread(&Kz->F);
                 const NetOut N = kread(&Kz->N);
                 zero_cell<FUSE_NET>(L, T_offset, G, F, N, k, i, j);
-                        if constexpr (SPEC == SOLVER_SEAICE || SPEC == SOLVER_SEAICE_LEAN) ice_zero_net(opaque(K), G, k, i, j);
+                        if constexpr (seaice_spec(SPEC)) ice_zero_net(opaque(K), G, k, i, j);
             }
         }
         for (int d = 32; d; d >>= 1) {
@@ -612,7 +612,7 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
                         const int jj = row_of(idx, wx, wx_rcp);
                         const int i = idx - jj * wx - G.ring, j = jj - G.ring;
                         zero_cell<FUSE_NET>(L, T_offset, G, F, N, cell_index(G, i, j), i, j);
-                        if constexpr (SPEC == SOLVER_SEAICE || SPEC == SOLVER_SEAICE_LEAN) ice_zero_net(opaque(K), G, cell_index(G, i, j), i, j);
+                        if constexpr (seaice_spec(SPEC)) ice_zero_net(opaque(K), G, cell_index(G, i, j), i, j);
                     }
             }
         } else {  // stale list: redo the range the slow way
@@ -643,7 +643,7 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
                         const FluxOut F = kread(&Kz->F);
                         const NetOut N = kread(&Kz->N);
                         zero_cell<FUSE_NET>(L, T_offset, G, F, N, k, i, j);
-                        if constexpr (SPEC == SOLVER_SEAICE || SPEC == SOLVER_SEAICE_LEAN) ice_zero_net(opaque(K), G, k, i, j);
+                        if constexpr (seaice_spec(SPEC)) ice_zero_net(opaque(K), G, k, i, j);
                     }
                 }
                 const unsigned long long m = __ballot(wet);
@@ -675,7 +675,7 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
             const int q = start + lane;
             const bool in_range = q < nwet;
             const int qc = in_range ? q : nwet - 1;
-            if constexpr (SPEC == SOLVER_SEAICE || SPEC == SOLVER_SEAICE_LEAN) {
+            if constexpr (seaice_spec(SPEC)) {
                 // ---- atmosphere–sea-ice interface: same list, same batches, the skin temperature inside the loop ----
                 const IceParams Ice = kread(&K->Ice);
                 IceConsts c;
@@ -723,11 +723,11 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
                 Scales s{0.0, 0.0, 0.0, 0, 0};
                 const bool solve = in_range && !ice_free;
                 if (__ballot(solve) != 0ull) {  // (a batch of open water — most of the surface — skips the solve altogether)
-                    if constexpr (SPEC == SOLVER_SEAICE_LEAN) {
+                    if constexpr (seaice_lean_spec(SPEC)) {
                         const LeanIceConsts lc{c.rho, c.cp, c.qav, c.Ls, c.Ti, c.hk, c.Qd, c.theta_a, c.pa, frcp1(c.pa), frcp1(c.rho * P.R_v), c.dU2};
-                        s = ice_iterate_lean<COARE>(P, L, Ice, lc, tab, solve, Ts);
+                        s = ice_iterate_lean<COARE, seaice_lin_spec(SPEC)>(P, L, Ice, lc, tab, solve, Ts);
                     } else {
-                        s = ice_iterate<COARE>(P, L, Ice, c, tab, solve, Ts);
+                        s = ice_iterate<COARE, seaice_lin_spec(SPEC)>(P, L, Ice, c, tab, solve, Ts);
                     }
                 }
                 if (ice_free) s = Scales{0.0, 0.0, 0.0, 0, 0};  // zero_interface_state: no fluxes; the skin temperature stays the input
@@ -844,7 +844,7 @@ struct IceOceanArgs {
     // dispatch order: up to eight segments of (kind, first, count); kind 0 = interface chunks, 1 = ocean chunks, 2 = interpolation
     int nseg, seg_kind[8], seg_first[8], seg_count[8];
 };
-template <bool COARE_ICE, bool COARE_OCEAN>
+template <bool COARE_ICE, bool COARE_OCEAN, int ICE_SPEC>  // ICE_SPEC: SOLVER_SEAICE_LEAN or SOLVER_SEAICE_LEAN_LIN
 __global__ __launch_bounds__(AO_BLOCK, 3) void ice_ocean_kernel(IceOceanArgs unused_by_name) {
     typedef const IceOceanArgs __attribute__((address_space(4)))* ArgsPtr;
     ArgsPtr K = (ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -871,7 +871,7 @@ __global__ __launch_bounds__(AO_BLOCK, 3) void ice_ocean_kernel(IceOceanArgs unu
         return;
     }
     block = kind == 2 ? nch + idx : idx;  // the interpolation's workgroups: numbered as in ao_flux_fast_kernel's tail
-    ao_flux_fast_body<COARE_ICE, SOLVER_SEAICE_LEAN, false, AO_BLOCK, true>((SolverArgsPtr)&K->A, block);
+    ao_flux_fast_body<COARE_ICE, ICE_SPEC, false, AO_BLOCK, true>((SolverArgsPtr)&K->A, block);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1019,6 +1019,7 @@ hipError_t launch_ai_fluxes(hipStream_t st, const LaunchCfg& L, const DevParams&
     const bool coare = P.similarity_form == CF_SIMILARITY_COARE_LOGARITHMIC;
     // constant roughness lengths and a gustiness floor (both production presets): the lean iteration body
     const bool lean = C.specialization == SOLVER_ICE && L.solver == CF_SOLVER_TABLES;
+    const bool lin = Ice.skin_scheme == CF_SKIN_LINEARISED;   // (its own kernels: ice_iterate's LIN)
     if (net_ice) A.NI = *net_ice;
     if (tail) {
         // tail workgroups behind the interface solve's (lean iteration, narrow geometry): the next step's interpolation and / or
@@ -1096,24 +1097,38 @@ hipError_t launch_ai_fluxes(hipStream_t st, const LaunchCfg& L, const DevParams&
             const dim3 mgrid((unsigned)(L.n_chunks + tail->ocean->n_chunks + A.tail_blocks));
             constexpr size_t lds = (size_t)(Geom<AO_BLOCK>::LDS_BYTES > LeanGeom<AO_BLOCK>::LDS_BYTES ? Geom<AO_BLOCK>::LDS_BYTES : LeanGeom<AO_BLOCK>::LDS_BYTES);
             static_assert(lds <= 53760, "three workgroups per CU");
-            if (coare) {
-                if (tail->ocean->coare) hipLaunchKernelGGL((ice_ocean_kernel<true, true>), mgrid, dim3(AO_BLOCK), lds, st, M);
-                else hipLaunchKernelGGL((ice_ocean_kernel<true, false>), mgrid, dim3(AO_BLOCK), lds, st, M);
-            } else {
-                if (tail->ocean->coare) hipLaunchKernelGGL((ice_ocean_kernel<false, true>), mgrid, dim3(AO_BLOCK), lds, st, M);
-                else hipLaunchKernelGGL((ice_ocean_kernel<false, false>), mgrid, dim3(AO_BLOCK), lds, st, M);
-            }
+#define CF_IO_LAUNCH(SPEC_)                                                                                                   \
+    do {                                                                                                                      \
+        if (coare) {                                                                                                          \
+            if (tail->ocean->coare) hipLaunchKernelGGL((ice_ocean_kernel<true, true, SPEC_>), mgrid, dim3(AO_BLOCK), lds, st, M); \
+            else hipLaunchKernelGGL((ice_ocean_kernel<true, false, SPEC_>), mgrid, dim3(AO_BLOCK), lds, st, M);              \
+        } else {                                                                                                              \
+            if (tail->ocean->coare) hipLaunchKernelGGL((ice_ocean_kernel<false, true, SPEC_>), mgrid, dim3(AO_BLOCK), lds, st, M); \
+            else hipLaunchKernelGGL((ice_ocean_kernel<false, false, SPEC_>), mgrid, dim3(AO_BLOCK), lds, st, M);             \
+        }                                                                                                                     \
+    } while (0)
+            if (lin) CF_IO_LAUNCH(SOLVER_SEAICE_LEAN_LIN);
+            else CF_IO_LAUNCH(SOLVER_SEAICE_LEAN);
+#undef CF_IO_LAUNCH
             return hipGetLastError();
         }
         const dim3 tgrid((unsigned)(L.n_chunks + A.tail_blocks + A.stress_blocks));
-        if (coare) hipLaunchKernelGGL((ao_flux_fast_kernel<true, SOLVER_SEAICE_LEAN, false, AO_BLOCK, true>), tgrid, dim3(AO_BLOCK), Geom<AO_BLOCK>::LDS_BYTES, st, A);
-        else hipLaunchKernelGGL((ao_flux_fast_kernel<false, SOLVER_SEAICE_LEAN, false, AO_BLOCK, true>), tgrid, dim3(AO_BLOCK), Geom<AO_BLOCK>::LDS_BYTES, st, A);
+#define CF_AI_TAIL_LAUNCH(COARE_, SPEC_) \
+    hipLaunchKernelGGL((ao_flux_fast_kernel<COARE_, SPEC_, false, AO_BLOCK, true>), tgrid, dim3(AO_BLOCK), Geom<AO_BLOCK>::LDS_BYTES, st, A)
+        if (lin) { if (coare) CF_AI_TAIL_LAUNCH(true, SOLVER_SEAICE_LEAN_LIN); else CF_AI_TAIL_LAUNCH(false, SOLVER_SEAICE_LEAN_LIN); }
+        else { if (coare) CF_AI_TAIL_LAUNCH(true, SOLVER_SEAICE_LEAN); else CF_AI_TAIL_LAUNCH(false, SOLVER_SEAICE_LEAN); }
+#undef CF_AI_TAIL_LAUNCH
         return hipGetLastError();
     }
 #define CF_AI_LAUNCH(COARE_, SPEC_, BLOCK_) \
     hipLaunchKernelGGL((ao_flux_fast_kernel<COARE_, SPEC_, false, BLOCK_>), grid, dim3(BLOCK_), Geom<BLOCK_>::LDS_BYTES, st, A)
-    if (lean) { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LEAN, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LEAN, AO_BLOCK); }
-    else { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE, AO_BLOCK); }
+    if (lin) {
+        if (lean) { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LEAN_LIN, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LEAN_LIN, AO_BLOCK); }
+        else { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LIN, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LIN, AO_BLOCK); }
+    } else {
+        if (lean) { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LEAN, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LEAN, AO_BLOCK); }
+        else { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE, AO_BLOCK); }
+    }
 #undef CF_AI_LAUNCH
     return hipGetLastError();
 }

@@ -187,9 +187,12 @@ normalize_salinity_flux!(b::CoFluxBackend, flux::Ptr{Float64}, additional, area,
                        b.ctx, flux, additional, area, mask, mean_out))
 
 # ---- atmosphere–sea-ice interface: compute_atmosphere_sea_ice_fluxes!(coupled_model) ---------------
+const CF_SKIN_EXPLICIT = Int32(0)
+const CF_SKIN_SEMI_IMPLICIT = Int32(1)
+const CF_SKIN_LINEARISED = Int32(2)      # one Newton step on the surface energy balance per iteration (include/coflux.h)
 # SkinTemperature(ConductiveFlux) + SurfaceRadiationProperties(sea_ice_albedo, 1.0) (atmosphere.jl:34-44)
 mutable struct CfSeaIceParams
-    struct_size::Int32; skin_temperature_scheme::Int32       # CF_SKIN_EXPLICIT = 0 / CF_SKIN_SEMI_IMPLICIT = 1
+    struct_size::Int32; skin_temperature_scheme::Int32       # CF_SKIN_EXPLICIT = 0 / CF_SKIN_SEMI_IMPLICIT = 1 / CF_SKIN_LINEARISED = 2
     conductivity::Float64; consolidation_thickness::Float64; maximum_temperature_change::Float64
     ice_salinity::Float64; liquidus_slope::Float64; freshwater_melting_temperature::Float64
     albedo::Float64; emissivity::Float64; temperature_offset::Float64

@@ -36,10 +36,11 @@
 extern "C" {
 #endif
 
-#define CF_ABI_VERSION 4 /* 2: cf_flux_params.shear_gustiness_coefficient; 3: CF_OPT_MAX_BLOCKS, CF_OPT_PROFILE_STRIDE, CF_OPT_FUSED_INTERP,
+#define CF_ABI_VERSION 5 /* 2: cf_flux_params.shear_gustiness_coefficient; 3: CF_OPT_MAX_BLOCKS, CF_OPT_PROFILE_STRIDE, CF_OPT_FUSED_INTERP,
                           * CF_SOLVER_TABLES_R2(_OUTER) and the 768-thread geometry (CF_OPT_AO_CHUNK = 3072) retired; CF_OPT_AO_CHUNK and
                           * CF_OPT_INTERP_TILE_CAP are experiment options (COFLUX_EXPERIMENTS=1); 4: time averages accumulated on the
-                          * device (cf_average_*, cf_attach_average; cf_run_schedule unchanged) */
+                          * device (cf_average_*, cf_attach_average; cf_run_schedule unchanged); 5: CF_SKIN_LINEARISED, a third
+                          * value of cf_sea_ice_params.skin_temperature_scheme that older libraries reject */
 
 /* status codes */
 #define CF_OK 0
@@ -578,9 +579,21 @@ int cf_window_source(cf_window* w, int64_t n1, int64_t n2, double time_fraction,
  *                  (h/k)·∂Q/∂T exceeds 1 for ice thicker than ≈ 0.1–0.2 m in wind, where it orbits under the ±ΔT_max
  *                  limiter until maxiter;
  *   SEMI_IMPLICIT  the upwelling longwave linearised about the previous skin temperature,
- *                  T★ = (Tᵢ − (h/k)(Q_v + Q_c + Q_d)) / (1 + (h/k) εσ Tₛ³)  — the damped form.                    */
+ *                  T★ = (Tᵢ − (h/k)(Q_v + Q_c + Q_d)) / (1 + (h/k) εσ Tₛ³)  — the damped form;
+ *   LINEARISED     one Newton step on the whole balance per iteration: all four terms linearised about the previous Tₛ,
+ *                  with the previous iterate's u★ and transfer coefficients held fixed,
+ *                    Q(Tₛ)  = −ρ u★ (ℒ_s q★ + c_p θ★) + Q_d + εσTₛ⁴                       (what EXPLICIT computes)
+ *                    Q'(Tₛ) = 4εσTₛ³ + ρ c_p u★ χ_θ + ρ ℒ_s u★ χ_q · dq_s/dT(Tₛ)
+ *                    χ_θ = κ/D_θ, χ_q = κ/D_q   (profile factors of the previous similarity step; 0 before the first)
+ *                    dq_s/dT = q_s(Tₛ) ((a_i − 1)/Tₛ + b_i/Tₛ²), a_i = (c_pv − c_pi)/R_v, b_i = (ℒ_s0 − (c_pv − c_pi) T_0)/R_v
+ *                    T★ = (Tᵢ − (h/k)(Q(Tₛ) − Q'(Tₛ) Tₛ)) / (1 + (h/k) Q'(Tₛ)),   h = h_eff;
+ *                  it contracts where EXPLICIT orbits (the turbulent feedback (h/k) ρ c_p C_h U ≈ 10 on metre-thick ice in
+ *                  wind).  A fixed point of it is a fixed point of EXPLICIT.
+ * Every scheme then applies the NaN guard, the ±ΔT_max limiter and the cap at the melting point before the similarity step;
+ * the stop rule, the initial scales and maxiter are the same.                                                             */
 #define CF_SKIN_EXPLICIT 0
 #define CF_SKIN_SEMI_IMPLICIT 1
+#define CF_SKIN_LINEARISED 2
 typedef struct cf_sea_ice_params {
     int32_t struct_size;                   /* sizeof(cf_sea_ice_params) */
     int32_t skin_temperature_scheme;       /* CF_SKIN_* */
