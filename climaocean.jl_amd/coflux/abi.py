@@ -30,6 +30,8 @@ OPT_SOLVER_PATH, OPT_CERTIFIED_BUDGET, OPT_ICE_FREE_CELLS, OPT_LATENCY_LAYOUT, O
 ICE_FREE_ITERATE, ICE_FREE_ZERO = 0, 1
 PIPELINE_WITHIN_CALL, PIPELINE_CONTINUING = 1, 2   # cf_run_schedule.pipeline
 AVERAGE_MAX_FIELDS = 16                            # fields of one time averager (cf_average_create)
+INTEGRALS_MAX_ENTRIES, INTEGRALS_MAX_FIELDS = 32, 32   # entries / distinct arrays of one surface integrator (cf_integrals_create)
+INTEGRAND_ONE, INTEGRAND_FIELD, INTEGRAND_PRODUCT, INTEGRAND_ABOVE = 0, 1, 2, 3
 SOLVER_PATH_EXACT, SOLVER_PATH_CERTIFIED = 0, 1      # how the Monin–Obukhov fixed point is reached (include/coflux.h)
 CERTIFIED_EXACT_FLAG = 0x100                         # `iterations` of a cell the certified path solved on the exact path
 SOLVER_TABLES, SOLVER_LIBM = 0, 1
@@ -191,6 +193,18 @@ class InterpWeights(C.Structure):
                 ("cos_rot", C.c_void_p), ("sin_rot", C.c_void_p), ("latitude", C.c_void_p)]
 
 
+class IntegralEntry(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("region_bit", C.c_int32), ("a", C.c_void_p), ("b", C.c_void_p),
+                ("threshold", C.c_double)]
+
+
+class IntegralsDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_entries", C.c_int32),
+                ("area", C.c_void_p), ("mask", C.c_void_p), ("region", C.c_void_p),
+                ("max_workgroups", C.c_int32), ("reserved", C.c_int32),
+                ("entries", IntegralEntry * INTEGRALS_MAX_ENTRIES)]
+
+
 # Every symbol include/coflux.h declares (tests check they are all exported).
 EXPORTED_SYMBOLS = (
     "cf_version", "cf_default_flux_params", "cf_create", "cf_destroy", "cf_last_error",
@@ -211,6 +225,8 @@ EXPORTED_SYMBOLS = (
     "cf_window_upload", "cf_window_find", "cf_window_source",
     "cf_ensure_chunk_table", "cf_solver_path", "cf_solver_iteration_path", "cf_solver_latency_layout", "cf_comm_count", "cf_build_stamp", "cf_discard_prefetched_atmosphere_state",
     "cf_average_create", "cf_average_destroy", "cf_average_reset", "cf_average_collect", "cf_average_weight", "cf_attach_average",
+    "cf_integrals_create", "cf_integrals_destroy", "cf_integrals_collect", "cf_integrals_count", "cf_integrals_read",
+    "cf_integrals_reset", "cf_attach_integrals",
 )
 
 PACKAGE_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -350,6 +366,13 @@ def load_library(path=None):
     lib.cf_average_collect.argtypes = [vp, C.c_double]
     lib.cf_average_weight.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.cf_attach_average.argtypes = [vp, vp, C.c_int32, C.c_double]
+    lib.cf_integrals_create.argtypes = [vp, C.POINTER(IntegralsDesc), C.c_int32, C.POINTER(vp)]
+    lib.cf_integrals_destroy.argtypes = [vp]
+    lib.cf_integrals_collect.argtypes = [vp, C.c_double]
+    lib.cf_integrals_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.cf_integrals_read.argtypes = [vp, C.c_int64, C.c_int64, c_double_p, c_double_p]
+    lib.cf_integrals_reset.argtypes = [vp]
+    lib.cf_attach_integrals.argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("cf_last_error", "cf_device_alloc", "cf_window_host_buffer", "cf_build_stamp"):

@@ -31,6 +31,7 @@ from . import interface_computations as ic
 from .runtime import EXCHANGE_NAMES, FLUX_NAMES, FLUX_OPTIONAL, NET_NAMES, FluxContext
 
 minutes, hours, days = 60.0, 3600.0, 86400.0
+EARTH_RADIUS = 6.371e6   # m (Oceananigans' R_Earth)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -69,6 +70,20 @@ class LatitudeLongitudeGrid:
         fi, fj, phi = self.fractional_indices(nsx, nsy)
         return dict(separable=True, fi=to_device(fi), fj=to_device(fj), latitude=to_device(phi))
 
+    def cell_latitudes(self):
+        """φ [deg] of the cell centres in the halo layout (ny + 2hy, nx + 2hx)."""
+        (nx, ny, _), (hx, hy, _) = self.size, self.halo
+        phi = self.latitude[0] + (np.arange(-hy, ny + hy) + 0.5) * (self.latitude[1] - self.latitude[0]) / ny
+        return np.ascontiguousarray(np.broadcast_to(phi[:, None], self.surface_shape))
+
+    def cell_areas(self):
+        """Az = R² Δλ (sin φ_f[j+1] − sin φ_f[j]) [m²] in the halo layout (the formula runs on through the halo rows)."""
+        (nx, ny, _), (hx, hy, _) = self.size, self.halo
+        dlam = np.deg2rad((self.longitude[1] - self.longitude[0]) / nx)
+        faces = np.deg2rad(self.latitude[0] + np.arange(-hy, ny + hy + 1) * (self.latitude[1] - self.latitude[0]) / ny)
+        rows = EARTH_RADIUS ** 2 * dlam * np.diff(np.sin(faces))
+        return np.ascontiguousarray(np.broadcast_to(rows[:, None], self.surface_shape))
+
 
 @dataclass
 class TripolarGrid:
@@ -90,8 +105,26 @@ class TripolarGrid:
     latitude: Optional[np.ndarray] = None      # (ny, nx) cell-centre φ [deg]
     cos_rotation: Optional[np.ndarray] = None
     sin_rotation: Optional[np.ndarray] = None
+    area: Optional[np.ndarray] = None          # (ny, nx) cell areas Az [m²] of a real grid (nothing is guessed without them)
 
     fold_north = True
+
+    def _halo_layout(self, a, fill):
+        (nx, ny, _), (hx, hy, _) = self.size, self.halo
+        g = np.full(self.surface_shape, fill, dtype=np.asarray(a).dtype)
+        g[hy:hy + ny, hx:hx + nx] = a
+        return g
+
+    def cell_latitudes(self):
+        """φ [deg] of the cell centres in the halo layout; the halos hold NaN (no cell there belongs to a hemisphere)."""
+        return self._halo_layout(np.asarray(self.mesh()[1], dtype=np.float64), np.nan)
+
+    def cell_areas(self):
+        """The `area` array of the real grid in the halo layout (halos 0)."""
+        if self.area is None:
+            raise ValueError("TripolarGrid: cell areas are not derived from the synthetic mesh; pass TripolarGrid(area=Az) "
+                             "(ny × nx, m²) or hand an area array to the integrals")
+        return self._halo_layout(np.asarray(self.area, dtype=np.float64), 0.0)
 
     @property
     def surface_shape(self):
@@ -753,6 +786,129 @@ class SurfaceFluxAverages:
             self.windows.append((t_k, arrays))
             if self.on_window is not None:
                 self.on_window(t_k, arrays)
+
+
+# ---------------------------------------------------------------------------------------------
+# scalar time series: area-weighted surface integrals on the device (cf_integrals_*)
+# ---------------------------------------------------------------------------------------------
+REGION_GLOBAL, REGION_NORTH, REGION_SOUTH = 0, 1, 2   # bits of hemisphere_regions
+
+
+def hemisphere_regions(grid):
+    """The uint8 region array of the sea-ice diagnostics in the halo layout: bit 0 everywhere, bit 1 where φ > 0, bit 2 where
+    φ < 0 — both strict, like arctic_condition / antarctic_condition (visualize/common.jl:715-787): a cell at exactly
+    φ = 0 is in neither hemisphere."""
+    phi = grid.cell_latitudes()
+    return (1 + 2 * (phi > 0) + 4 * (phi < 0)).astype(np.uint8)
+
+
+class IterationInterval:
+    """IterationInterval(n): every n-th iteration."""
+
+    def __init__(self, interval):
+        if int(interval) != interval or interval < 1:
+            raise ValueError(f"IterationInterval: interval = {interval} (an integer ≥ 1)")
+        self.interval = int(interval)
+
+    def actuate(self, iteration):
+        return iteration % self.interval == 0
+
+
+class SurfaceIntegrals:
+    """An output writer of scalar time series: SurfaceIntegrals(model, outputs; schedule = IterationInterval(1), regions, area).
+    `outputs`: name → (kind, a[, b[, threshold[, region bit]]]) with kind "one" | "field" | "product" | "above" as in
+    FluxContext.integrals, or "mean": ∫ a dA / ∫ dA over the same region, formed on the host from a "field" entry and the
+    "one" entry of that region (added once per region).  Every collection is one record on the device
+    (cf_integrals_collect: no host synchronisation); series() reads them.  A full device series is moved to the host and
+    started again, so `capacity` bounds memory, not the length of a run.  `regions`: uint8 region bits (default: every cell in
+    bit 0), `area`: cell areas (default: grid.cell_areas()), both host or device arrays in the halo layout."""
+
+    def __init__(self, model, outputs, schedule=None, regions=None, area=None, capacity=4096):
+        itf = model.interfaces
+        ctx = self.ctx = itf.context
+        self.model = model
+        self.schedule = IterationInterval(schedule) if isinstance(schedule, int) else (schedule or IterationInterval(1))
+        on_device = lambda a: a if isinstance(a, torch.Tensor) else ctx.to_device(a)  # noqa: E731
+        self.area = on_device(model.ocean.grid.cell_areas() if area is None else area)
+        self.regions = None if regions is None else on_device(regions)
+        mask = model.ocean.model.wet_mask if ctx.params.mask_kind == abi.MASK_U8 else None
+        entries, self._columns, ones = [], {}, {}
+        pad = lambda spec: tuple(spec) + ("one", None, None, 0.0, 0)[len(spec):]  # noqa: E731
+        for name, spec in outputs.items():
+            kind, a, b, threshold, bit = pad(spec)
+            if kind == "mean":
+                if bit not in ones:
+                    ones[bit] = len(entries)
+                    entries.append(("one", None, None, 0.0, bit))
+                self._columns[name] = (len(entries), ones[bit])
+                entries.append(("field", a, None, 0.0, bit))
+            else:
+                self._columns[name] = (len(entries), None)
+                entries.append((kind, a, b, threshold, bit))
+        self.entries = entries
+        self.integrator = ctx.integrals(entries, area=self.area, mask=mask, region=self.regions, capacity=capacity)
+        self._values, self._times = [], []
+
+    def initialize(self, simulation):
+        pass
+
+    def _drain(self):
+        values, times = self.integrator.read()
+        if len(times):
+            self._values.append(values)
+            self._times.append(times)
+            self.integrator.reset()
+
+    def write(self, clock):
+        if not self.schedule.actuate(clock.iteration):
+            return
+        if self.integrator.count() == self.integrator.capacity:
+            self._drain()
+        self.integrator.collect(clock.time)
+
+    def records(self):
+        """(values[n, n_entries], times[n]): every record so far, raw entries in the order of `entries`."""
+        self._drain()
+        if not self._times:
+            return np.zeros((0, len(self.entries))), np.zeros(0)
+        self._values, self._times = [np.concatenate(self._values)], [np.concatenate(self._times)]
+        return self._values[0], self._times[0]
+
+    @property
+    def times(self):
+        return self.records()[1]
+
+    def series(self):
+        """{name: np.ndarray[n]}: the integrals, and for "mean" outputs integral / integral of 1 over the same region."""
+        values, _ = self.records()
+        return {name: values[:, c] if one is None else values[:, c] / values[:, one] for name, (c, one) in self._columns.items()}
+
+    def close(self):
+        self.integrator.close()
+
+
+def sea_ice_integrals(model, threshold=0.15, **kw):
+    """compute_ice_diagnostics (visualize/common.jl:715-787) as a writer: arctic_ / antarctic_ × volume ∫ hᵢ ℵ dA, area ∫ ℵ dA
+    and extent ∫ [ℵ > 0.15] dA (threshold: common.jl:721), per step instead of from the 5-day means."""
+    si = model.sea_ice
+    if si is None or si.thickness is None:
+        raise ValueError("sea_ice_integrals: the model has no sea ice with a thickness")
+    outputs = {}
+    for prefix, bit in (("arctic", REGION_NORTH), ("antarctic", REGION_SOUTH)):
+        outputs[prefix + "_volume"] = ("product", si.thickness, si.concentration, 0.0, bit)
+        outputs[prefix + "_area"] = ("field", si.concentration, None, 0.0, bit)
+        outputs[prefix + "_extent"] = ("above", si.concentration, None, threshold, bit)
+    kw.setdefault("regions", hemisphere_regions(model.ocean.grid))
+    return SurfaceIntegrals(model, outputs, **kw)
+
+
+def surface_global_means(model, **kw):
+    """The global means of the reference's `:averages` writer (omip_diagnostics.jl:194-218) that live on the surface: hfds,
+    wfo (the ocean's net T and S fluxes), hfss, hfls, tos, sos — area-weighted over the wet cells of region 0."""
+    itf, st = model.interfaces, model.ocean.surface_state()
+    net, ao = itf.net_fluxes._ocean_fields, itf.atmosphere_ocean_interface._fields
+    fields = dict(hfds=net["T"], wfo=net["S"], hfss=ao["sensible_heat"], hfls=ao["latent_heat"], tos=st["T"], sos=st["S"])
+    return SurfaceIntegrals(model, {name: ("mean", f, None, 0.0, REGION_GLOBAL) for name, f in fields.items()}, **kw)
 
 
 class JRA55PrescribedLand:

@@ -388,6 +388,22 @@ class FluxContext:
         self._attached_average = averager
         self._check(self.lib.cf_attach_average(self._h, h, int(stride), float(step_weight)), "cf_attach_average")
 
+    # -- surface integrals ------------------------------------------------------------------------
+    def integrals(self, entries, area=None, mask=None, region=None, capacity=1024, max_workgroups=0):
+        """A device-side time series of area-weighted, masked, regional integrals (cf_integrals_create).  `entries`: up to
+        abi.INTEGRALS_MAX_ENTRIES tuples (kind, a, b, threshold, region_bit) — kind "one" | "field" | "product" | "above" or
+        abi.INTEGRAND_*, `a` / `b` ocean-grid float64 fields (None where the kind has none); trailing items may be left out.
+        `area`: float64 cell areas, `mask`: the context's wet mask, `region`: uint8 region bits (all ocean-grid arrays)."""
+        return SurfaceIntegrator(self, entries, area, mask, region, capacity, max_workgroups)
+
+    def attach_integrals(self, integrator, stride=1, time_origin=0.0, step_seconds=1.0):
+        """time_steps() appends a record of `integrator` after every step s with (s + 1) % stride == 0, stamped
+        time_origin + (s + 1) · step_seconds (cf_attach_integrals); None detaches."""
+        h = integrator._h if integrator is not None else None
+        self._attached_integrals = integrator
+        self._check(self.lib.cf_attach_integrals(self._h, h, int(stride), float(time_origin), float(step_seconds)),
+                    "cf_attach_integrals")
+
     # -- peer-direct halo rows / tripolar fold -----------------------------------------------------
     def peer_halo_export(self, max_fields=4, max_rows=2):
         buf = C.create_string_buffer(abi.PEER_HANDLE_BYTES)
@@ -471,6 +487,79 @@ class TimeAverager:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self.lib.cf_average_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+INTEGRAND_KINDS = dict(one=abi.INTEGRAND_ONE, field=abi.INTEGRAND_FIELD, product=abi.INTEGRAND_PRODUCT, above=abi.INTEGRAND_ABOVE)
+
+
+class SurfaceIntegrator:
+    """cf_integrals_*: every collect(time) appends one record — entry e is Σ A·x over the wet interior cells that carry the
+    entry's region bit — to a series kept on the device, in one pass over the interior; read() is the only host
+    synchronisation.  The library borrows the pointers: the tensors are kept alive here."""
+
+    def __init__(self, ctx, entries, area=None, mask=None, region=None, capacity=1024, max_workgroups=0):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.n_entries, self.capacity = len(entries), int(capacity)
+        if self.n_entries > abi.INTEGRALS_MAX_ENTRIES:
+            raise ValueError(f"{self.n_entries} entries (at most {abi.INTEGRALS_MAX_ENTRIES})")
+        desc = abi.IntegralsDesc()
+        desc.struct_size, desc.n_entries, desc.max_workgroups = C.sizeof(abi.IntegralsDesc), self.n_entries, int(max_workgroups)
+        self._keep = [area, mask, region]
+        for name, t, dtype in (("area", area, torch.float64), ("mask", mask, None), ("region", region, torch.uint8)):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.is_contiguous() and tuple(t.shape) == ctx.shape and dtype in (None, t.dtype)):
+                raise ValueError(f"{name} is a contiguous device array of shape {ctx.shape}" + (f" and dtype {dtype}" if dtype else ""))
+            setattr(desc, name, t.data_ptr())
+        for e, entry in enumerate(entries):
+            kind, a, b, threshold, bit = tuple(entry) + ("one", None, None, 0.0, 0)[len(entry):]
+            E = desc.entries[e]
+            E.kind = INTEGRAND_KINDS[kind] if isinstance(kind, str) else int(kind)
+            E.region_bit, E.threshold = int(bit), float(threshold)
+            for key, t in (("a", a), ("b", b)):
+                if t is None:
+                    continue
+                if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == ctx.shape):
+                    raise ValueError(f"entry {e}: {key} is a contiguous float64 device array of shape {ctx.shape}")
+                setattr(E, key, t.data_ptr())
+                self._keep.append(t)
+        h = C.c_void_p()
+        ctx._check(self.lib.cf_integrals_create(ctx._h, C.byref(desc), self.capacity, C.byref(h)), "cf_integrals_create")
+        self._h = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise CofluxError(f"{what} failed ({rc}): {self.lib.cf_last_error(None).decode()}")
+
+    def collect(self, time=0.0):
+        self._check(self.lib.cf_integrals_collect(self._h, float(time)), "cf_integrals_collect")
+
+    def count(self):
+        n = C.c_int64()
+        self._check(self.lib.cf_integrals_count(self._h, C.byref(n)), "cf_integrals_count")
+        return n.value
+
+    def read(self, first=0, n=None):
+        """(values[n, n_entries], times[n]) of records first … first + n − 1 (n = None: to the end of the series)."""
+        n = self.count() - first if n is None else n
+        values, times = np.zeros((max(n, 0), self.n_entries)), np.zeros(max(n, 0))
+        self._check(self.lib.cf_integrals_read(self._h, int(first), int(n), values.ctypes.data_as(abi.c_double_p),
+                                               times.ctypes.data_as(abi.c_double_p)), "cf_integrals_read")
+        return values, times
+
+    def reset(self):
+        self._check(self.lib.cf_integrals_reset(self._h), "cf_integrals_reset")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self.lib.cf_integrals_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -153,6 +153,11 @@ struct cf_ctx {
     cf_average* average = nullptr;
     int32_t average_stride = 1;
     double average_step_weight = 0.0;
+    // surface integrals (coflux_integrals.cpp): the same pair for the integrators (cf_attach_integrals)
+    std::vector<cf_integrals*> integrators;
+    cf_integrals* integrals = nullptr;
+    int32_t integrals_stride = 1;
+    double integrals_time_origin = 0.0, integrals_step_seconds = 0.0;
 };
 
 struct cf_average {
@@ -161,6 +166,16 @@ struct cf_average {
     AverageFields fields{};
     double total = 0.0;      // the window's total weight
     int64_t samples = 0;
+};
+
+struct cf_integrals {
+    cf_ctx* ctx = nullptr;       // NULL once the context is destroyed
+    int device = 0;
+    IntegralArgs args{};
+    int max_blocks = 0;
+    int64_t capacity = 0, count = 0;
+    std::vector<double> times;   // of the records, host side
+    double* d_series = nullptr;  // [capacity][n_entries]; the partial sums and the entries' descriptors lie behind it
 };
 
 // sets the thread-local and the context's last-error text and returns `code`
@@ -186,5 +201,11 @@ extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_
 int average_collect(cf_average* a, double weight);
 // coflux_average.cpp: cf_destroy orphans the context's averagers
 void average_forget_context(cf_ctx* ctx);
+// coflux_integrals.cpp: one collection of `q` (the series must have room: integrals_room)
+int integrals_collect(cf_integrals* q, double time);
+// coflux_integrals.cpp: CF_ERR_INVALID unless the attached integrator's series has room for what cf_time_steps(first_step, nsteps) collects
+int integrals_room(cf_ctx* ctx, int64_t first_step, int nsteps);
+// coflux_integrals.cpp: cf_destroy orphans the context's integrators
+void integrals_forget_context(cf_ctx* ctx);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state)
 extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx);

@@ -156,5 +156,27 @@ struct AverageFields {
 };
 hipError_t launch_average(hipStream_t st, const AverageFields& F, int nfields, const GridDesc& G, bool store, double c_prev,
                           double c_new);
+// cf_integrals_collect (coflux_integrals.hip): one record of area-weighted, masked, regional integrals; the distinct `a` / `b`
+// arrays of the entries are numbered (field slots) by the host
+// interior cells per tile of the summation order (a constant of the record's bits; A/B builds may set it: 512 · 1 / 2 / 4)
+#ifndef COFLUX_INTEGRALS_TILE
+#define COFLUX_INTEGRALS_TILE 1024
+#endif
+constexpr int INTEGRALS_TILE = COFLUX_INTEGRALS_TILE;
+struct IntegralArgs {
+    const double* field[CF_INTEGRALS_MAX_FIELDS];
+    const double* area;
+    const void* mask;
+    const uint8_t* region;
+    double* partial;                  // [tiles][bucket] per-tile sums
+    const uint32_t* entry;            // device, [CF_INTEGRALS_MAX_ENTRIES]: kind | slot of a << 8 | slot of b << 16 | region mask << 24 (0: unused)
+    const double* threshold;          // device, [CF_INTEGRALS_MAX_ENTRIES]
+    double z_surface;
+    int32_t mask_kind, n_fields, n_entries;
+};
+int integrals_bucket(int n_entries);          // the compile-time entry count an integrator of n_entries runs with: 8 / 16 / 32
+unsigned integrals_tiles(const GridDesc& G);
+// the tile kernel on min(tiles, max_blocks) workgroups (0: one per tile), then the combination into record[0 … n_entries)
+hipError_t launch_integrals(hipStream_t st, const IntegralArgs& K, const GridDesc& G, double* record, int max_blocks);
 
 }  // namespace coflux

@@ -303,6 +303,7 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         s.time_fraction = total - whole;
         return s;
     };
+    CHECK(integrals_room(ctx, first_step, nsteps));   // a series that would overflow: nothing is launched
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (int n = 0; n < S->n_ocean_states; ++n) {
         if (ctx->dev.mask_kind != CF_MASK_NONE && !S->ocean_states[n].mask) return fail(ctx, CF_ERR_INVALID, "ocean state %d has no mask", n);
@@ -378,6 +379,9 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         // the same steps.  Queued behind every launch of the step — the face stresses of the merged and tail forms included
         if (ctx->average && (step + 1) % ctx->average_stride == 0)
             CHECK(average_collect(ctx->average, ctx->average_stride * ctx->average_step_weight));
+        // an attached integrator (cf_attach_integrals): the same rule, one record per collected step
+        if (ctx->integrals && (step + 1) % ctx->integrals_stride == 0)
+            CHECK(integrals_collect(ctx->integrals, ctx->integrals_time_origin + (double)(step + 1) * ctx->integrals_step_seconds));
     }
     return CF_OK;
 }

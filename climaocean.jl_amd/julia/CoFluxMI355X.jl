@@ -348,6 +348,58 @@ attach_average!(b, a::Union{Nothing, CoFluxAverage}, stride = 1, step_weight = 1
     check(b.ctx, ccall((:cf_attach_average, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64),
                        b.ctx, isnothing(a) ? C_NULL : a.ptr, stride, step_weight))
 
+# ---- surface integrals on the device: scalar time series (omip_diagnostics.jl:194-218, visualize/common.jl:715-787) -----
+# An integrator turns surface fields into records of area-weighted, masked, regional integrals (one pass per collection)
+# and keeps the series on the device; read_integrals is the only host synchronisation.  attach_integrals! makes
+# time_steps! append a record every `stride` steps.
+const CF_INTEGRAND_ONE, CF_INTEGRAND_FIELD, CF_INTEGRAND_PRODUCT, CF_INTEGRAND_ABOVE = Int32(0), Int32(1), Int32(2), Int32(3)
+struct CfIntegralEntry
+    kind::Int32; region_bit::Int32
+    a::Ptr{Float64}; b::Ptr{Float64}
+    threshold::Float64
+end
+CfIntegralEntry() = CfIntegralEntry(CF_INTEGRAND_ONE, 0, C_NULL, C_NULL, 0.0)
+struct CfIntegralsDesc
+    struct_size::Int32; n_entries::Int32
+    area::Ptr{Float64}; mask::Ptr{Cvoid}; region::Ptr{UInt8}
+    max_workgroups::Int32; reserved::Int32
+    entries::NTuple{32, CfIntegralEntry}
+end
+function CfIntegralsDesc(entries::Vector{CfIntegralEntry}; area = C_NULL, mask = C_NULL, region = C_NULL, max_workgroups = 0)
+    length(entries) <= 32 || error("CoFluxMI355X: at most 32 integral entries")
+    padded = ntuple(k -> k <= length(entries) ? entries[k] : CfIntegralEntry(), 32)
+    return CfIntegralsDesc(sizeof(CfIntegralsDesc), length(entries), area, mask, region, max_workgroups, 0, padded)
+end
+mutable struct CoFluxIntegrals
+    ptr::Ptr{Cvoid}
+    backend::CoFluxBackend
+    n_entries::Int
+end
+function CoFluxIntegrals(b::CoFluxBackend, desc::CfIntegralsDesc, capacity)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(b.ctx, ccall((:cf_integrals_create, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfIntegralsDesc}, Int32, Ref{Ptr{Cvoid}}),
+                       b.ctx, desc, capacity, out))
+    q = CoFluxIntegrals(out[], b, desc.n_entries)
+    finalizer(x -> ccall((:cf_integrals_destroy, libcoflux), Cint, (Ptr{Cvoid},), x.ptr), q)
+    return q
+end
+collect!(q::CoFluxIntegrals, time) = check(C_NULL, ccall((:cf_integrals_collect, libcoflux), Cint, (Ptr{Cvoid}, Float64), q.ptr, time))
+reset!(q::CoFluxIntegrals) = check(C_NULL, ccall((:cf_integrals_reset, libcoflux), Cint, (Ptr{Cvoid},), q.ptr))
+function integrals_count(q::CoFluxIntegrals)
+    n = Ref{Int64}(0)
+    check(C_NULL, ccall((:cf_integrals_count, libcoflux), Cint, (Ptr{Cvoid}, Ref{Int64}), q.ptr, n))
+    return n[]
+end
+function read_integrals(q::CoFluxIntegrals, first = 0, n = integrals_count(q) - first)
+    values = zeros(Float64, q.n_entries, n); times = zeros(Float64, n)   # column r is record first + r
+    check(C_NULL, ccall((:cf_integrals_read, libcoflux), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+                        q.ptr, first, n, values, times))
+    return (values = values, times = times)
+end
+attach_integrals!(b, q::Union{Nothing, CoFluxIntegrals}, stride = 1, time_origin = 0.0, step_seconds = 1.0) =
+    check(b.ctx, ccall((:cf_attach_integrals, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Float64),
+                       b.ctx, isnothing(q) ? C_NULL : q.ptr, stride, time_origin, step_seconds))
+
 # ---- SeaIceAlbedo(hi, hs, Ts) (atmosphere.jl:30-44) and compute_sea_ice_ocean_fluxes! (omip_simulation.jl:71-77) ------
 mutable struct CfSeaIceAlbedoParams
     struct_size::Int32; reserved::Int32

@@ -40,7 +40,9 @@ extern "C" {
                           * CF_SOLVER_TABLES_R2(_OUTER) and the 768-thread geometry (CF_OPT_AO_CHUNK = 3072) retired; CF_OPT_AO_CHUNK and
                           * CF_OPT_INTERP_TILE_CAP are experiment options (COFLUX_EXPERIMENTS=1); 4: time averages accumulated on the
                           * device (cf_average_*, cf_attach_average; cf_run_schedule unchanged); 5: CF_SKIN_LINEARISED, a third
-                          * value of cf_sea_ice_params.skin_temperature_scheme that older libraries reject */
+                          * value of cf_sea_ice_params.skin_temperature_scheme that older libraries reject; still 5: surface integrals and
+                          * their time series (cf_integrals_*, cf_attach_integrals) are purely additive — no existing struct or
+                          * entry point changed, a host finds them by symbol */
 
 /* status codes */
 #define CF_OK 0
@@ -945,6 +947,84 @@ int cf_average_collect(cf_average* a, double weight);
 int cf_average_weight(cf_average* a, double* total, int64_t* samples);
 /* Footprint: cf_time_steps' own, and cf_average_collect's at every collected step.                                     */
 int cf_attach_average(cf_ctx* ctx, cf_average* a, int32_t stride, double step_weight);
+
+/* ------------------------------------------------------------------------------------------
+ * Area-weighted surface integrals and their time series on the device: the scalars every reference run derives from the
+ * surface — the global means of the `:averages` writer (OMIPConfigurations/omip_diagnostics.jl:194-218) and the Arctic /
+ * Antarctic sea-ice volume ∫ hᵢ ℵ dA, area ∫ ℵ dA and extent ∫ [ℵ > 0.15] dA of compute_ice_diagnostics
+ * (experiments/OMIPSimulations/scripts/visualize/common.jl:715-787, Integral(field; condition)).  An integrator holds the
+ * weights (cell areas, wet mask, region bits), up to CF_INTEGRALS_MAX_ENTRIES entries and a series of `capacity` records in
+ * device memory that the library owns.  The value of entry e in a record is
+ *     Σ A · x   over the interior cells that are wet AND have bit `region_bit` set in `region`,
+ *     x = 1 (CF_INTEGRAND_ONE) | a (_FIELD) | a·b (_PRODUCT; b = a gives a square) | 1 if a > threshold else 0 (_ABOVE, strict).
+ * Excluded cells (land, outside the region, halos) do not contribute at all: their values are selected away, so they may
+ * be NaN or Inf, the area's included.  An entry whose region is empty is exactly 0.0.  A cell may be in several regions
+ * or in none.
+ * One collection is one pass over the interior plus a tiny combination launch; every distinct `a` / `b` array is loaded
+ * once per cell however many entries name it (at most CF_INTEGRALS_MAX_FIELDS distinct arrays): 8·(distinct fields) + 8
+ * (area) + mask + 1 (region) bytes per cell.
+ * Reproducibility: the bits of a record depend only on the interior values, the weights and (nx, ny) — not on the halo
+ * widths or where the arrays start in memory, not on `max_workgroups` or the device's CU count, not on whether the host
+ * or cf_time_steps made the collection, not on what else is attached, not on the run.  No floating-point atomics: fixed
+ * tiles of 1024 consecutive interior cells (row by row) → per-tile partial sums → a fixed-order combination
+ * (csrc/coflux_integrals.hip states the order).  a·b, ·A and every addition are rounded separately (no FMA).
+ *   cf_integrals_create   CF_ERR_INVALID for a wrong struct_size, n_entries outside 1…CF_INTEGRALS_MAX_ENTRIES, an unknown
+ *                         kind, a NULL `a` (every kind but _ONE) or NULL `b` (_PRODUCT), a region bit outside 0…7, a
+ *                         non-finite threshold (_ABOVE), more than CF_INTEGRALS_MAX_FIELDS distinct arrays, max_workgroups < 0
+ *                         or capacity < 1.  The pointers are borrowed: the arrays outlive the integrator.
+ *   cf_integrals_destroy  detaches the integrator if it is attached; an integrator outlived by its context may still be
+ *                         destroyed (every other call on it then fails).
+ *   cf_integrals_collect  record number `count` is written, stream ordered, no host synchronisation; `time` is kept on the
+ *                         host.  CF_ERR_INVALID, and nothing is launched or written, when the series is full.
+ *   cf_integrals_count    the number of records since the last reset.
+ *   cf_integrals_read     synchronises the context's stream and copies records first … first + n − 1 (n × n_entries doubles,
+ *                         record-major) and their times (h_times may be NULL).  Any sub-range; reading does not consume.
+ *   cf_integrals_reset    the series is empty again.  No device work.
+ *   cf_attach_integrals   cf_time_steps collects `q` after the cf_update_state of every step s (global index) with
+ *                         (s + 1) % stride == 0, stamped time_origin + (s + 1) · step_seconds; NULL detaches.  One integrator
+ *                         per context, independent of the averager of cf_attach_average: both may be attached, the averager
+ *                         collects first.  Stream order puts the collection behind every write of the step (every
+ *                         CF_OPT_MERGED_PREFETCH / _HALO_IN_SOLVER_LAUNCH / _SOLVER_PATH / _FUSED_NET mode alike); a run split
+ *                         into CF_PIPELINE_CONTINUING calls yields the same records as one call.  A cf_time_steps call whose
+ *                         collections (they follow from first_step, nsteps and stride) would not fit the series fails with
+ *                         CF_ERR_INVALID before it launches anything.  CF_ERR_INVALID for stride < 1, a non-finite time
+ *                         origin or step, or an integrator of another context.
+ * Each context integrates its own slab; combining slabs is the host's sum of a few doubles.
+ * ---------------------------------------------------------------------------------------- */
+#define CF_INTEGRALS_MAX_ENTRIES 32
+#define CF_INTEGRALS_MAX_FIELDS 32
+#define CF_INTEGRAND_ONE 0
+#define CF_INTEGRAND_FIELD 1
+#define CF_INTEGRAND_PRODUCT 2
+#define CF_INTEGRAND_ABOVE 3
+typedef struct cf_integral_entry {
+    int32_t kind;          /* CF_INTEGRAND_* */
+    int32_t region_bit;    /* 0…7: the bit of `region` a cell must carry */
+    const double* a;       /* ocean-grid f64 array (every kind but _ONE) */
+    const double* b;       /* _PRODUCT only */
+    double threshold;      /* _ABOVE only */
+} cf_integral_entry;
+typedef struct cf_integrals_desc {
+    int32_t struct_size;   /* sizeof(cf_integrals_desc) */
+    int32_t n_entries;     /* 1…CF_INTEGRALS_MAX_ENTRIES */
+    const double* area;    /* ocean-grid f64 cell areas Az; NULL: 1 */
+    const void* mask;      /* wet mask of the context's mask kind (CF_MASK_U8 / _BOTTOM_HEIGHT); NULL or CF_MASK_NONE: all wet */
+    const uint8_t* region; /* ocean-grid uint8 array of region bits; NULL: every cell is in region bit 0 only */
+    int32_t max_workgroups; /* 0: one workgroup per tile; > 0 caps the launch (scheduling only: never a bit of a record) */
+    int32_t reserved;
+    cf_integral_entry entries[CF_INTEGRALS_MAX_ENTRIES];
+} cf_integrals_desc;
+typedef struct cf_integrals cf_integrals;
+int cf_integrals_create(cf_ctx* ctx, const cf_integrals_desc* desc, int32_t capacity, cf_integrals** out);
+int cf_integrals_destroy(cf_integrals* q);
+/* Footprint: reads the entries' arrays, the area, the mask and the region on I; writes no caller array (the record goes to
+ * the library's own series).                                                                                           */
+int cf_integrals_collect(cf_integrals* q, double time);
+int cf_integrals_count(cf_integrals* q, int64_t* records);
+int cf_integrals_read(cf_integrals* q, int64_t first, int64_t n, double* h_values, double* h_times);
+int cf_integrals_reset(cf_integrals* q);
+/* Footprint: cf_time_steps' own, and cf_integrals_collect's at every collected step.                                   */
+int cf_attach_integrals(cf_ctx* ctx, cf_integrals* q, int32_t stride, double time_origin, double step_seconds);
 
 /* Builds the flux solver's schedule for `mask` (the cost-balanced chunk table and the wet lists, three tiny kernels and
  * two 4-byte read-backs) ahead of the first step instead of inside it.  Optional: cf_compute_atmosphere_ocean_fluxes,
