@@ -297,6 +297,21 @@ class FluxContext:
         """Build the solver's schedule for `mask` now instead of inside the first step."""
         self._check(self.lib.cf_ensure_chunk_table(self._h, _ptr(mask)), "cf_ensure_chunk_table")
 
+    def debug_chunk_table(self):
+        """(begins, wet_counts, lists_valid) of the chunk table as the device built it (cf_debug_chunk_table, after
+        ensure_chunk_table or a solve): int32 arrays of n + 1 and n entries and whether the static wet lists are in use."""
+        n, valid = C.c_int(), C.c_int()
+        capacity = 1024
+        while True:
+            begins, counts = np.zeros(capacity, dtype=np.int32), np.zeros(capacity, dtype=np.int32)
+            rc = self.lib.cf_debug_chunk_table(self._h, begins.ctypes.data_as(C.POINTER(C.c_int)),
+                                               counts.ctypes.data_as(C.POINTER(C.c_int)), capacity, C.byref(n), C.byref(valid))
+            if rc != 0 and n.value + 1 > capacity:   # too few ints: *n_chunks says how many
+                capacity = n.value + 1
+                continue
+            self._check(rc, "cf_debug_chunk_table")
+            return begins[:n.value + 1].copy(), counts[:n.value].copy(), bool(valid.value)
+
     def solver_path(self):
         """(lean_kernel, fused): which kernels cf_update_state launches for the current formulation and options; fused = 0
         three launches, 1 net fluxes in the solver's epilogue, 2 the interpolation in its prologue as well."""

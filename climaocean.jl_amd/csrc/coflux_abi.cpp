@@ -737,6 +737,28 @@ int cf_ensure_chunk_table(cf_ctx* ctx, const void* mask) {
     return ensure_chunk_table(ctx, mask);
 }
 
+// self-test hook: the table as the device kernels built it (tests/test_mask_atlas.py holds it against a NumPy partition)
+int cf_debug_chunk_table(cf_ctx* ctx, int* begins, int* wet_counts, int capacity, int* n_chunks, int* lists_valid) {
+    if (!ctx || !n_chunks || !lists_valid) return fail(ctx, CF_ERR_INVALID, "cf_debug_chunk_table: bad arguments");
+    *n_chunks = 0;
+    *lists_valid = 0;
+    if (!ctx->chunk_valid || !ctx->d_chunk_begins || ctx->launch.n_chunks <= 0)
+        return fail(ctx, CF_ERR_INVALID, "cf_debug_chunk_table: no chunk table is valid (cf_ensure_chunk_table first)");
+    const int n = ctx->launch.n_chunks;
+    *n_chunks = n;
+    *lists_valid = ctx->launch.d_wet_pos ? 1 : 0;
+    if (!begins || !wet_counts || capacity < n + 1)
+        return fail(ctx, CF_ERR_INVALID, "cf_debug_chunk_table: %d ints are too few for %d chunks", capacity, n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<int> info((size_t)4 * n, 0);
+    HIP_TRY(ctx, hipMemcpyAsync(begins, ctx->d_chunk_begins, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->d_lean_info)
+        HIP_TRY(ctx, hipMemcpyAsync(info.data(), ctx->d_lean_info, sizeof(int) * info.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int c = 0; c < n; ++c) wet_counts[c] = info[(size_t)4 * c];
+    return CF_OK;
+}
+
 // A requested interpolation that rides in another launch stages its JRA55 tile (4 waves × 9 variables × cap × 8 B) in THAT
 // launch's dynamic LDS: a solver launch has ≥ 40 960 B (CF_OPT_INTERP_TILE_CAP ≤ 142), the face-stress launch 64 KB.  A cap
 // beyond that falls through to the stand-alone interpolation on the main stream.

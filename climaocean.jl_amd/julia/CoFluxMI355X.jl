@@ -307,6 +307,22 @@ discard_prefetched_atmosphere_state!(b) =
 ensure_chunk_table!(b, mask::Ptr{Cvoid}) =
     check(b.ctx, ccall((:cf_ensure_chunk_table, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), b.ctx, mask))
 
+# self-test hook: the table as built — (begins, wet cells per chunk, static lists in use); after ensure_chunk_table!
+function debug_chunk_table(b; capacity::Integer = 1024)
+    n, valid = Ref{Cint}(0), Ref{Cint}(0)
+    while true
+        begins, counts = zeros(Cint, capacity), zeros(Cint, capacity)
+        rc = ccall((:cf_debug_chunk_table, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}, Cint, Ref{Cint}, Ref{Cint}),
+                   b.ctx, begins, counts, capacity, n, valid)
+        if rc != 0 && n[] + 1 > capacity
+            capacity = n[] + 1
+            continue
+        end
+        check(b.ctx, rc)
+        return begins[1:n[] + 1], counts[1:n[]], valid[] == 1
+    end
+end
+
 # ---- run!(simulation) of a prescribed-ocean model inside the library (bench / offline forcing runs) -------------------
 struct CfRunSchedule
     struct_size::Int32; n_ocean_states::Int32

@@ -491,6 +491,13 @@ int cf_debug_eval(cf_ctx* ctx, int function, int n, const double* d_x, double* d
  * out[0] = number of rounds, then per round (wet cells per chunk, number of chunks).  Returns the wet-cell cost
  * unit, or −1 if `capacity` ints are too few. */
 int cf_debug_chunk_plan(long long total_cost, int cu_count, int forced_wet_per_chunk, int* out, int capacity);
+/* Self-test hook: the chunk table as the device built it for the context's current mask (cf_ensure_chunk_table first).
+ * Synchronises the context's stream.  begins[0..n] = first window cell (row-major over the ring-inclusive window) of
+ * every chunk, closed by the cell count; wet_counts[0..n-1] = wet cells listed per chunk; *n_chunks = n is always set;
+ * *lists_valid = 1 when the static wet lists are in use (0: some chunk overflowed its list and every workgroup classifies
+ * its range per call).  Returns CF_ERR_INVALID when no table is valid or `capacity` < n + 1 ints per array (*n_chunks is
+ * still set then: retry with n + 1).  Changes no state. */
+int cf_debug_chunk_table(cf_ctx* ctx, int* begins, int* wet_counts, int capacity, int* n_chunks, int* lists_valid);
 int cf_sync(cf_ctx* ctx);
 
 /* Device memory for callers that cannot own HIP memory themselves (Julia without AMDGPU.jl). */
