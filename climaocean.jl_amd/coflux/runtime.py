@@ -312,6 +312,13 @@ class FluxContext:
             self._check(rc, "cf_debug_chunk_table")
             return begins[:n.value + 1].copy(), counts[:n.value].copy(), bool(valid.value)
 
+    def debug_interp_grid(self):
+        """(rows, blocks) of the tiled interpolation on this context's grid under its options (cf_debug_interp_grid): rows of 64
+        cells per wave tile — automatic, or what abi.OPT_INTERP_TILE_ROWS forces — and workgroups; launches nothing."""
+        rows, blocks = C.c_int(), C.c_int()
+        self._check(self.lib.cf_debug_interp_grid(self._h, C.byref(rows), C.byref(blocks)), "cf_debug_interp_grid")
+        return rows.value, blocks.value
+
     def solver_path(self):
         """(lean_kernel, fused): which kernels cf_update_state launches for the current formulation and options; fused = 0
         three launches, 1 net fluxes in the solver's epilogue, 2 the interpolation in its prologue as well."""

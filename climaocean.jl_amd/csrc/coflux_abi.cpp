@@ -536,6 +536,11 @@ int cf_set_option(cf_ctx* ctx, int option, int value) {
             if (value != 0 && (value < 16 || value > 224)) return fail(ctx, CF_ERR_INVALID, "interp tile cap %d: 0 (LDS-free gather kernel) or 16…224", value);
             ctx->launch.interp_cap = value;
             return CF_OK;
+        case CF_OPT_INTERP_TILE_ROWS:
+            if (!experiment_knob("COFLUX_EXPERIMENTS")) return fail(ctx, CF_ERR_INVALID, "CF_OPT_INTERP_TILE_ROWS is an experiment option: start the process with COFLUX_EXPERIMENTS=1");
+            if (value != 0 && value != 1 && value != 2 && value != 4) return fail(ctx, CF_ERR_INVALID, "interp tile rows %d: 0 (automatic), 1, 2 or 4", value);
+            ctx->launch.interp_rows = value;
+            return CF_OK;
         case CF_OPT_TRIP_HINTS:
             if (value < 0 || value > 3) return fail(ctx, CF_ERR_INVALID, "trip hints %d: 0 (off), 1 (on), 2 (automatic), 3 (on, the lean kernel in quarter-chunk windows)", value);
             if (ctx->lean_hints && value != 1 && value != 3) ctx->chunk_valid = false;  // the lean kernel's lists go back to index order
@@ -756,6 +761,13 @@ int cf_debug_chunk_table(cf_ctx* ctx, int* begins, int* wet_counts, int capacity
         HIP_TRY(ctx, hipMemcpyAsync(info.data(), ctx->d_lean_info, sizeof(int) * info.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int c = 0; c < n; ++c) wet_counts[c] = info[(size_t)4 * c];
+    return CF_OK;
+}
+
+// self-test hook: the tiled interpolation's launch shape on this context's grid under its options (tests/test_weight_atlas.py)
+int cf_debug_interp_grid(cf_ctx* ctx, int* rows, int* blocks) {
+    if (!ctx || !rows || !blocks) return fail(ctx, CF_ERR_INVALID, "cf_debug_interp_grid: bad arguments");
+    interpolate_grid(ctx->launch, ctx->grid, rows, blocks);
     return CF_OK;
 }
 

@@ -184,7 +184,9 @@ void interpolate_grid(const LaunchCfg& L, const GridDesc& G, int* rows_out, int*
     const int wx = G.nx + 2 * G.ring, wy = G.ny + 2 * G.ring;
     const int tiles_x = (wx + 63) / 64;
     const long tiles4 = (long)tiles_x * ((wy + 3) / 4) * 256 / (L.cu_count > 0 ? L.cu_count : 256);
-    const int rows = tiles4 >= 1200 ? 4 : (tiles4 >= 600 ? 2 : 1);
+    const int auto_rows = tiles4 >= 1200 ? 4 : (tiles4 >= 600 ? 2 : 1);
+    // (experiments and the weight atlas of the test suite: CF_OPT_INTERP_TILE_ROWS picks the instantiation on any surface)
+    const int rows = L.interp_rows == 1 || L.interp_rows == 2 || L.interp_rows == 4 ? L.interp_rows : auto_rows;
     const int ntiles = tiles_x * ((wy + rows - 1) / rows);
     int blocks = (ntiles + IT_WAVES - 1) / IT_WAVES;
     // Everything resident at once (≤ 4 workgroups per CU: LDS) but not evenly — 817 workgroups on 256 CUs leave 49 CUs

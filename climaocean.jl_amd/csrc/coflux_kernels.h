@@ -28,6 +28,7 @@ struct HaloRider;
 struct LaunchCfg {
     int solver;              // CF_SOLVER_*
     int interp_cap;          // float2 entries per variable of a wave's LDS-staged JRA55 tile
+    int interp_rows;         // CF_OPT_INTERP_TILE_ROWS: rows of 64 cells per wave tile, 1 / 2 / 4 (0 = automatic, by surface size)
     int ao_chunk;            // wet cells per solver workgroup: 256 / 512 / 768 (0 = automatic)
     int cu_count;            // compute units of the device (sizes the automatic chunk)
     const double* d_tables;  // device copy of the solver tables (coflux_tables.cpp)

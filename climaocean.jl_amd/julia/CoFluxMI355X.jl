@@ -323,6 +323,13 @@ function debug_chunk_table(b; capacity::Integer = 1024)
     end
 end
 
+# self-test hook: (rows of 64 cells per wave tile, workgroups) of the tiled interpolation on this context's grid and options
+function debug_interp_grid(b)
+    rows, blocks = Ref{Cint}(0), Ref{Cint}(0)
+    check(b.ctx, ccall((:cf_debug_interp_grid, libcoflux), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}), b.ctx, rows, blocks))
+    return Int(rows[]), Int(blocks[])
+end
+
 # ---- run!(simulation) of a prescribed-ocean model inside the library (bench / offline forcing runs) -------------------
 struct CfRunSchedule
     struct_size::Int32; n_ocean_states::Int32

@@ -42,7 +42,8 @@ extern "C" {
                           * device (cf_average_*, cf_attach_average; cf_run_schedule unchanged); 5: CF_SKIN_LINEARISED, a third
                           * value of cf_sea_ice_params.skin_temperature_scheme that older libraries reject; still 5: surface integrals and
                           * their time series (cf_integrals_*, cf_attach_integrals) are purely additive — no existing struct or
-                          * entry point changed, a host finds them by symbol */
+                          * entry point changed, a host finds them by symbol; likewise CF_OPT_INTERP_TILE_ROWS (an experiment option)
+                          * and cf_debug_interp_grid */
 
 /* status codes */
 #define CF_OK 0
@@ -340,8 +341,9 @@ int cf_set_stream(cf_ctx* ctx, void* hip_stream);
 
 /* Options (cf_set_option).  None of them changes what is computed beyond the stated tolerance.  TEN are part of the drop-in
  * surface: CF_OPT_SOLVER, _TRIP_HINTS, _FUSED_NET, _ICE_ORBIT_SHORTCUT, _MERGED_PREFETCH, _SOLVER_PATH, _CERTIFIED_BUDGET,
- * _ICE_FREE_CELLS, _LATENCY_LAYOUT, _HALO_IN_SOLVER_LAUNCH.  Two more are EXPERIMENT options, accepted only in a process started with
- * COFLUX_EXPERIMENTS=1 (measurements, and the test-suite's schedule-invariance checks): CF_OPT_INTERP_TILE_CAP, CF_OPT_AO_CHUNK.
+ * _ICE_FREE_CELLS, _LATENCY_LAYOUT, _HALO_IN_SOLVER_LAUNCH.  Three more are EXPERIMENT options, accepted only in a process started with
+ * COFLUX_EXPERIMENTS=1 (measurements, and the test-suite's schedule-invariance checks): CF_OPT_INTERP_TILE_CAP, CF_OPT_AO_CHUNK,
+ * CF_OPT_INTERP_TILE_ROWS.
  * Numbers 2, 5 and 8 were CF_OPT_MAX_BLOCKS, _PROFILE_STRIDE and _FUSED_INTERP (retired in ABI version 3: cf_set_option
  * answers CF_ERR_INVALID).                                                                                              */
 #define CF_OPT_SOLVER 0           /* CF_SOLVER_*                                                   */
@@ -462,6 +464,11 @@ int cf_set_stream(cf_ctx* ctx, void* hip_stream);
                                    * (tests/test_steps.py: 2 and 4 ranks, lat-lon and tripolar).  0 (default): the exchange kernel of its
                                    * own.  What it buys on N devices is UNMEASURED: no multi-GPU node has run either form;
                                    * one launch boundary and a 3–5 µs kernel per step are what it removes from a 26 µs slab step.        */
+#define CF_OPT_INTERP_TILE_ROWS 15 /* EXPERIMENT option.  Rows of 64 cells per wave tile of the tiled interpolation: 0 (default) = automatic
+                                   * by surface size (4 from ≈ 307 k window cells per 256 CUs, 2 from ≈ 154 k, else 1), or 1, 2, 4 = that
+                                   * instantiation on any surface — in the interpolation's own launch, the merged stress + interpolation
+                                   * launch and the tail workgroups of the solver launches alike.  Results do not depend on it, bit for
+                                   * bit (tests/test_weight_atlas.py); cf_debug_interp_grid reports the choice.                          */
 #define CF_SOLVER_TABLES 0  /* default: reference iteration path on LDS-tabulated ψ / log / exp.  Accuracy of the tabulated primitives
                                against libm (tests/test_gpu_parity.py::test_device_primitives_accuracy): ψ_m, ψ_h ≤ 5e-12 of
                                max(|ψ|, 1) for |ζ| < 1024 (every state a converging iteration can stop on) and ≤ 2e-10 for
@@ -498,6 +505,11 @@ int cf_debug_chunk_plan(long long total_cost, int cu_count, int forced_wet_per_c
  * its range per call).  Returns CF_ERR_INVALID when no table is valid or `capacity` < n + 1 ints per array (*n_chunks is
  * still set then: retry with n + 1).  Changes no state. */
 int cf_debug_chunk_table(cf_ctx* ctx, int* begins, int* wet_counts, int capacity, int* n_chunks, int* lists_valid);
+/* Self-test hook (host arithmetic only, launches nothing, changes no state): the shape of the tiled interpolation on the
+ * context's grid under its current options, wherever it runs (its own launch, the merged stress + interpolation launch, the
+ * tail workgroups of a solver launch): *rows = rows of 64 cells per wave tile (1, 2 or 4: automatic by surface size and the
+ * device's CU count, or what CF_OPT_INTERP_TILE_ROWS forces), *blocks = workgroups of four waves. */
+int cf_debug_interp_grid(cf_ctx* ctx, int* rows, int* blocks);
 int cf_sync(cf_ctx* ctx);
 
 /* Device memory for callers that cannot own HIP memory themselves (Julia without AMDGPU.jl). */
