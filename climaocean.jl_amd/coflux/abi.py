@@ -33,6 +33,8 @@ PIPELINE_WITHIN_CALL, PIPELINE_CONTINUING = 1, 2   # cf_run_schedule.pipeline
 AVERAGE_MAX_FIELDS = 16                            # fields of one time averager (cf_average_create)
 INTEGRALS_MAX_ENTRIES, INTEGRALS_MAX_FIELDS = 32, 32   # entries / distinct arrays of one surface integrator (cf_integrals_create)
 INTEGRAND_ONE, INTEGRAND_FIELD, INTEGRAND_PRODUCT, INTEGRAND_ABOVE = 0, 1, 2, 3
+REGRID_MAX_FIELDS = 16                               # fields of one apply of a surface regridder (cf_regrid_apply)
+REGRID_MEAN, REGRID_SUM = 0, 1
 SOLVER_PATH_EXACT, SOLVER_PATH_CERTIFIED = 0, 1      # how the Monin–Obukhov fixed point is reached (include/coflux.h)
 CERTIFIED_EXACT_FLAG = 0x100                         # `iterations` of a cell the certified path solved on the exact path
 SOLVER_TABLES, SOLVER_LIBM = 0, 1
@@ -206,6 +208,12 @@ class IntegralsDesc(C.Structure):
                 ("entries", IntegralEntry * INTEGRALS_MAX_ENTRIES)]
 
 
+class RegridDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("mode", C.c_int32), ("n_rows", C.c_int64), ("nnz", C.c_int64),
+                ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("weight", C.c_void_p), ("mask", C.c_void_p),
+                ("max_workgroups", C.c_int32), ("reserved", C.c_int32)]
+
+
 # Every symbol include/coflux.h declares (tests check they are all exported).
 EXPORTED_SYMBOLS = (
     "cf_version", "cf_default_flux_params", "cf_create", "cf_destroy", "cf_last_error",
@@ -228,6 +236,7 @@ EXPORTED_SYMBOLS = (
     "cf_average_create", "cf_average_destroy", "cf_average_reset", "cf_average_collect", "cf_average_weight", "cf_attach_average",
     "cf_integrals_create", "cf_integrals_destroy", "cf_integrals_collect", "cf_integrals_count", "cf_integrals_read",
     "cf_integrals_reset", "cf_attach_integrals",
+    "cf_regrid_create", "cf_regrid_destroy", "cf_regrid_apply",
 )
 
 PACKAGE_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -376,6 +385,9 @@ def load_library(path=None):
     lib.cf_integrals_read.argtypes = [vp, C.c_int64, C.c_int64, c_double_p, c_double_p]
     lib.cf_integrals_reset.argtypes = [vp]
     lib.cf_attach_integrals.argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double]
+    lib.cf_regrid_create.argtypes = [vp, C.POINTER(RegridDesc), C.POINTER(vp)]
+    lib.cf_regrid_destroy.argtypes = [vp]
+    lib.cf_regrid_apply.argtypes = [vp, C.c_int32, C.POINTER(vp), C.POINTER(vp), vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("cf_last_error", "cf_device_alloc", "cf_window_host_buffer", "cf_build_stamp"):

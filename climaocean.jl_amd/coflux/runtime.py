@@ -426,6 +426,14 @@ class FluxContext:
         self._check(self.lib.cf_attach_integrals(self._h, h, int(stride), float(time_origin), float(step_seconds)),
                     "cf_attach_integrals")
 
+    # -- sparse surface operators -----------------------------------------------------------------
+    def regridder(self, row_ptr, col, weight, mask=None, mode="mean", max_workgroups=0):
+        """A fixed sparse surface operator on the device (cf_regrid_create): CSR over destination rows — row_ptr (n_rows + 1),
+        col (interior cell numbers j·nx + i) and weight (≥ 0), host arrays as coflux.regridding builds them; `mask`: the
+        context's wet mask (ocean-grid device array); mode "mean" (Σ w x / Σ w over the wet entries, NaN where that is 0) or
+        "sum".  apply(sources) regrids up to abi.REGRID_MAX_FIELDS ocean-grid fields in one pass."""
+        return SurfaceRegridder(self, row_ptr, col, weight, mask, mode, max_workgroups)
+
     # -- peer-direct halo rows / tripolar fold -----------------------------------------------------
     def peer_halo_export(self, max_fields=4, max_rows=2):
         buf = C.create_string_buffer(abi.PEER_HANDLE_BYTES)
@@ -582,6 +590,77 @@ class SurfaceIntegrator:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self.lib.cf_integrals_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+REGRID_MODES = dict(mean=abi.REGRID_MEAN, sum=abi.REGRID_SUM)
+
+
+class SurfaceRegridder:
+    """cf_regrid_*: apply(sources) → one dense device tensor of n_rows doubles per source, dst[r] = Σ w x / Σ w over the wet
+    entries of row r ("mean"; NaN where no entry is wet) or Σ w x ("sum"), and `coverage` = Σ w — one pass for all sources, no
+    host synchronisation.  The operator is copied to the device at construction; the mask is borrowed and kept alive here."""
+
+    def __init__(self, ctx, row_ptr, col, weight, mask=None, mode="mean", max_workgroups=0):
+        self.ctx, self.lib = ctx, ctx.lib
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        weight = np.ascontiguousarray(weight, dtype=np.float64)
+        if row_ptr.ndim != 1 or row_ptr.size < 2 or col.ndim != 1 or col.shape != weight.shape:
+            raise ValueError("regridder: row_ptr (n_rows + 1 entries, n_rows ≥ 1), col and weight (nnz entries each) are 1-D arrays")
+        if mask is not None and not (mask.is_cuda and mask.is_contiguous() and tuple(mask.shape) == ctx.shape):
+            raise ValueError(f"mask is a contiguous device array of shape {ctx.shape}")
+        self.n_rows, self.nnz, self.mask = row_ptr.size - 1, col.size, mask
+        self.mode = REGRID_MODES[mode] if isinstance(mode, str) else int(mode)
+        desc = abi.RegridDesc()
+        desc.struct_size, desc.mode, desc.n_rows, desc.nnz = C.sizeof(abi.RegridDesc), self.mode, self.n_rows, self.nnz
+        desc.row_ptr, desc.col, desc.weight = row_ptr.ctypes.data, col.ctypes.data, weight.ctypes.data
+        desc.mask, desc.max_workgroups = (mask.data_ptr() if mask is not None else None), int(max_workgroups)
+        h = C.c_void_p()
+        ctx._check(self.lib.cf_regrid_create(ctx._h, C.byref(desc), C.byref(h)), "cf_regrid_create")
+        self._h = h
+        self.coverage = None
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise CofluxError(f"{what} failed ({rc}): {self.lib.cf_last_error(None).decode()}")
+
+    def apply(self, sources, out=None, coverage=True):
+        """Regrids `sources` (ocean-grid float64 device fields) into `out` (device tensors of at least n_rows doubles; new ones
+        by default) and returns them; `self.coverage` is the row sums of the wet weights (coverage=False: not written, None;
+        a tensor: written there)."""
+        sources = list(sources)
+        for t in sources:
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == self.ctx.shape):
+                raise ValueError(f"regridded fields are contiguous float64 device arrays of shape {self.ctx.shape}")
+        n = len(sources)
+        if out is None:
+            out = [torch.empty(self.n_rows, dtype=torch.float64, device=self.ctx.device) for _ in sources]
+        out = list(out)
+        if len(out) != n:
+            raise ValueError(f"{n} sources, {len(out)} outputs")
+        if coverage is True:
+            coverage = torch.empty(self.n_rows, dtype=torch.float64, device=self.ctx.device)
+        elif coverage is False:
+            coverage = None
+        for t in out + ([coverage] if coverage is not None else []):
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() >= self.n_rows):
+                raise ValueError(f"outputs are contiguous float64 device arrays of at least {self.n_rows} elements")
+        src = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in sources])
+        dst = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in out])
+        self._check(self.lib.cf_regrid_apply(self._h, n, src, dst, _ptr(coverage)), "cf_regrid_apply")
+        self.coverage = coverage
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self.lib.cf_regrid_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

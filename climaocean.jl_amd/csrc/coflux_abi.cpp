@@ -471,6 +471,7 @@ int cf_destroy(cf_ctx* ctx) {
     if (!ctx) return CF_OK;
     average_forget_context(ctx);
     integrals_forget_context(ctx);
+    regrid_forget_context(ctx);
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     if (ctx->d_tables) (void)hipFree(ctx->d_tables);

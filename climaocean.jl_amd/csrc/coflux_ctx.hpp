@@ -158,6 +158,8 @@ struct cf_ctx {
     cf_integrals* integrals = nullptr;
     int32_t integrals_stride = 1;
     double integrals_time_origin = 0.0, integrals_step_seconds = 0.0;
+    // surface regridders (coflux_regrid.cpp): every one made on this context (cf_destroy orphans them)
+    std::vector<cf_regrid*> regridders;
 };
 
 struct cf_average {
@@ -176,6 +178,15 @@ struct cf_integrals {
     int64_t capacity = 0, count = 0;
     std::vector<double> times;   // of the records, host side
     double* d_series = nullptr;  // [capacity][n_entries]; the partial sums and the entries' descriptors lie behind it
+};
+
+struct cf_regrid {
+    cf_ctx* ctx = nullptr;       // NULL once the context is destroyed
+    int device = 0;
+    RegridTables tables{};
+    int64_t n_rows = 0;
+    int max_blocks = 0;
+    void* d_block = nullptr;     // the one allocation behind every table
 };
 
 // sets the thread-local and the context's last-error text and returns `code`
@@ -207,5 +218,7 @@ int integrals_collect(cf_integrals* q, double time);
 int integrals_room(cf_ctx* ctx, int64_t first_step, int nsteps);
 // coflux_integrals.cpp: cf_destroy orphans the context's integrators
 void integrals_forget_context(cf_ctx* ctx);
+// coflux_regrid.cpp: cf_destroy orphans the context's regridders
+void regrid_forget_context(cf_ctx* ctx);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state)
 extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx);

@@ -180,4 +180,39 @@ unsigned integrals_tiles(const GridDesc& G);
 // the tile kernel on min(tiles, max_blocks) workgroups (0: one per tile), then the combination into record[0 … n_entries)
 hipError_t launch_integrals(hipStream_t st, const IntegralArgs& K, const GridDesc& G, double* record, int max_blocks);
 
+// cf_regrid_apply (coflux_regrid.hip): a fixed sparse surface operator on up to CF_REGRID_MAX_FIELDS fields in one pass.
+// The host (coflux_regrid.cpp) turns the CSR operator into the tables below at create; all of them are device arrays.
+constexpr int REGRID_SHORT = 64;        // rows of at most this many entries: one 16-lane group each, four rows per wave
+constexpr int REGRID_SEGMENT = 256;     // longer rows: segments of this many consecutive entries, one wave each
+constexpr int REGRID_PARTIAL = CF_REGRID_MAX_FIELDS + 1;   // doubles per segment partial: N of every field, then D
+constexpr uint32_t REGRID_NONE = 0xffffffffu;
+struct RegridSegment {                  // one wave's work on a long row
+    uint32_t row, start, count, slot;   // entries [start, start + count); slot REGRID_NONE: the row's only segment, finished here
+};
+struct RegridLongRow {                  // a row of several segments, finished by the combination launch
+    uint32_t row, first_slot, n_segments, reserved;
+};
+struct RegridTables {
+    const uint32_t* offset;             // [nnz] halo-layout element offset of the entry's source cell
+    const double* weight;               // [nnz]
+    const uint32_t* row_start;          // [n_rows + 1]
+    const uint32_t* short_rows;         // [4 · n_short_units] row index or REGRID_NONE (padding of the last unit)
+    const RegridSegment* segments;      // [n_segments]
+    const RegridLongRow* long_rows;     // [n_long_rows]
+    double* partial;                    // [slots][REGRID_PARTIAL]
+    const void* mask;
+    double z_surface;
+    uint32_t n_short_units, n_segments, n_long_rows;
+    int32_t mask_kind, mode;
+};
+struct RegridFields {
+    const double* src[CF_REGRID_MAX_FIELDS];
+    double* dst[CF_REGRID_MAX_FIELDS];
+    double* coverage;
+    int32_t n_fields;
+};
+// the row kernel (instantiated for 1 / 4 / 8 / 16 ≥ n_fields fields) on min(ceil(units / 4), max_blocks) workgroups (0: 8 per
+// compute unit), then the combination of the rows of several segments
+hipError_t launch_regrid(hipStream_t st, const RegridTables& T, const RegridFields& F, int max_blocks, int cu_count);
+
 }  // namespace coflux

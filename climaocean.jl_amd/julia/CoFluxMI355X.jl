@@ -423,6 +423,42 @@ attach_integrals!(b, q::Union{Nothing, CoFluxIntegrals}, stride = 1, time_origin
     check(b.ctx, ccall((:cf_attach_integrals, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Float64),
                        b.ctx, isnothing(q) ? C_NULL : q.ptr, stride, time_origin, step_seconds))
 
+# ---- a fixed sparse surface operator on the device (visualize/cache.jl:918-937, 983-1011) ---------------------------------
+# CSR over destination rows: `row_ptr` (0-based, n_rows + 1 entries), `col` (0-based interior cell numbers j·nx + i) and
+# `weight` (≥ 0) are host arrays, copied to the device at construction — a SparseMatrixCSC of ConservativeRegridding.jl goes
+# in through its transpose.  regrid!(rg, sources, destinations; coverage) applies it to up to 16 ocean-grid device fields
+# in one pass: Σ w x / Σ w over the wet entries of a row (CF_REGRID_MEAN; NaN where no entry is wet) or Σ w x (CF_REGRID_SUM).
+const CF_REGRID_MEAN, CF_REGRID_SUM = Int32(0), Int32(1)
+const CF_REGRID_MAX_FIELDS = 16
+struct CfRegridDesc
+    struct_size::Int32; mode::Int32
+    n_rows::Int64; nnz::Int64
+    row_ptr::Ptr{Int64}; col::Ptr{Int32}; weight::Ptr{Float64}; mask::Ptr{Cvoid}
+    max_workgroups::Int32; reserved::Int32
+end
+mutable struct CoFluxRegridder
+    ptr::Ptr{Cvoid}
+    backend::CoFluxBackend
+    n_rows::Int
+end
+function CoFluxRegridder(b::CoFluxBackend, row_ptr::Vector{Int64}, col::Vector{Int32}, weight::Vector{Float64};
+                         mask = C_NULL, mode = CF_REGRID_MEAN, max_workgroups = 0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve row_ptr col weight begin
+        desc = CfRegridDesc(sizeof(CfRegridDesc), mode, length(row_ptr) - 1, length(col), pointer(row_ptr), pointer(col),
+                            pointer(weight), mask, max_workgroups, 0)
+        check(b.ctx, ccall((:cf_regrid_create, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfRegridDesc}, Ref{Ptr{Cvoid}}), b.ctx, desc, out))
+    end
+    rg = CoFluxRegridder(out[], b, length(row_ptr) - 1)
+    finalizer(x -> ccall((:cf_regrid_destroy, libcoflux), Cint, (Ptr{Cvoid},), x.ptr), rg)
+    return rg
+end
+function regrid!(rg::CoFluxRegridder, sources::Vector{Ptr{Float64}}, destinations::Vector{Ptr{Float64}}; coverage = C_NULL)
+    length(sources) == length(destinations) || error("CoFluxMI355X: one destination per source")
+    check(C_NULL, ccall((:cf_regrid_apply, libcoflux), Cint, (Ptr{Cvoid}, Int32, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Float64}),
+                        rg.ptr, length(sources), sources, destinations, coverage))
+end
+
 # ---- SeaIceAlbedo(hi, hs, Ts) (atmosphere.jl:30-44) and compute_sea_ice_ocean_fluxes! (omip_simulation.jl:71-77) ------
 mutable struct CfSeaIceAlbedoParams
     struct_size::Int32; reserved::Int32

@@ -43,7 +43,7 @@ extern "C" {
                           * value of cf_sea_ice_params.skin_temperature_scheme that older libraries reject; still 5: surface integrals and
                           * their time series (cf_integrals_*, cf_attach_integrals) are purely additive — no existing struct or
                           * entry point changed, a host finds them by symbol; likewise CF_OPT_INTERP_TILE_ROWS (an experiment option)
-                          * and cf_debug_interp_grid */
+                          * and cf_debug_interp_grid, and the sparse surface operator (cf_regrid_*) */
 
 /* status codes */
 #define CF_OK 0
@@ -1044,6 +1044,67 @@ int cf_integrals_read(cf_integrals* q, int64_t first, int64_t n, double* h_value
 int cf_integrals_reset(cf_integrals* q);
 /* Footprint: cf_time_steps' own, and cf_integrals_collect's at every collected step.                                   */
 int cf_attach_integrals(cf_ctx* ctx, cf_integrals* q, int32_t stride, double time_origin, double step_seconds);
+
+/* ------------------------------------------------------------------------------------------
+ * A fixed sparse surface operator applied on the device: the conservative regridding of surface fields onto the shared
+ * 360 × 180 latitude–longitude grid behind every figure of a reference run (regrid_surface_to_latlon,
+ * experiments/OMIPSimulations/scripts/visualize/cache.jl:983-1011, applied to SURFACE_LATLON_FIELDS, :1026-1042) and its
+ * zonal means (compute_zonal_mean, cache.jl:918-937).  Both are one sparse matrix applied to `field · mask` and to `mask`
+ * and a division; the operator is fixed per grid, the apply runs for every field of every record.  Still ABI 5: additive.
+ * The operator is CSR over destination rows: row r owns entries row_ptr[r] … row_ptr[r + 1] − 1, entry k names the source
+ * cell col[k] = j·nx + i of the interior (the numbering of the surface integrals) with weight[k] ≥ 0.  Empty rows and
+ * repeated columns within a row are legal.  With W(r) the entries of row r whose source cell is wet,
+ *     D = Σ_{k∈W} weight[k],        N_f = Σ_{k∈W} weight[k] · src_f[col[k]],        coverage[r] = D,
+ *     dst_f[r] = N_f / D, NaN where D == 0 (CF_REGRID_MEAN: cache.jl:1006-1009) | N_f, exactly +0.0 for an empty or all-land
+ *     row (CF_REGRID_SUM).
+ * Excluded entries (land) are selected away, never multiplied by zero: a land cell's field value may be NaN or Inf; a NaN
+ * in a wet cell propagates.  One apply serves up to CF_REGRID_MAX_FIELDS fields in one pass: the entry's column, weight and
+ * mask byte are loaded once for all of them and each field costs one 8-byte gather per entry —
+ * nnz · (13 + 8 K) + 8 · n_rows · (K + 1) algorithmic bytes for K fields.
+ * Reproducibility: weight·x, every addition and the division are rounded separately (no FMA), there are no floating-point
+ * atomics, and THE SUMMATION ORDER OF A ROW IS A FUNCTION OF THAT ROW'S ENTRY COUNT n ALONE (land entries keep their place
+ * and add a selected +0.0):
+ *     n ≤ 64: 16 lanes; lane g adds entries g, g + 16, g + 32, g + 48 in that order to +0.0 (an absent entry adds +0.0), the
+ *             lanes are combined by the butterfly v += shfl_xor(v, 8), 4, 2, 1;
+ *     n > 64: segments of 256 consecutive entries; in a segment lane l of 64 adds its entries l, l + 64, l + 128, l + 192 to
+ *             +0.0, then the butterfly 32 … 1; the segment partials are added in segment order, ((p₀ + p₁) + p₂) + ….
+ * D is summed in the same order (csrc/coflux_regrid.hip).  The bits of dst_f[r] therefore depend only on the row's (col,
+ * weight) in the order given, the mask and the interior values — not on the row's index or its neighbours in the operator,
+ * the halo widths or where the arrays start in memory, `max_workgroups` or the device's CU count, n_fields or which other
+ * fields ride along, or the run.
+ *   cf_regrid_create   copies the operator to the device (the host arrays may be freed afterwards; `mask` is borrowed and
+ *                      read at every apply).  CF_ERR_INVALID, with nothing allocated or launched, for a wrong struct_size,
+ *                      n_rows < 1, nnz < 0, n_rows or nnz ≥ 2³¹, a NULL row_ptr (or NULL col / weight with nnz > 0),
+ *                      row_ptr[0] != 0, a row_ptr that is not monotone, row_ptr[n_rows] != nnz, a column outside
+ *                      0 … nx·ny − 1, a negative or non-finite weight, an unknown mode or max_workgroups < 0.
+ *   cf_regrid_apply    stream ordered on the context's stream, no host synchronisation.  `src` and `dst` are HOST arrays of
+ *                      n_fields device pointers.  CF_ERR_INVALID, and nothing is launched or written, for n_fields outside
+ *                      1 … CF_REGRID_MAX_FIELDS or a NULL array or entry of `src` / `dst`; `coverage` may be NULL.
+ *   cf_regrid_destroy  a regridder outlived by its context may still be destroyed (an apply on it fails).
+ * Slabs: each context applies the operator restricted to its own columns (renumbered to its interior) in CF_REGRID_SUM mode
+ * with `coverage`; the host adds the per-slab numerators and coverages and divides.  The library does not combine slabs.
+ * ---------------------------------------------------------------------------------------- */
+#define CF_REGRID_MAX_FIELDS 16
+#define CF_REGRID_MEAN 0
+#define CF_REGRID_SUM 1
+typedef struct cf_regrid_desc {
+    int32_t struct_size;     /* sizeof(cf_regrid_desc) */
+    int32_t mode;            /* CF_REGRID_MEAN / CF_REGRID_SUM */
+    int64_t n_rows;          /* destination cells, ≥ 1 */
+    int64_t nnz;             /* entries, = row_ptr[n_rows] */
+    const int64_t* row_ptr;  /* HOST, n_rows + 1 entries, non-decreasing, row_ptr[0] = 0 */
+    const int32_t* col;      /* HOST, nnz interior cell numbers c = j·nx + i */
+    const double* weight;    /* HOST, nnz weights, finite and ≥ 0 */
+    const void* mask;        /* DEVICE wet mask of the context's mask kind (CF_MASK_U8 / _BOTTOM_HEIGHT); NULL or CF_MASK_NONE: all wet */
+    int32_t max_workgroups;  /* 0: automatic; > 0 caps the launch (scheduling only: never a bit of a result) */
+    int32_t reserved;
+} cf_regrid_desc;
+typedef struct cf_regrid cf_regrid;
+int cf_regrid_create(cf_ctx* ctx, const cf_regrid_desc* desc, cf_regrid** out);
+int cf_regrid_destroy(cf_regrid* rg);
+/* Footprint: reads every src[f] and the mask on I only (at the cells the operator names); writes exactly n_rows doubles of
+ * every dst[f] and, unless it is NULL, of coverage.                                                                     */
+int cf_regrid_apply(cf_regrid* rg, int32_t n_fields, const double* const* src, double* const* dst, double* coverage);
 
 /* Builds the flux solver's schedule for `mask` (the cost-balanced chunk table and the wet lists, three tiny kernels and
  * two 4-byte read-backs) ahead of the first step instead of inside it.  Optional: cf_compute_atmosphere_ocean_fluxes,
