@@ -31,6 +31,10 @@ OPT_SOLVER_PATH, OPT_CERTIFIED_BUDGET, OPT_ICE_FREE_CELLS, OPT_LATENCY_LAYOUT, O
 ICE_FREE_ITERATE, ICE_FREE_ZERO = 0, 1
 PIPELINE_WITHIN_CALL, PIPELINE_CONTINUING = 1, 2   # cf_run_schedule.pipeline
 AVERAGE_MAX_FIELDS = 16                            # fields of one time averager (cf_average_create)
+DERIVED_MAX_SOURCES = 16                           # distinct source arrays of one derived averager (cf_average_create_derived)
+(TERM_FIELD, TERM_PRODUCT, TERM_CENTER_X, TERM_CENTER_Y, TERM_CENTER_X_SQUARE, TERM_CENTER_Y_SQUARE, TERM_KINETIC_ENERGY,
+ TERM_EAST, TERM_NORTH) = range(9)                 # cf_average_term.kind
+TERM_AT_CENTERS = 1                                # cf_average_term.flags (EAST / NORTH)
 INTEGRALS_MAX_ENTRIES, INTEGRALS_MAX_FIELDS = 32, 32   # entries / distinct arrays of one surface integrator (cf_integrals_create)
 INTEGRAND_ONE, INTEGRAND_FIELD, INTEGRAND_PRODUCT, INTEGRAND_ABOVE = 0, 1, 2, 3
 REGRID_MAX_FIELDS = 16                               # fields of one apply of a surface regridder (cf_regrid_apply)
@@ -196,6 +200,16 @@ class InterpWeights(C.Structure):
                 ("cos_rot", C.c_void_p), ("sin_rot", C.c_void_p), ("latitude", C.c_void_p)]
 
 
+class AverageTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("a", C.c_void_p), ("b", C.c_void_p), ("scale", C.c_double),
+                ("mean", C.c_void_p)]
+
+
+class AverageDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_terms", C.c_int32), ("terms", C.POINTER(AverageTerm)),
+                ("cos_rotation", C.c_void_p), ("sin_rotation", C.c_void_p), ("max_workgroups", C.c_int32), ("reserved", C.c_int32)]
+
+
 class IntegralEntry(C.Structure):
     _fields_ = [("kind", C.c_int32), ("region_bit", C.c_int32), ("a", C.c_void_p), ("b", C.c_void_p),
                 ("threshold", C.c_double)]
@@ -234,6 +248,7 @@ EXPORTED_SYMBOLS = (
     "cf_window_upload", "cf_window_find", "cf_window_source",
     "cf_ensure_chunk_table", "cf_debug_chunk_table", "cf_debug_interp_grid", "cf_solver_path", "cf_solver_iteration_path", "cf_solver_latency_layout", "cf_comm_count", "cf_build_stamp", "cf_discard_prefetched_atmosphere_state",
     "cf_average_create", "cf_average_destroy", "cf_average_reset", "cf_average_collect", "cf_average_weight", "cf_attach_average",
+    "cf_average_create_derived",
     "cf_integrals_create", "cf_integrals_destroy", "cf_integrals_collect", "cf_integrals_count", "cf_integrals_read",
     "cf_integrals_reset", "cf_attach_integrals",
     "cf_regrid_create", "cf_regrid_destroy", "cf_regrid_apply",
@@ -378,6 +393,7 @@ def load_library(path=None):
     lib.cf_average_collect.argtypes = [vp, C.c_double]
     lib.cf_average_weight.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.cf_attach_average.argtypes = [vp, vp, C.c_int32, C.c_double]
+    lib.cf_average_create_derived.argtypes = [vp, C.POINTER(AverageDesc), C.POINTER(vp)]
     lib.cf_integrals_create.argtypes = [vp, C.POINTER(IntegralsDesc), C.c_int32, C.POINTER(vp)]
     lib.cf_integrals_destroy.argtypes = [vp]
     lib.cf_integrals_collect.argtypes = [vp, C.c_double]

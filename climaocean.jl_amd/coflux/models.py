@@ -750,14 +750,182 @@ SURFACE_FLUX_OUTPUTS = (("tauuo", "net", "u"), ("tauvo", "net", "v"), ("hfds", "
                         ("hfss", "atmosphere_ocean", "sensible_heat"), ("hfls", "atmosphere_ocean", "latent_heat"))
 
 
+# derived outputs (cf_average_create_derived): small expression objects over ocean-grid device fields.  Each lowers to one
+# term of the collection launch — the derived array is never written to memory — and `Scaled` multiplies the term's scale.
+class SurfaceExpression:
+    kind, flags, rotates = None, 0, False
+    fold_sign = -1.0   # of a y-face operand under the tripolar fold: a vector component changes sign (cf_fold_north_halo)
+
+    def __init__(self, a, b=None):
+        self.a, self.b = a, b
+
+    def term(self):
+        """(kind, flags, a, b, scale) as cf_average_term has them."""
+        return self.kind, self.flags, self.a, self.b, 1.0
+
+    def neighbours(self):
+        """(fields read at [i+1], fields read at [j+1])"""
+        kind, flags, a, b, _ = self.term()
+        faces = kind in (abi.TERM_EAST, abi.TERM_NORTH) and not flags & abi.TERM_AT_CENTERS
+        east = [a] if kind in (abi.TERM_CENTER_X, abi.TERM_CENTER_X_SQUARE, abi.TERM_KINETIC_ENERGY) or faces else []
+        north = [a] if kind in (abi.TERM_CENTER_Y, abi.TERM_CENTER_Y_SQUARE) else [b] if kind == abi.TERM_KINETIC_ENERGY or faces else []
+        return east, north
+
+
+class Product(SurfaceExpression):
+    """Product(a, b): a·b at the cell."""
+    kind = abi.TERM_PRODUCT
+
+    def __init__(self, a, b):
+        super().__init__(a, b)
+
+
+class Squared(Product):
+    """Squared(f): f·f — tossq = Squared(tos) (omip_diagnostics.jl:111-113)."""
+
+    def __init__(self, f):
+        super().__init__(f, f)
+
+
+class CenteredX(SurfaceExpression):
+    """CenteredX(u): ℑx u = (u[i] + u[i+1])/2, an x-face field at the cell centre."""
+    kind = abi.TERM_CENTER_X
+
+    def __init__(self, u):
+        super().__init__(u)
+
+
+class CenteredY(SurfaceExpression):
+    """CenteredY(v, fold_sign=-1): ℑy v = (v[j] + v[j+1])/2; fold_sign = +1 for a y-face field that is no vector component."""
+    kind = abi.TERM_CENTER_Y
+
+    def __init__(self, v, fold_sign=-1.0):
+        super().__init__(v)
+        self.fold_sign = float(fold_sign)
+
+
+class CenteredXSquare(CenteredX):
+    """CenteredXSquare(u): ℑx(u²), uu_at_ccc (omip_diagnostics.jl:13-25)."""
+    kind = abi.TERM_CENTER_X_SQUARE
+
+
+class CenteredYSquare(CenteredY):
+    """CenteredYSquare(v): ℑy(v²), vv_at_ccc."""
+    kind = abi.TERM_CENTER_Y_SQUARE
+
+
+class KineticEnergy(SurfaceExpression):
+    """KineticEnergy(u, v): (ℑx(u²) + ℑy(v²))/2, ke_at_ccc."""
+    kind = abi.TERM_KINETIC_ENERGY
+
+    def __init__(self, u, v):
+        super().__init__(u, v)
+
+
+class East(SurfaceExpression):
+    """East(u, v, at_centers=False): the geographic east component p·cos θ − q·sin θ of a grid-aligned vector, p = ℑx u and
+    q = ℑy v (face fields) or p = u, q = v with at_centers (visualize/cache.jl:462-464)."""
+    kind, rotates = abi.TERM_EAST, True
+
+    def __init__(self, u, v, at_centers=False):
+        super().__init__(u, v)
+        self.flags = abi.TERM_AT_CENTERS if at_centers else 0
+
+
+class North(East):
+    """North(u, v, at_centers=False): p·sin θ + q·cos θ."""
+    kind = abi.TERM_NORTH
+
+
+class Scaled(SurfaceExpression):
+    """Scaled(expr, factor): factor · expr, as the scale of the term (a field alone: a FIELD term); nested factors are
+    multiplied on the host."""
+
+    def __init__(self, expr, factor):
+        inner = isinstance(expr, SurfaceExpression)
+        super().__init__(expr.a if inner else expr, expr.b if inner else None)
+        self.expr, self.factor = expr, float(factor)
+        self.rotates, self.fold_sign = getattr(expr, "rotates", False), getattr(expr, "fold_sign", -1.0)
+
+    def term(self):
+        if isinstance(self.expr, SurfaceExpression):
+            kind, flags, a, b, scale = self.expr.term()
+            return kind, flags, a, b, scale * self.factor
+        return abi.TERM_FIELD, 0, self.expr, None, self.factor
+
+
+def variance(mean_sq, mean):
+    """mean(x²) − mean(x)² from two window means (visualize/cache.jl:370), host arrays; rounding may leave it slightly negative."""
+    mean = np.asarray(mean)
+    return np.asarray(mean_sq) - mean * mean
+
+
+def grid_rotation(model):
+    """(cos θ, sin θ) of the grid's i-axis against geographic east as ocean-grid device arrays: the interpolation weights'
+    on a TripolarGrid, identity arrays (1, 0) on a LatitudeLongitudeGrid.  Made once per model."""
+    itf = model.interfaces
+    if getattr(itf, "_grid_rotation", None) is None:
+        w, ctx = itf.weights, itf.context
+        if w.get("cos_rot") is not None:
+            itf._grid_rotation = (w["cos_rot"], w["sin_rot"])
+        else:
+            itf._grid_rotation = (ctx.zeros() + 1.0, ctx.zeros())
+    return itf._grid_rotation
+
+
+def omip_surface_outputs(model):
+    """The reference's `:surface` writer (omip_diagnostics.jl:106-141) for the fields this repository has, by its names: tos,
+    sos, uos, vos, the squares tossq, sossq, the centred squares uosq = ℑx(u²), vosq = ℑy(v²) and kes = ke_at_ccc
+    (omip_diagnostics.jl:13-25,166-167,197), the fluxes tauuo, tauvo, hfds, wfo, hfss, hfls, and siconc / sithick with sea
+    ice.  uosq, vosq and kes read u at [i+1] and v at [j+1]: the ocean fills those halos."""
+    itf, st = model.interfaces, model.ocean.surface_state()
+    net, ao = itf.net_fluxes._ocean_fields, itf.atmosphere_ocean_interface._fields
+    T, S, u, v = st["T"], st["S"], st["u"], st["v"]
+    out = dict(tos=T, sos=S, uos=u, vos=v, tossq=Squared(T), sossq=Squared(S),
+               uosq=CenteredXSquare(u), vosq=CenteredYSquare(v), kes=KineticEnergy(u, v))
+    groups = dict(net=net, atmosphere_ocean=ao)
+    out.update({name: groups[group][key] for name, group, key in SURFACE_FLUX_OUTPUTS})
+    ice = model.sea_ice
+    if ice is not None:
+        out["siconc"] = ice.concentration
+        if ice.thickness is not None:
+            out["sithick"] = ice.thickness
+    return out
+
+
+RHO_OCEAN, CP_OCEAN = 1026.0, 3991.86795711963   # visualize/common.jl:17-18
+
+
+def geographic_surface_outputs(model):
+    """What the reference's figures make of the time means before regridding (linear, so averaged directly): the wind stress
+    in N m⁻² as geographic east / north components, −ρ · (ℑx tauuo, ℑy tauvo) rotated (cache.jl:372-386); the surface
+    current the same way (cache.jl:430-466); hfds in W m⁻², ρ · cp · JT (cache.jl:359-361).  The rotation is grid_rotation's.
+    The stress terms read tauuo at [i+1] and tauvo at [j+1], halo cells the library does not write: SurfaceFluxAverages fills
+    them before every collection (see there).  The current's terms read the ocean's own u and v halos."""
+    itf, st = model.interfaces, model.ocean.surface_state()
+    net = itf.net_fluxes._ocean_fields
+    return dict(tauuo_east=Scaled(East(net["u"], net["v"]), -RHO_OCEAN), tauvo_north=Scaled(North(net["u"], net["v"]), -RHO_OCEAN),
+                uos_east=East(st["u"], st["v"]), vos_north=North(st["u"], st["v"]), hfds=Scaled(net["T"], RHO_OCEAN * CP_OCEAN))
+
+
 class SurfaceFluxAverages:
     """An averaged output writer for surface fields: SurfaceFluxAverages(model; outputs, schedule = AveragedTimeInterval(5days)).
     The default outputs are the OMIP set tauuo, tauvo, hfds, wfo (the ocean's net u, v, T, S fluxes) and hfss, hfls (the
     atmosphere–ocean interface's sensible and latent heat); any dict name → ocean-grid device field works, sea-ice fields
     included.  The means are accumulated on the device (cf_average_collect: one launch per sample); a completed window is
-    appended to `windows` as (t_k, {name: interior numpy array}) and handed to `on_window(t_k, arrays)`.  No file format."""
+    appended to `windows` as (t_k, {name: interior numpy array}) and handed to `on_window(t_k, arrays)`.  No file format.
+    An output may also be a derived quantity — Squared, Product, CenteredX/Y, CenteredX/YSquare, KineticEnergy, East, North,
+    Scaled (omip_surface_outputs and geographic_surface_outputs are presets): the outputs then go through
+    cf_average_create_derived, abi.AVERAGE_MAX_FIELDS terms per launch, with `rotation` = (cos θ, sin θ) device arrays
+    (default: grid_rotation(model)) for East / North.  More outputs than that make several averagers (`averagers`);
+    `averager` is only the first of them, so attaching it to time_steps() collects the first sixteen outputs alone.
+    Halos: a term that reads [i+1] / [j+1] of a field the LIBRARY writes (the net fluxes, the interface fluxes: written on the
+    interior only) gets that field's first east halo column / north halo row filled here before every collection —
+    periodic wrap in x (zero on a grid that does not close in longitude: the face is a wall), the tripolar fold
+    (cf_fold_north_halo, y-face, the expression's fold_sign) or zero on a grid without a fold (the north wall).  A single
+    slab only: neighbour slabs are not exchanged.  Every other field's halos (the ocean state's) are the caller's."""
 
-    def __init__(self, model, outputs=None, schedule=None, on_window=None):
+    def __init__(self, model, outputs=None, schedule=None, on_window=None, rotation=None):
         itf = model.interfaces
         if outputs is None:
             groups = dict(net=itf.net_fluxes._ocean_fields, atmosphere_ocean=itf.atmosphere_ocean_interface._fields)
@@ -767,10 +935,62 @@ class SurfaceFluxAverages:
         self.on_window = on_window
         ctx = itf.context
         self.means = {name: ctx.zeros() for name in self.outputs}
-        self.averager = ctx.average(list(self.outputs.values()), list(self.means.values()))
+        if not any(isinstance(o, SurfaceExpression) for o in self.outputs.values()):
+            self.averagers = [ctx.average(list(self.outputs.values()), list(self.means.values()))]
+        else:
+            if rotation is None and any(getattr(o, "rotates", False) for o in self.outputs.values()):
+                rotation = grid_rotation(model)
+            self.averagers = [ctx.derived_average(terms, *(rotation or (None, None))) for terms in self.descriptor()]
+            self._plan_halo_fills()
+        self.averager = self.averagers[0]
         self.windows = []
         g = model.ocean.grid
         (self._nx, self._ny, _), (self._hx, self._hy, _) = g.size, g.halo
+
+    def descriptor(self):
+        """The term tables (kind, a, b, scale, flags, mean) of the outputs, abi.AVERAGE_MAX_FIELDS terms per averager."""
+        terms = []
+        for name, o in self.outputs.items():
+            kind, flags, a, b, scale = o.term() if isinstance(o, SurfaceExpression) else (abi.TERM_FIELD, 0, o, None, 1.0)
+            terms.append((kind, a, b, scale, flags, self.means[name]))
+        n = abi.AVERAGE_MAX_FIELDS
+        return [terms[k:k + n] for k in range(0, len(terms), n)]
+
+    _east, _north = (), ()
+
+    def _plan_halo_fills(self):
+        itf = self.model.interfaces
+        groups = [itf.net_fluxes._ocean_fields, itf.atmosphere_ocean_interface._fields, getattr(itf.net_fluxes, "_sea_ice_fields", {})]
+        if getattr(itf, "atmosphere_sea_ice_interface", None) is not None:
+            groups.append(itf.atmosphere_sea_ice_interface._fields)
+        written = {t.data_ptr() for g in groups for t in g.values() if t is not None}
+        east, north = {}, {}
+        for o in self.outputs.values():
+            if isinstance(o, SurfaceExpression):
+                e, n = o.neighbours()
+                east.update({t.data_ptr(): t for t in e if t.data_ptr() in written})
+                north.update({t.data_ptr(): (t, o.fold_sign) for t in n if t.data_ptr() in written})
+        self._east, self._north = list(east.values()), list(north.values())
+
+    def fill_halos(self):
+        """The first east halo column / north halo row of the library-written fields that a term reads there (class docstring)."""
+        if not (self._east or self._north):
+            return
+        g, itf = self.model.ocean.grid, self.model.interfaces
+        nx, ny, hx, hy = self._nx, self._ny, self._hx, self._hy
+        lon = getattr(g, "longitude", None)
+        periodic = getattr(g, "fold_north", False) or not isinstance(lon, tuple) or abs(abs(lon[1] - lon[0]) - 360.0) < 1e-9
+        for t in self._east:
+            if periodic:
+                t[hy:hy + ny, hx + nx] = t[hy:hy + ny, hx]
+            else:
+                t[hy:hy + ny, hx + nx] = 0.0
+        if self._north and getattr(itf, "fold_north", False):
+            fields = [t for t, _ in self._north]
+            itf.context.fold_north_halo(fields, [abi.FOLD_Y_FACE] * len(fields), [s for _, s in self._north], rows=1)
+        else:
+            for t, _ in self._north:
+                t[hy + ny, hx:hx + nx] = 0.0
 
     def initialize(self, simulation):
         self.schedule.initialize(self.model.clock.time, simulation.dt)
@@ -778,11 +998,14 @@ class SurfaceFluxAverages:
     def write(self, clock):
         weight, t_k = self.schedule.sample(clock.time, clock.iteration)
         if weight is not None:
-            self.averager.collect(weight)
+            self.fill_halos()
+            for averager in self.averagers:
+                averager.collect(weight)
         if t_k is not None:
             hx, hy = self._hx, self._hy
             arrays = {name: m[hy:hy + self._ny, hx:hx + self._nx].to("cpu", copy=True).numpy() for name, m in self.means.items()}
-            self.averager.reset()
+            for averager in self.averagers:
+                averager.reset()
             self.windows.append((t_k, arrays))
             if self.on_window is not None:
                 self.on_window(t_k, arrays)

@@ -403,6 +403,15 @@ class FluxContext:
         ocean-grid float64 fields; collect(weight) after each sample, read the means, reset() for the next window."""
         return TimeAverager(self, sources, means)
 
+    def derived_average(self, terms, cos_rotation=None, sin_rotation=None, max_workgroups=0):
+        """A device-side running mean of derived quantities (cf_average_create_derived), a TimeAverager like average()'s.
+        `terms`: up to abi.AVERAGE_MAX_FIELDS tuples (kind, a, b, scale, flags, mean) — kind a name of TERM_KINDS or
+        abi.TERM_*, `a` / `b` / `mean` ocean-grid float64 fields (b None where the kind has none), the sample is x · scale;
+        `cos_rotation` / `sin_rotation`: ocean-grid float64 fields, for "east" / "north" terms.  Where a kind reads [i+1] /
+        [j+1] the caller has filled the first east halo column / north halo row of that field.  `max_workgroups` caps the
+        launch (0: the library's; scheduling only)."""
+        return TimeAverager.derived(self, terms, cos_rotation, sin_rotation, max_workgroups)
+
     def attach_average(self, averager, stride=1, step_weight=1.0):
         """time_steps() collects `averager` after every step s with (s + 1) % stride == 0, weight stride · step_weight
         (cf_attach_average); None detaches."""
@@ -478,6 +487,11 @@ class FluxContext:
         self._check(self.lib.cf_halo_exchange_rows(self._h, arr, len(tensors), rows), "cf_halo_exchange_rows")
 
 
+TERM_KINDS = dict(field=abi.TERM_FIELD, product=abi.TERM_PRODUCT, center_x=abi.TERM_CENTER_X, center_y=abi.TERM_CENTER_Y,
+                  center_x_square=abi.TERM_CENTER_X_SQUARE, center_y_square=abi.TERM_CENTER_Y_SQUARE,
+                  kinetic_energy=abi.TERM_KINETIC_ENERGY, east=abi.TERM_EAST, north=abi.TERM_NORTH)
+
+
 class TimeAverager:
     """cf_average_*: after collections of weights w₁ … wₙ every `means[k]` holds Σ w f / Σ w of `sources[k]` on the interior
     (halos untouched), accumulated on the device in one launch per collection.  The library borrows the pointers: the tensors
@@ -497,6 +511,39 @@ class TimeAverager:
         h = C.c_void_p()
         ctx._check(self.lib.cf_average_create(ctx._h, n, src, dst, C.byref(h)), "cf_average_create")
         self._h = h
+
+    @classmethod
+    def derived(cls, ctx, terms, cos_rotation=None, sin_rotation=None, max_workgroups=0):
+        """cf_average_create_derived (FluxContext.derived_average): `sources` are the distinct input fields, rotation
+        arrays included, `terms` the table as given."""
+        self = cls.__new__(cls)
+        self.ctx, self.lib = ctx, ctx.lib
+        self.terms = [tuple(t) for t in terms]
+        if len(self.terms) > abi.AVERAGE_MAX_FIELDS:
+            raise ValueError(f"{len(self.terms)} terms (at most {abi.AVERAGE_MAX_FIELDS})")
+        table = (abi.AverageTerm * max(len(self.terms), 1))()
+        self.sources, self.means = [], []
+
+        def pointer(t, what):
+            if t is None:
+                return None
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == ctx.shape):
+                raise ValueError(f"{what} is a contiguous float64 device array of shape {ctx.shape}")
+            if what != "mean" and not any(t is s for s in self.sources):
+                self.sources.append(t)
+            return t.data_ptr()
+        for k, (kind, a, b, scale, flags, mean) in enumerate(self.terms):
+            T = table[k]
+            T.kind = TERM_KINDS[kind] if isinstance(kind, str) else int(kind)
+            T.flags, T.scale = int(flags), float(scale)
+            T.a, T.b, T.mean = pointer(a, f"term {k}: a"), pointer(b, f"term {k}: b"), pointer(mean, "mean")
+            self.means.append(mean)
+        desc = abi.AverageDesc(C.sizeof(abi.AverageDesc), len(self.terms), table, pointer(cos_rotation, "cos_rotation"),
+                               pointer(sin_rotation, "sin_rotation"), int(max_workgroups), 0)
+        h = C.c_void_p()
+        ctx._check(self.lib.cf_average_create_derived(ctx._h, C.byref(desc), C.byref(h)), "cf_average_create_derived")
+        self._h = h
+        return self
 
     def _check(self, rc, what):
         if rc != 0:

@@ -10,7 +10,10 @@ int average_collect(cf_average* a, double weight) {
     const double c_prev = store ? 0.0 : a->total / total;
     const double c_new = store ? 1.0 : weight / total;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_average(ctx->stream, a->fields, a->nfields, ctx->grid, store, c_prev, c_new));
+    if (a->derived)
+        HIP_TRY(ctx, launch_derived_average(ctx->stream, a->terms, ctx->grid, store, c_prev, c_new));
+    else
+        HIP_TRY(ctx, launch_average(ctx->stream, a->fields, a->nfields, ctx->grid, store, c_prev, c_new));
     a->total = total;
     ++a->samples;
     return CF_OK;

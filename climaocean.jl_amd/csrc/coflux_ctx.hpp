@@ -168,6 +168,8 @@ struct cf_average {
     AverageFields fields{};
     double total = 0.0;      // the window's total weight
     int64_t samples = 0;
+    bool derived = false;    // made by cf_average_create_derived (coflux_derived.cpp): `terms` replaces `fields`
+    DerivedArgs terms{};
 };
 
 struct cf_integrals {

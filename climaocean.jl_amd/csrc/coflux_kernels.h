@@ -157,6 +157,20 @@ struct AverageFields {
 };
 hipError_t launch_average(hipStream_t st, const AverageFields& F, int nfields, const GridDesc& G, bool store, double c_prev,
                           double c_new);
+// cf_average_collect of a derived averager (coflux_derived.hip): the distinct source arrays of the terms (rotation arrays
+// included) are numbered by the host; term t reads slots a[t] / b[t]; bit s of need_x / need_y: some term reads slot s at
+// [i+1] / [j+1]; cos_slot / sin_slot: −1 without an EAST / NORTH term
+struct DerivedArgs {
+    const double* src[CF_DERIVED_MAX_SOURCES];
+    double* mean[CF_AVERAGE_MAX_FIELDS];
+    double scale[CF_AVERAGE_MAX_FIELDS];
+    uint8_t kind[CF_AVERAGE_MAX_FIELDS], flags[CF_AVERAGE_MAX_FIELDS], a[CF_AVERAGE_MAX_FIELDS], b[CF_AVERAGE_MAX_FIELDS];
+    int32_t n_src, n_terms;
+    uint32_t need_x, need_y;
+    int32_t cos_slot, sin_slot;
+    int32_t max_blocks, pad;   // cf_average_desc.max_workgroups (0: the kernel's own cap); the launcher reads it, the kernel does not
+};
+hipError_t launch_derived_average(hipStream_t st, const DerivedArgs& A, const GridDesc& G, bool store, double c_prev, double c_new);
 // cf_integrals_collect (coflux_integrals.hip): one record of area-weighted, masked, regional integrals; the distinct `a` / `b`
 // arrays of the entries are numbered (field slots) by the host
 // interior cells per tile of the summation order (a constant of the record's bits; A/B builds may set it: 512 · 1 / 2 / 4)

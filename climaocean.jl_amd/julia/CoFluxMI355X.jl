@@ -371,6 +371,37 @@ attach_average!(b, a::Union{Nothing, CoFluxAverage}, stride = 1, step_weight = 1
     check(b.ctx, ccall((:cf_attach_average, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64),
                        b.ctx, isnothing(a) ? C_NULL : a.ptr, stride, step_weight))
 
+# ---- derived quantities averaged in the collection launch (omip_diagnostics.jl:13-25,111-123; visualize/cache.jl:359-466) --
+# Squares, face → centre means, centred squares, kinetic energy and the rotation to geographic east / north, each times a
+# scale, evaluated per cell inside the averager's launch: the derived array never exists in memory.  The result is an
+# ordinary CoFluxAverage (collect!, reset!, average_weight, attach_average!).
+const CF_TERM_FIELD, CF_TERM_PRODUCT, CF_TERM_CENTER_X, CF_TERM_CENTER_Y = Int32(0), Int32(1), Int32(2), Int32(3)
+const CF_TERM_CENTER_X_SQUARE, CF_TERM_CENTER_Y_SQUARE, CF_TERM_KINETIC_ENERGY = Int32(4), Int32(5), Int32(6)
+const CF_TERM_EAST, CF_TERM_NORTH = Int32(7), Int32(8)
+const CF_TERM_AT_CENTERS = Int32(1)
+struct CfAverageTerm
+    kind::Int32; flags::Int32
+    a::Ptr{Float64}; b::Ptr{Float64}
+    scale::Float64
+    mean::Ptr{Float64}
+end
+struct CfAverageDesc
+    struct_size::Int32; n_terms::Int32
+    terms::Ptr{CfAverageTerm}
+    cos_rotation::Ptr{Float64}; sin_rotation::Ptr{Float64}
+    max_workgroups::Int32; reserved::Int32
+end
+function CoFluxAverage(b::CoFluxBackend, terms::Vector{CfAverageTerm}; cos_rotation = C_NULL, sin_rotation = C_NULL, max_workgroups = 0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve terms begin
+        desc = CfAverageDesc(sizeof(CfAverageDesc), length(terms), pointer(terms), cos_rotation, sin_rotation, max_workgroups, 0)
+        check(b.ctx, ccall((:cf_average_create_derived, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfAverageDesc}, Ref{Ptr{Cvoid}}), b.ctx, desc, out))
+    end
+    a = CoFluxAverage(out[], b, unique(vcat([t.a for t in terms], [t.b for t in terms if t.b != C_NULL])), [t.mean for t in terms])
+    finalizer(x -> ccall((:cf_average_destroy, libcoflux), Cint, (Ptr{Cvoid},), x.ptr), a)
+    return a
+end
+
 # ---- surface integrals on the device: scalar time series (omip_diagnostics.jl:194-218, visualize/common.jl:715-787) -----
 # An integrator turns surface fields into records of area-weighted, masked, regional integrals (one pass per collection)
 # and keeps the series on the device; read_integrals is the only host synchronisation.  attach_integrals! makes

@@ -968,6 +968,76 @@ int cf_average_weight(cf_average* a, double* total, int64_t* samples);
 int cf_attach_average(cf_ctx* ctx, cf_average* a, int32_t stride, double step_weight);
 
 /* ------------------------------------------------------------------------------------------
+ * Derived surface quantities averaged in the collection launch: what a reference run averages beyond arrays that exist —
+ * the squares tossq, sossq (omip_diagnostics.jl:111-123; variances are mean(x²) − mean(x)², visualize/cache.jl:366-370),
+ * the centred squares of the face velocities and the kinetic energy (uu_at_ccc = ℑx(u²), vv_at_ccc = ℑy(v²),
+ * ke_at_ccc = (ℑx(u²) + ℑy(v²))/2, omip_diagnostics.jl:13-25) — and what every figure does to a time mean, all of it linear
+ * and so commuting with the mean: face → centre (cache.jl:378-386), rotation to geographic east / north with the grid's
+ * (cos θ, sin θ) (cache.jl:406-466), scaling to CMIP units (cache.jl:359-361,378).
+ *
+ * cf_average_create_derived returns an ordinary cf_average: cf_average_collect / _reset / _weight / _destroy and
+ * cf_attach_average work on it unchanged.  Each of its n_terms (1 … CF_AVERAGE_MAX_FIELDS) turns arrays into one SAMPLE per
+ * interior cell (i, j), and the sample enters the recurrence above in place of f: the first collection of a window stores
+ * m = sample and never reads m, every later one computes m = (m · c_prev) + (sample · c_new).  With x per kind as in the
+ * table below — [i+1] the cell's east neighbour, [j+1] its north neighbour, the convention of cf_ocean_surface.u / v —
+ *     sample = x · scale        (always multiplied: scale = 1.0 is exact and keeps −0.0 and NaN)
+ * (a NaN stays a NaN; its sign and payload are not part of the contract — IEEE 754 leaves them open, and a subtraction is
+ * an addition of the negated operand on this device)
+ * and every product, sum and · 0.5 rounded on its own, in the order written (no FMA).  For EAST / NORTH, p = CENTER_X(a)
+ * and q = CENTER_Y(b), or p = a and q = b with CF_TERM_AT_CENTERS; c and s are cos_rotation and sin_rotation at the cell.
+ * All arrays are float64 in the context's halo layout, 8-byte aligned.  There is no mask: every interior cell is evaluated
+ * and land values pass through (the reference masks after the time mean).  Where a term reads [i+1] / [j+1] the caller
+ * has filled the first east halo column / north halo row of that array: periodic wrap, neighbour slab or cf_fold_north_halo.
+ * The library's own outputs (cf_interface_fluxes, cf_net_ocean_fluxes) are written on the interior (and ring) only: a term
+ * that reads their [i+1] / [j+1] needs those halos filled after every step and before the collection, which a caller can do
+ * between cf_update_state and cf_average_collect but NOT inside cf_time_steps — attach such terms only on arrays whose halos
+ * the caller keeps (the ocean state), and keep face → centre terms on flux fields to the host-driven loop.
+ *
+ * CF_ERR_INVALID, with nothing allocated or launched: wrong struct_size; max_workgroups < 0 or reserved != 0; n_terms outside 1 … CF_AVERAGE_MAX_FIELDS or
+ * terms NULL; an unknown kind, a flag bit other than CF_TERM_AT_CENTERS, or that flag on a kind other than EAST / NORTH;
+ * NULL a or mean; NULL b where the kind reads it (PRODUCT, KINETIC_ENERGY, EAST, NORTH); NULL cos_rotation / sin_rotation
+ * with an EAST / NORTH term; a non-finite scale; a kind that reads [i+1] on a context with hx < 1 or [j+1] with hy < 1;
+ * more than CF_DERIVED_MAX_SOURCES distinct source arrays (the rotation arrays count when a term reads them); a mean
+ * whose parent array ((nx + 2hx)(ny + 2hy) doubles from its pointer) overlaps a source, a rotation array or another mean.
+ * The descriptor and its term table are host memory, read during the call only.
+ *
+ * Footprint of a collection (ONE launch for all terms; each distinct source array is loaded once per cell however many
+ * terms name it, the [i+1] value comes from the neighbouring lane): reads each source on I, plus column nx (rows
+ * 0 … ny − 1) where a term reads its [i+1], plus row ny (columns 0 … nx − 1) where a term reads its [j+1]; reads and writes
+ * the means on I (the first collection of a window only writes them).  Nothing else is read or written.  The bits of
+ * every mean depend on those values and the weights alone — not on halo widths, base alignment, the launched grid or on
+ * which other terms ride along.  Algorithmic bytes per cell: 8 · (distinct source arrays) + 16 · n_terms accumulating,
+ * 8 · (distinct source arrays) + 8 · n_terms storing.
+ * ---------------------------------------------------------------------------------------- */
+#define CF_TERM_FIELD            0  /* x = a                                             */
+#define CF_TERM_PRODUCT          1  /* x = a·b            (b == a: a square)             */
+#define CF_TERM_CENTER_X         2  /* x = (a[i,j] + a[i+1,j]) · 0.5        ℑx           */
+#define CF_TERM_CENTER_Y         3  /* x = (a[i,j] + a[i,j+1]) · 0.5        ℑy           */
+#define CF_TERM_CENTER_X_SQUARE  4  /* x = (a[i,j]·a[i,j] + a[i+1,j]·a[i+1,j]) · 0.5     */
+#define CF_TERM_CENTER_Y_SQUARE  5  /* same with j+1                                     */
+#define CF_TERM_KINETIC_ENERGY   6  /* x = (X_SQUARE(a) + Y_SQUARE(b)) · 0.5             */
+#define CF_TERM_EAST             7  /* x = p·c − q·s                                     */
+#define CF_TERM_NORTH            8  /* x = p·s + q·c                                     */
+#define CF_TERM_AT_CENTERS       1  /* flag for EAST / NORTH                             */
+#define CF_DERIVED_MAX_SOURCES   16
+typedef struct cf_average_term {
+    int32_t kind, flags;
+    const double* a;
+    const double* b;
+    double scale;
+    double* mean;
+} cf_average_term;
+typedef struct cf_average_desc {
+    int32_t struct_size, n_terms;
+    const cf_average_term* terms;   /* HOST array */
+    const double* cos_rotation;     /* ocean-grid layout; EAST / NORTH only */
+    const double* sin_rotation;
+    int32_t max_workgroups;         /* cap of a collection's launch, 0 = the library's (scheduling only, never results) */
+    int32_t reserved;               /* 0 */
+} cf_average_desc;
+int cf_average_create_derived(cf_ctx* ctx, const cf_average_desc* desc, cf_average** out);
+
+/* ------------------------------------------------------------------------------------------
  * Area-weighted surface integrals and their time series on the device: the scalars every reference run derives from the
  * surface — the global means of the `:averages` writer (OMIPConfigurations/omip_diagnostics.jl:194-218) and the Arctic /
  * Antarctic sea-ice volume ∫ hᵢ ℵ dA, area ∫ ℵ dA and extent ∫ [ℵ > 0.15] dA of compute_ice_diagnostics
