@@ -532,13 +532,13 @@ int cf_set_option(cf_ctx* ctx, int option, int value) {
             ctx->launch.solver = value;
             return CF_OK;
         case CF_OPT_INTERP_TILE_CAP:
-            if (!experiment_knob("COFLUX_EXPERIMENTS")) return fail(ctx, CF_ERR_INVALID, "CF_OPT_INTERP_TILE_CAP is an experiment option: start the process with COFLUX_EXPERIMENTS=1");
+            if (!experiments_enabled()) return fail(ctx, CF_ERR_INVALID, "CF_OPT_INTERP_TILE_CAP is an experiment option: start the process with COFLUX_EXPERIMENTS=1");
             // 4 waves × 9 variables × cap × 8 B of dynamic LDS must fit a workgroup's 64 KB
             if (value != 0 && (value < 16 || value > 224)) return fail(ctx, CF_ERR_INVALID, "interp tile cap %d: 0 (LDS-free gather kernel) or 16…224", value);
             ctx->launch.interp_cap = value;
             return CF_OK;
         case CF_OPT_INTERP_TILE_ROWS:
-            if (!experiment_knob("COFLUX_EXPERIMENTS")) return fail(ctx, CF_ERR_INVALID, "CF_OPT_INTERP_TILE_ROWS is an experiment option: start the process with COFLUX_EXPERIMENTS=1");
+            if (!experiments_enabled()) return fail(ctx, CF_ERR_INVALID, "CF_OPT_INTERP_TILE_ROWS is an experiment option: start the process with COFLUX_EXPERIMENTS=1");
             if (value != 0 && value != 1 && value != 2 && value != 4) return fail(ctx, CF_ERR_INVALID, "interp tile rows %d: 0 (automatic), 1, 2 or 4", value);
             ctx->launch.interp_rows = value;
             return CF_OK;
@@ -593,7 +593,7 @@ int cf_set_option(cf_ctx* ctx, int option, int value) {
             ctx->fast.cert_budget = ctx->certified_budget / CERT_SAFETY;
             return CF_OK;
         case CF_OPT_AO_CHUNK:
-            if (!experiment_knob("COFLUX_EXPERIMENTS")) return fail(ctx, CF_ERR_INVALID, "CF_OPT_AO_CHUNK is an experiment option: start the process with COFLUX_EXPERIMENTS=1");
+            if (!experiments_enabled()) return fail(ctx, CF_ERR_INVALID, "CF_OPT_AO_CHUNK is an experiment option: start the process with COFLUX_EXPERIMENTS=1");
             if (value != 0 && value != 256 && value != 512 && value != 768 && value != 1024 && value != 1280)
                 return fail(ctx, CF_ERR_INVALID, "solver chunk %d: wet cells per workgroup must be 0 (automatic), 256, 512, 768, 1024 or 1280 "
                             "(uniform size)", value);
@@ -959,18 +959,9 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     } else if (tail) {
         int rows = 4, blocks = 1;
         interpolate_grid(ctx->launch, ctx->grid, &rows, &blocks);
-        static const int tail_cap = [] {  // (experiments: COFLUX_EXPERIMENTS=1 COFLUX_TAIL_BLOCKS=n, read once)
-            const char* e = experiment_knob("COFLUX_TAIL_BLOCKS");
-            return e ? std::max(1, std::atoi(e)) : 0;
-        }();
-        if (tail_cap > 0) blocks = std::min(blocks, tail_cap);
-        static const int tail_pos = [] {  // (experiments: COFLUX_TAIL_POS = dispatch index of the first interpolation workgroup; default: behind the solver)
-            const char* e = experiment_knob("COFLUX_TAIL_POS");
-            return e ? std::atoi(e) : -1;
-        }();
         if (tail_lean)
             HIP_TRY(ctx, launch_ao_fluxes_lean(ctx->stream, ctx->launch, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
-                                               ctx->d_land_freshwater, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out, rows, blocks, tail_pos, halo));
+                                               ctx->d_land_freshwater, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out, rows, blocks, halo));
         else
             HIP_TRY(ctx, launch_ly_fluxes_with_tail(ctx->stream, ctx->launch, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
                                                     ctx->d_land_freshwater, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out, rows, blocks));
@@ -1404,13 +1395,9 @@ int cf_update_state_sea_ice(cf_ctx* ctx, const cf_atmos_source* src, const cf_in
     // … and the ocean solve itself: its workgroups ride behind the interface solve's (both FP64-bound and independent of each
     // other; two queues do not overlap them, one launch does — profiles/r04_experiments.md §17); the stresses, which need the
     // ocean solve's ρτ everywhere, then get a launch of their own behind it
-    static const bool ocean_rides_allowed = [] {  // (experiments: COFLUX_EXPERIMENTS=1 COFLUX_OCEAN_RIDER=0 keeps the two solver launches)
-        const char* e = experiment_knob("COFLUX_OCEAN_RIDER");
-        return !(e && e[0] == '0');
-    }();
     OceanRider rider;
     CHECK(update_state_impl(ctx, src, w, ocean, atmos, ao_fluxes, ice_partition, net, ice_tail, &stress_held,
-                            ice_tail && ocean_rides_allowed ? &rider : nullptr));
+                            ice_tail ? &rider : nullptr));
     AiTail T{};
     bool interp_rides = false;
     const bool stress_after = rider.valid && stress_held;

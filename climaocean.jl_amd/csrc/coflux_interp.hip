@@ -13,7 +13,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "coflux_interp_cell.hpp"
 #include "coflux_interp_tiles.hpp"
@@ -195,11 +194,6 @@ void interpolate_grid(const LaunchCfg& L, const GridDesc& G, int* rows_out, int*
     // 600 → 17.3, 560 → 17.5 µs; no effect below 2 workgroups per CU, slightly negative above 4: left alone there)
     const int cus = L.cu_count > 0 ? L.cu_count : 256;
     if (blocks > 2 * cus && blocks <= 4 * cus) blocks = std::max(2 * cus, blocks * 25 / 32);
-    static const int blocks_cap = [] {  // (experiments: COFLUX_EXPERIMENTS=1 COFLUX_INTERP_BLOCKS=n, read once)
-        const char* cap = experiment_knob("COFLUX_INTERP_BLOCKS");
-        return cap ? std::max(1, std::atoi(cap)) : 0;
-    }();
-    if (blocks_cap > 0) blocks = std::min(blocks, blocks_cap);
     *rows_out = rows;
     *blocks_out = blocks;
 }

@@ -31,7 +31,7 @@ __device__ __forceinline__ int wave_reduce(int v) {
 __device__ __forceinline__ int wave_min(int v) { return wave_reduce<true>(v); }
 __device__ __forceinline__ int wave_max(int v) { return wave_reduce<false>(v); }
 
-// (blend_levels, bilinear, the corner convention: coflux_interp_cell.hpp — shared with the solver's fused prologue)
+// (wrap_index, blend_levels, bilinear: coflux_interp_cell.hpp — shared with the gather kernels of coflux_interp.hip)
 // LDS traffic of one wave is ordered by issue; this only stops the compiler from moving accesses.
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

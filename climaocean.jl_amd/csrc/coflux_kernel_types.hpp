@@ -166,6 +166,16 @@ inline FluxOut make_fluxes(const cf_interface_fluxes* f) {
     return FluxOut{f->sensible_heat, f->latent_heat,       f->water_vapor,       f->x_momentum,     f->y_momentum,
                    f->temperature,   f->friction_velocity, f->temperature_scale, f->humidity_scale, f->iterations};
 }
+// (either pointer may be null: no sea ice / no land runoff; no net fluxes)
+inline IceIn make_ice_in(const cf_sea_ice_fields* ice, const double* land) {
+    if (!ice) return IceIn{nullptr, nullptr, nullptr, nullptr, nullptr, land};
+    return IceIn{ice->concentration, ice->interface_heat, ice->salt_flux, ice->x_stress, ice->y_stress, land};
+}
+inline NetOut make_net_out(const cf_net_ocean_fluxes* net) {
+    if (!net) return NetOut{};
+    return NetOut{net->u, net->v, net->T, net->S, net->shortwave_surface_flux, net->upwelling_longwave, net->downwelling_longwave,
+                  net->downwelling_shortwave};
+}
 
 // FINAL: the launch assembles the net fluxes itself, so nothing in the step reads these fields again (ρτ excepted: the face-stress
 // launch does) — streaming stores (coflux_solver_shared.hpp::gstore_final has the measurements)

@@ -9,17 +9,15 @@
 
 namespace coflux {
 
-// Experiment knobs (COFLUX_LAYERS, COFLUX_SORT_WINDOWS, COFLUX_INTERP_BLOCKS: scheduling only, never results) are honoured
-// only in a process started with COFLUX_EXPERIMENTS=1, and each is read once per process — a stray variable in a
-// production environment cannot silently change what a run measures.
-inline const char* experiment_knob(const char* name) {
+// The experiment options of cf_set_option (CF_OPT_INTERP_TILE_CAP, CF_OPT_INTERP_TILE_ROWS, CF_OPT_AO_CHUNK: scheduling only,
+// never results) are accepted only in a process started with COFLUX_EXPERIMENTS=1; the variable is read once per process.
+inline bool experiments_enabled() {
     static const bool enabled = [] {
         const char* e = std::getenv("COFLUX_EXPERIMENTS");
         return e != nullptr && e[0] == '1';
     }();
-    return enabled ? std::getenv(name) : nullptr;
+    return enabled;
 }
-
 
 struct LoopParams;
 struct IceParams;
@@ -72,7 +70,7 @@ hipError_t launch_ao_fluxes_lean(hipStream_t st, const LaunchCfg& L, const DevPa
                                  const cf_ocean_surface* o, const cf_exchange_fields* e, const cf_interface_fluxes* f,
                                  const cf_sea_ice_fields* ice = nullptr, const cf_net_ocean_fluxes* net = nullptr, const double* land = nullptr,
                                  const cf_atmos_source* next_src = nullptr, const cf_interp_weights* w = nullptr,
-                                 const cf_exchange_fields* next_out = nullptr, int tail_rows = 0, int tail_blocks = 0, int tail_pos = -1,
+                                 const cf_exchange_fields* next_out = nullptr, int tail_rows = 0, int tail_blocks = 0,
                                  const HaloRider* halo = nullptr);
 // the step's peer-direct halo rows can ride in the ocean solver's launch (exact path of the lean kernel, with tail workgroups)
 bool lean_halo_rides(const LaunchCfg& L, const LoopParams& C);

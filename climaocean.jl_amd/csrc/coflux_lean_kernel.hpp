@@ -10,19 +10,9 @@
 #include "coflux_certified.hpp"
 #include "coflux_solver_shared.hpp"
 
-#ifndef CF_LEAN_WAVES
-#define CF_LEAN_WAVES 3  // waves per SIMD the narrow lean kernel is compiled for (4: ≤ 128 VGPRs; needs ≤ 40 960 B of LDS per workgroup)
-#endif
-#ifndef CF_LEAN_PREFETCH
-#define CF_LEAN_PREFETCH 0  // 1: the next batch's inputs are requested before the current batch iterates (measured: 23 more live registers cost more than the wait, 70.3 vs 68.3 us)
-#endif
-
-#ifndef LEAN_STAMP  // (per-wave time stamps: coflux_solver_lean.hip under -DCF_LEAN_STAMPS)
-#define LEAN_STAMP(q) do { } while (0)
-#define LEAN_STAMP_SET(q, v) do { } while (0)
-#endif
-
 namespace coflux {
+
+constexpr int LEAN_WAVES = 3;  // waves per SIMD the narrow lean kernel is compiled for
 
 struct LeanArgs {
     LoopParams L;
@@ -86,9 +76,6 @@ struct LeanGeom {
     static_assert(PARAMS_OFFSET % 16 == 0 && LEAN_LIST_OFFSET % 1024 == 0 && (CHUNK * 4) % 1024 == 0, "LDS-DMA pieces");
 };
 static_assert(LeanGeom<AO_BLOCK>::LDS_BYTES <= 53760, "three narrow lean solver workgroups must fit the CU's 160 KB of LDS");
-#ifndef CF_SKIP_LDS_ASSERT
-static_assert(CF_LEAN_WAVES <= 3 || LeanGeom<AO_BLOCK>::LDS_BYTES <= 40960, "four narrow lean workgroups per CU: 160 KB / 4 in 1280-byte granules");
-#endif
 
 // zero_interface_state of a land cell: all fluxes 0, T = 0 K (and, in the fused form, zero net fluxes inside the interior)
 template <bool FUSE>
@@ -121,9 +108,6 @@ __device__ __forceinline__ void lean_zero_cell(const LoopParams& L, double T_off
 // and works it off as one batch of the exact iteration (mo_iterate_lean) — compaction: sixteen batches' cells in one —;
 // cells that fail their certificate after the close, entries beyond the queue's capacity, and a workgroup's first
 // uncertified cells when its list is already handed out run the exact iteration in their own batch at once.
-#ifndef CF_CERT_NET_SALT
-#define CF_CERT_NET_SALT 1  // (0: A/B builds without the certificate's net-salinity term)
-#endif
 // LINE: the iteration in its one-wave-per-SIMD layout (mo_iterate_lean_line; coflux_solver_slab.hip builds those kernels
 // through tools/gcn_sched.py); bitwise the same results.
 // HALO (with TAIL, exact path): the step's peer-direct halo rows inside this launch.  The first
@@ -196,11 +180,9 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
     unsigned* wavehash = reinterpret_cast<unsigned*>(smem + Geo::WAVEHASH_OFFSET);
     DevParams* lp = reinterpret_cast<DevParams*>(smem + Geo::PARAMS_OFFSET);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    LEAN_STAMP(0);
     const int wx = G.nx + 2 * G.ring;
     const unsigned wx_rcp = (unsigned)K->wx_reciprocal;
     const bool use_static = K->sorted != nullptr;
-    unsigned long long stamp_iter = 0, stamp_batches = 0, stamp_trips = 0;
     // ---- start phase: everything is REQUESTED before anything is looked at, in straight-line code ----------------
     // (1) LDS-DMA (global_load_lds, 1 KB per wave instruction, no VGPR round trip): the parameter block, the tables,
     //     the chunk's sorted list; (2) the raw mask words of my share of the chunk's cell range (fingerprint, land).
@@ -280,9 +262,7 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
     if constexpr (CERT) {  // the exact-path queue (hist + cursor): every entry invalid until its producer has written it
         if (tid < 2 * AO_BINS) hist[tid] = -1;
     }
-    LEAN_STAMP(1);
     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): my mask words and my share of the DMA have landed
-    LEAN_STAMP(2);
 #pragma unroll
     for (int n = 0; n < LAND_UNROLL; ++n) asm volatile("" : "+v"(raw_lo[n]), "+v"(raw_hi[n]));
     // fingerprint of the range's wet set as the mask is NOW; land gets its zeros behind the barrier
@@ -324,7 +304,6 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
         wavehash[2 * wave + 1] = hy;
     }
     __syncthreads();  // the ONE barrier of the start phase: tables, parameters, list and fingerprints are in LDS
-    LEAN_STAMP(3);
     if constexpr (HALO) {
         // a boundary chunk: the halo rows its first batch is about to load (nothing before this point reads the ocean state)
         if (wait_south) peer_halo_wait(&opaque(K)->H.counters[2], K->H.expect_done[0]);
@@ -460,7 +439,6 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
         for (;;) {
             if constexpr (CERT) {
                 if (!straggling && start >= nwet) {
-                    LEAN_STAMP(4);  // (stamped builds: the end phase of a certified wave is its share of the exact-path queue)
                     // no batch left for this wave.  The FIRST wave of the workgroup to get here closes the queue and works it
                     // off: one atomic add of QUEUE_CLOSED onto the fill count returns the number of entries reserved so far —
                     // the closer waits for those to be written — and every later reservation lands beyond the capacity, i.e.
@@ -487,7 +465,7 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
             const bool in_range = q < limit;
             double Mp_now = 0.0;
             const double raw_So = raw.So;
-            if constexpr (CERT && CF_CERT_NET_SALT) {
+            if constexpr (CERT) {
                 if (!straggling) Mp_now = gload(opaque(K)->E.Mp, (unsigned)cell_of(start) * 8u);
             }
             // ℑxᶜᵃᵃ u, ℑyᵃᶜᵃ v: cell-centre ocean velocity from the two bracketing faces
@@ -496,22 +474,13 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
             // the interface temperature does not depend on the iteration: written now, not carried across it
             if (in_range) store_result(opaque(K)->F.Ts, (unsigned)cell_of(start) * 8u, c.Ts - T_offset);
             CertNetSalt net_salt;
-            if constexpr (CERT && CF_CERT_NET_SALT) {
+            if constexpr (CERT) {
                 // J_S is assembled from the vapour flux (by this launch's epilogue or by net_cell_kernel): the certificate is
                 // told what it may cancel against — in every certified launch, so that a cell's bits do not depend on the schedule
                 // (two FP32 registers across the iteration; the precipitation is read again, in FP64, where J_S is assembled)
                 net_salt.Mp = (float)Mp_now;
                 net_salt.floor_v = CERT_JS_FLOOR * __builtin_amdgcn_rcpf((float)raw_So * (float)P.rho_f_inv);
             }
-#if CF_LEAN_PREFETCH
-            int next;
-            if constexpr (CERT) next = straggling ? start + 64 : claim();
-            else next = claim();
-            if (next < limit) raw = request(next);
-#endif
-#ifdef CF_LEAN_STAMPS
-            const unsigned long long t_it = __builtin_readcyclecounter();
-#endif
             Scales s;
             bool finish = in_range;  // lanes whose results are written by this batch
             if constexpr (CERT) {
@@ -554,15 +523,6 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
                 if constexpr (LINE) s = mo_iterate_lean_line<COARE>(L, c, tab, in_range);
                 else s = mo_iterate_lean<COARE>(L, c, tab, in_range);
             }
-#ifdef CF_LEAN_STAMPS
-            stamp_iter += __builtin_readcyclecounter() - t_it;
-            ++stamp_batches;
-            {
-                int m = in_range ? (s.it & 0xff) : 0;
-                for (int d = 32; d; d >>= 1) m = max(m, __shfl_xor(m, d));
-                stamp_trips += (unsigned long long)m;
-            }
-#endif
             if (finish) {
                 LeanArgsPtr Ke = opaque(K);
                 // (cell coordinates recomputed from the list entry: cheaper than registers held across the iteration)
@@ -606,12 +566,10 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
                     atomicAdd(&hist[lean_bin(q, w)], 1);
                 }
             }
-#if !CF_LEAN_PREFETCH
             int next;
             if constexpr (CERT) next = straggling ? start + 64 : claim();
             else next = claim();
             if (next < limit) raw = request(next);
-#endif
             start = next;
         }
         if (have_list || end >= range_end) break;
@@ -624,9 +582,6 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
         }
         __syncthreads();
     }
-    if constexpr (!CERT) LEAN_STAMP(4);
-    LEAN_STAMP_SET(6, stamp_iter | (stamp_trips << 40));
-    LEAN_STAMP_SET(7, stamp_batches | ((unsigned long long)(have_list ? 1 : 0) << 32) | ((unsigned long long)(sorting ? 1 : 0) << 33));
     // ---- end phase: the list in next call's order (counting sort by this call's trip counts, longest first) --------
     // Behind a barrier, by the whole workgroup: a wave that runs out of batches has nothing else to do — every
     // workgroup of the kernel is resident from the start, no slot it could free is waited for — and the workgroup
@@ -657,7 +612,6 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
         for (int n = 0; n < PER_THREAD; ++n)
             if (at[n] >= 0) out[at[n]] = word[n] & LEAN_OFFSET_MASK;
     }
-    LEAN_STAMP(5);
 }
 
 }  // namespace coflux

@@ -8,8 +8,6 @@
 // device's resident-workgroup slots in whole rounds.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 #include "coflux_solver_shared.hpp"
@@ -18,18 +16,12 @@
 
 namespace coflux {
 
-#ifndef CF_LEAN_WAVES
-#define CF_LEAN_WAVES 3  // waves per SIMD the lean ocean solver is compiled for
-#endif
-
 // One workgroup geometry: 256 threads, three workgroups per CU (each with its own copy of the tables), chunks of ≤ 1280 wet
 // cells in arrival layers.  (Rounds 2-5 also shipped a 768-thread one-workgroup-per-CU geometry, CF_OPT_AO_CHUNK = 3072:
 // twelve waves of one age do not stagger themselves as three workgroups of different age do — 3 % slower on the 1/4°
 // surface, bitwise the same results; retired in round 6.)
 int wet_list_stride();
-template <int BLOCK>
 struct Geom {
-    static_assert(BLOCK == AO_BLOCK, "one workgroup geometry");
     static constexpr int CHUNK = AO_CHUNK;
     static constexpr int COUNTERS_OFFSET = TABLE_DOUBLES * 8 + CHUNK * 4;
     static constexpr int PARAMS_OFFSET = COUNTERS_OFFSET + 16 + 2 * 64 * 4;
@@ -37,8 +29,8 @@ struct Geom {
 };
 constexpr int AO_LAYER_1 = AO_CHUNK < 1024 ? AO_CHUNK : 1024, AO_LAYER_2 = AO_CHUNK < 768 ? AO_CHUNK : 768, AO_LAYER_3 = 512;  // wet cells per chunk of the last three arrival layers (plan_chunk_rounds)
 static_assert(AO_LAYER_1 <= AO_CHUNK && AO_LAYER_1 >= AO_LAYER_2 && AO_LAYER_2 >= AO_LAYER_3, "layer sizes");
-static_assert(AO_BINS == 64, "Geom<>::PARAMS_OFFSET spells the bin count out");
-static_assert(Geom<AO_BLOCK>::LDS_BYTES <= 53760, "three narrow solver workgroups must fit the CU's 160 KB of LDS");
+static_assert(AO_BINS == 64, "Geom::PARAMS_OFFSET spells the bin count out");
+static_assert(Geom::LDS_BYTES <= 53760, "three narrow solver workgroups must fit the CU's 160 KB of LDS");
 
 
 // ---------------------------------------------------------------------------------------------
@@ -197,15 +189,13 @@ int plan_chunk_rounds(long total, int cu_count, int forced_wet_per_chunk, ChunkR
         // issue priority does not change it, and it is not the CU's LDS pipe).  So that layer is cut into the SMALLEST pieces
         // that still give every CU at most one of them — 64 wet cells = one working wave where the excess allows: as few
         // cells as possible in the slow chains, no CU with a whole workgroup more than the others (1440×70: 27.3 → 26.0 µs per
-        // step, 1440×130: 33.6 → 32.6, 1440×140: 34.1 → 33.7).  (COFLUX_SLAB_SPLIT=0 with COFLUX_EXPERIMENTS=1: the uniform plan.)
+        // step, 1440×130: 33.6 → 32.6, 1440×140: 34.1 → 33.7).
         const long n256 = chunks(need, 256);
         int w2 = 256;
         const long whole = n256 > layer ? (n256 - 1) / layer : 0;  // dispatch layers of whole workgroups ahead of the last one (0: one layer is all)
         if (whole >= 1) {
-            static const bool split = [] { const char* e = experiment_knob("COFLUX_SLAB_SPLIT"); return !(e && e[0] == '0'); }();
             const long excess = need - whole * cap(256);
-            if (split)
-                for (w2 = 64; w2 < 256 && chunks(excess, w2) > layer; w2 += 64) {}
+            for (w2 = 64; w2 < 256 && chunks(excess, w2) > layer; w2 += 64) {}
         }
         if (w2 < 256) {
             add_round(256, whole * layer, false);
@@ -230,14 +220,6 @@ int plan_chunk_rounds(long total, int cu_count, int forced_wet_per_chunk, ChunkR
         // 72.4 with the layers; a half surface 64.8 vs 55.4).
         if (tail_plan && need > cap(AO_LAYER_1) + cap(AO_LAYER_2) && need <= cap(AO_LAYER_1) + cap(AO_LAYER_2) + cap(AO_LAYER_3))
             W1 = W2 = W3 = AO_LAYER_2;
-        if (const char* env = experiment_knob("COFLUX_LAYERS")) {  // experiments only (with COFLUX_EXPERIMENTS=1): "w1,w2,w3" (multiples of 64, w1 ≥ w2 ≥ w3, w1 ≤ AO_CHUNK)
-            int a = 0, b = 0, c = 0;
-            if (std::sscanf(env, "%d,%d,%d", &a, &b, &c) == 3 && a <= AO_CHUNK && a >= b && b >= c && c >= 64 && a % 64 == 0 && b % 64 == 0 && c % 64 == 0) {
-                W1 = a;
-                W2 = b;
-                W3 = c;
-            }
-        }
         const long body = need - cap(W2) - cap(W3);
         const long n1 = body > 0 ? (body + cap(W1) - 1) / cap(W1) * layer : 0;  // whole layers of the largest size
         add_round(W1, n1, false);
@@ -352,9 +334,9 @@ __device__ __forceinline__ void ice_zero_net(SolverArgsPtr K, const GridDesc& G,
 }
 
 // (a device routine: the kernel below, and ice_ocean_kernel, where the ocean solver's workgroups ride behind these)
-template <bool COARE, int SPEC, bool FUSE_NET, int BLOCK, bool TAIL = false>
+template <bool COARE, int SPEC, bool FUSE_NET, bool TAIL = false>
 __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int block) {
-    constexpr int CHUNK = Geom<BLOCK>::CHUNK;
+    constexpr int BLOCK = AO_BLOCK, CHUNK = Geom::CHUNK;
     SolverArgsPtr K = opaque(K_in);
     if constexpr (TAIL) {
         static_assert(BLOCK == 64 * IT_WAVES, "a tail workgroup is an interpolation workgroup");
@@ -411,10 +393,10 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* tab = reinterpret_cast<double*>(smem);
     unsigned* list = reinterpret_cast<unsigned*>(smem + TABLE_BYTES);
-    int* counters = reinterpret_cast<int*>(smem + Geom<BLOCK>::COUNTERS_OFFSET);  // [0] wet count, [1] cursor, [2] wet cells seen, [3] stale
+    int* counters = reinterpret_cast<int*>(smem + Geom::COUNTERS_OFFSET);  // [0] wet count, [1] cursor, [2] wet cells seen, [3] stale
     int* hist = counters + 4;
     int* bin_start = hist + AO_BINS;
-    DevParams* lp = reinterpret_cast<DevParams*>(smem + Geom<BLOCK>::PARAMS_OFFSET);
+    DevParams* lp = reinterpret_cast<DevParams*>(smem + Geom::PARAMS_OFFSET);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wx = G.nx + 2 * G.ring;
     const unsigned wx_rcp = (unsigned)K->wx_reciprocal;
@@ -431,10 +413,10 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
     //     but the chunk table.  One aligned 4-byte word per cell of a byte mask, the two halves of the double for a
     //     bottom-height mask — the same two load instructions either way, so no branch.
     static_assert(sizeof(DevParams) % 16 == 0 && sizeof(DevParams) <= 1024, "the parameter block is one LDS-DMA piece");
-    static_assert(Geom<BLOCK>::PARAMS_OFFSET % 16 == 0, "LDS-DMA destination alignment");
+    static_assert(Geom::PARAMS_OFFSET % 16 == 0, "LDS-DMA destination alignment");
     if (tid < (int)(sizeof(DevParams) / 16))
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(g_params) + lane * 16),
-                                         (__attribute__((address_space(3))) void*)(smem + Geom<BLOCK>::PARAMS_OFFSET), 16, 0, 0);
+                                         (__attribute__((address_space(3))) void*)(smem + Geom::PARAMS_OFFSET), 16, 0, 0);
     static_assert(TABLE_BYTES % 1024 == 0, "the table stage copies whole 1 KB pieces");
     {
         const char* gb = reinterpret_cast<const char*>(g_tab);
@@ -716,9 +698,7 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
                     c.alpha_g = alpha * P.inv_g;
                     Ts = S.top_temperature[k] + Ice.T_offset;
                     // CF_OPT_ICE_FREE_CELLS = zero: open water (ℵ = 0 and hᵢ = 0) has no atmosphere–sea-ice interface
-#ifndef CF_NO_ICE_FREE_OPTION  // (A/B builds: what the option's test costs the default mode — nothing measurable)
                     if (Ice.ice_free_zero != 0.0 && S.concentration) ice_free = S.concentration[k] == 0.0 && S.thickness[k] == 0.0;
-#endif
                 }
                 Scales s{0.0, 0.0, 0.0, 0, 0};
                 const bool solve = in_range && !ice_free;
@@ -826,9 +806,9 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
     }
 }
 
-template <bool COARE, int SPEC, bool FUSE_NET, int BLOCK, bool TAIL = false>
-__global__ __launch_bounds__(BLOCK, 3) void ao_flux_fast_kernel(SolverArgs unused_by_name) {
-    ao_flux_fast_body<COARE, SPEC, FUSE_NET, BLOCK, TAIL>((SolverArgsPtr)__builtin_amdgcn_kernarg_segment_ptr(), (int)blockIdx.x);
+template <bool COARE, int SPEC, bool FUSE_NET, bool TAIL = false>
+__global__ __launch_bounds__(AO_BLOCK, 3) void ao_flux_fast_kernel(SolverArgs unused_by_name) {
+    ao_flux_fast_body<COARE, SPEC, FUSE_NET, TAIL>((SolverArgsPtr)__builtin_amdgcn_kernarg_segment_ptr(), (int)blockIdx.x);
 }
 
 // Config 3 in ONE solver launch: the workgroups of the atmosphere–sea-ice interface solve (the long ones: ≈ 30 iterations per
@@ -871,7 +851,7 @@ __global__ __launch_bounds__(AO_BLOCK, 3) void ice_ocean_kernel(IceOceanArgs unu
         return;
     }
     block = kind == 2 ? nch + idx : idx;  // the interpolation's workgroups: numbered as in ao_flux_fast_kernel's tail
-    ao_flux_fast_body<COARE_ICE, ICE_SPEC, false, AO_BLOCK, true>((SolverArgsPtr)&K->A, block);
+    ao_flux_fast_body<COARE_ICE, ICE_SPEC, false, true>((SolverArgsPtr)&K->A, block);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -917,7 +897,7 @@ static void launch_ao_spec(hipStream_t st, dim3 grid, const LaunchCfg& L, const 
                        L.d_chunk_begins, I, N, IceStateIn{}, IceParams{},
                        z_surface, mask_kind, T_offset, row_reciprocal(G.nx + 2 * G.ring)};
 #define CF_LAUNCH(COARE_, SPEC_) \
-    hipLaunchKernelGGL((ao_flux_fast_kernel<COARE_, SPEC_, FUSE, AO_BLOCK>), grid, dim3(AO_BLOCK), Geom<AO_BLOCK>::LDS_BYTES, st, A)
+    hipLaunchKernelGGL((ao_flux_fast_kernel<COARE_, SPEC_, FUSE>), grid, dim3(AO_BLOCK), Geom::LDS_BYTES, st, A)
     // (SOLVER_OCEAN_LEAN never arrives here: launch_ao_fluxes hands it to coflux_solver_lean.hip)
     switch (C.specialization) {
         case SOLVER_ICE: CF_LAUNCH(COARE, SOLVER_ICE); break;
@@ -936,12 +916,9 @@ hipError_t launch_ly_fluxes_with_tail(hipStream_t st, const LaunchCfg& L, const 
     if (!L.d_chunk_begins || L.n_chunks <= 0 || !net || !next_src || !w || !next_out || L.interp_cap <= 0 || tail_blocks <= 0 ||
         C.specialization != SOLVER_LY)
         return hipErrorInvalidValue;
-    if ((size_t)IT_WAVES * CF_JRA55_NVARS * L.interp_cap * sizeof(double) > (size_t)Geom<AO_BLOCK>::LDS_BYTES) return hipErrorInvalidValue;
-    IceIn I{};
-    if (ice) I = IceIn{ice->concentration, ice->interface_heat, ice->salt_flux, ice->x_stress, ice->y_stress, nullptr};
-    I.land = land;
-    const NetOut N{net->u, net->v, net->T, net->S, net->shortwave_surface_flux, net->upwelling_longwave, net->downwelling_longwave,
-                   net->downwelling_shortwave};
+    if ((size_t)IT_WAVES * CF_JRA55_NVARS * L.interp_cap * sizeof(double) > (size_t)Geom::LDS_BYTES) return hipErrorInvalidValue;
+    const IceIn I = make_ice_in(ice, land);
+    const NetOut N = make_net_out(net);
     SolverArgs A{C, G, make_ocean(o), make_exchange(e), make_fluxes(f), L.d_tables, L.d_params, WetLists{L.d_wet_pos, nullptr},
                  L.d_chunk_begins, I, N, IceStateIn{}, IceParams{}, P.z_surface, P.mask_kind, P.T_offset, row_reciprocal(G.nx + 2 * G.ring)};
     A.Si = make_source(next_src);
@@ -951,8 +928,8 @@ hipError_t launch_ly_fluxes_with_tail(hipStream_t st, const LaunchCfg& L, const 
     A.tail_blocks = tail_blocks;
     A.tail_rows = tail_rows;
     A.tail_cap = L.interp_cap;
-    hipLaunchKernelGGL((ao_flux_fast_kernel<true, SOLVER_LY, true, AO_BLOCK, true>), dim3(L.n_chunks + tail_blocks), dim3(AO_BLOCK),
-                       Geom<AO_BLOCK>::LDS_BYTES, st, A);
+    hipLaunchKernelGGL((ao_flux_fast_kernel<true, SOLVER_LY, true, true>), dim3(L.n_chunks + tail_blocks), dim3(AO_BLOCK),
+                       Geom::LDS_BYTES, st, A);
     return hipGetLastError();
 }
 
@@ -971,13 +948,8 @@ hipError_t launch_ao_fluxes(hipStream_t st, const LaunchCfg& L, const DevParams&
     OceanIn O = make_ocean(o);
     Exchange E = make_exchange(e);
     FluxOut F = make_fluxes(f);
-    IceIn I{};
-    if (ice) I = IceIn{ice->concentration, ice->interface_heat, ice->salt_flux, ice->x_stress, ice->y_stress, nullptr};
-    I.land = land;
-    NetOut N{};
-    if (net)
-        N = NetOut{net->u, net->v, net->T, net->S, net->shortwave_surface_flux, net->upwelling_longwave,
-                   net->downwelling_longwave, net->downwelling_shortwave};
+    const IceIn I = make_ice_in(ice, land);
+    const NetOut N = make_net_out(net);
     // one workgroup per chunk of the cost-balanced table: the hardware dispatcher is the dynamic load balancer
     if (!L.d_chunk_begins || L.n_chunks <= 0) return hipErrorInvalidValue;
     dim3 grid(L.n_chunks);
@@ -1028,7 +1000,7 @@ hipError_t launch_ai_fluxes(hipStream_t st, const LaunchCfg& L, const DevParams&
         A.n_chunks = L.n_chunks;
         if (tail->next_out) {
             if (!tail->next_src || !tail->w || L.interp_cap <= 0 || tail->interp_blocks <= 0 ||
-                (size_t)IT_WAVES * CF_JRA55_NVARS * L.interp_cap * sizeof(double) > (size_t)Geom<AO_BLOCK>::LDS_BYTES)
+                (size_t)IT_WAVES * CF_JRA55_NVARS * L.interp_cap * sizeof(double) > (size_t)Geom::LDS_BYTES)
                 return hipErrorInvalidValue;
             A.Si = make_source(tail->next_src);
             A.Wi = make_weights(tail->w);
@@ -1044,9 +1016,7 @@ hipError_t launch_ai_fluxes(hipStream_t st, const LaunchCfg& L, const DevParams&
             A.stress_mask = tail->stress_ocean->mask;
             A.rtx = tail->stress_fluxes->x_momentum;
             A.rty = tail->stress_fluxes->y_momentum;
-            if (tail->stress_ice)
-                A.stress_ice = IceIn{tail->stress_ice->concentration, tail->stress_ice->interface_heat, tail->stress_ice->salt_flux,
-                                     tail->stress_ice->x_stress, tail->stress_ice->y_stress, nullptr};
+            A.stress_ice = make_ice_in(tail->stress_ice, nullptr);
             A.tau_x = tail->stress_net->u;
             A.tau_y = tail->stress_net->v;
         }
@@ -1059,43 +1029,18 @@ hipError_t launch_ai_fluxes(hipStream_t st, const LaunchCfg& L, const DevParams&
             memcpy(&M.O, tail->ocean->args, sizeof(LeanArgs));
             M.ocean_chunks = tail->ocean->n_chunks;
             {
-                // (experiments: COFLUX_EXPERIMENTS=1 COFLUX_ICE_OCEAN_ORDER="I0:768,O0:768,T" — segments of interface / ocean chunks
-                // first:count and the interpolation, in dispatch order; scratch/ice_ocean_orders.sh)
-                static const char* order = experiment_knob("COFLUX_ICE_OCEAN_ORDER");
-                int n = 0;
-                if (order && order[0]) {
-                    const char* c = order;
-                    while (*c && n < 8) {
-                        const char k = *c++;
-                        if (k == 'T') {
-                            M.seg_kind[n] = 2; M.seg_first[n] = 0; M.seg_count[n] = (int)A.tail_blocks;
-                        } else {
-                            M.seg_kind[n] = k == 'O' ? 1 : 0;
-                            M.seg_first[n] = (int)strtol(c, (char**)&c, 10);
-                            if (*c == ':') ++c;
-                            M.seg_count[n] = (int)strtol(c, (char**)&c, 10);
-                            const int total = k == 'O' ? tail->ocean->n_chunks : L.n_chunks;  // (the knob speaks of 768 chunks: clamp)
-                            M.seg_first[n] = std::min(M.seg_first[n], total);
-                            M.seg_count[n] = std::min(M.seg_count[n], total - M.seg_first[n]);
-                        }
-                        ++n;
-                        if (*c == ',') ++c;
-                    }
-                } else {
-                    // the ocean solve's FIRST arrival layer (its largest chunks, one per CU) ahead of the interface solve's workgroups,
-                    // the rest behind them: the riders left for the end are the short ones (249.1 µs per step against 255.2 with every
-                    // ocean chunk behind; its smallest layer first 252.4; profiles/r04_experiments.md §17)
-                    const int noc_all = tail->ocean->n_chunks, head = std::min(std::max(L.cu_count, 0), noc_all);
-                    M.seg_kind[0] = 1; M.seg_first[0] = 0; M.seg_count[0] = head;
-                    M.seg_kind[1] = 0; M.seg_first[1] = 0; M.seg_count[1] = L.n_chunks;
-                    M.seg_kind[2] = 1; M.seg_first[2] = head; M.seg_count[2] = noc_all - head;
-                    M.seg_kind[3] = 2; M.seg_first[3] = 0; M.seg_count[3] = (int)A.tail_blocks;
-                    n = 4;
-                }
-                M.nseg = n;
+                // the ocean solve's FIRST arrival layer (its largest chunks, one per CU) ahead of the interface solve's workgroups,
+                // the rest behind them: the riders left for the end are the short ones (249.1 µs per step against 255.2 with every
+                // ocean chunk behind; its smallest layer first 252.4; profiles/r04_experiments.md §17)
+                const int noc_all = tail->ocean->n_chunks, head = std::min(std::max(L.cu_count, 0), noc_all);
+                M.seg_kind[0] = 1; M.seg_first[0] = 0; M.seg_count[0] = head;
+                M.seg_kind[1] = 0; M.seg_first[1] = 0; M.seg_count[1] = L.n_chunks;
+                M.seg_kind[2] = 1; M.seg_first[2] = head; M.seg_count[2] = noc_all - head;
+                M.seg_kind[3] = 2; M.seg_first[3] = 0; M.seg_count[3] = (int)A.tail_blocks;
+                M.nseg = 4;
             }
             const dim3 mgrid((unsigned)(L.n_chunks + tail->ocean->n_chunks + A.tail_blocks));
-            constexpr size_t lds = (size_t)(Geom<AO_BLOCK>::LDS_BYTES > LeanGeom<AO_BLOCK>::LDS_BYTES ? Geom<AO_BLOCK>::LDS_BYTES : LeanGeom<AO_BLOCK>::LDS_BYTES);
+            constexpr size_t lds = (size_t)(Geom::LDS_BYTES > LeanGeom<AO_BLOCK>::LDS_BYTES ? Geom::LDS_BYTES : LeanGeom<AO_BLOCK>::LDS_BYTES);
             static_assert(lds <= 53760, "three workgroups per CU");
 #define CF_IO_LAUNCH(SPEC_)                                                                                                   \
     do {                                                                                                                      \
@@ -1114,20 +1059,20 @@ hipError_t launch_ai_fluxes(hipStream_t st, const LaunchCfg& L, const DevParams&
         }
         const dim3 tgrid((unsigned)(L.n_chunks + A.tail_blocks + A.stress_blocks));
 #define CF_AI_TAIL_LAUNCH(COARE_, SPEC_) \
-    hipLaunchKernelGGL((ao_flux_fast_kernel<COARE_, SPEC_, false, AO_BLOCK, true>), tgrid, dim3(AO_BLOCK), Geom<AO_BLOCK>::LDS_BYTES, st, A)
+    hipLaunchKernelGGL((ao_flux_fast_kernel<COARE_, SPEC_, false, true>), tgrid, dim3(AO_BLOCK), Geom::LDS_BYTES, st, A)
         if (lin) { if (coare) CF_AI_TAIL_LAUNCH(true, SOLVER_SEAICE_LEAN_LIN); else CF_AI_TAIL_LAUNCH(false, SOLVER_SEAICE_LEAN_LIN); }
         else { if (coare) CF_AI_TAIL_LAUNCH(true, SOLVER_SEAICE_LEAN); else CF_AI_TAIL_LAUNCH(false, SOLVER_SEAICE_LEAN); }
 #undef CF_AI_TAIL_LAUNCH
         return hipGetLastError();
     }
-#define CF_AI_LAUNCH(COARE_, SPEC_, BLOCK_) \
-    hipLaunchKernelGGL((ao_flux_fast_kernel<COARE_, SPEC_, false, BLOCK_>), grid, dim3(BLOCK_), Geom<BLOCK_>::LDS_BYTES, st, A)
+#define CF_AI_LAUNCH(COARE_, SPEC_) \
+    hipLaunchKernelGGL((ao_flux_fast_kernel<COARE_, SPEC_, false>), grid, dim3(AO_BLOCK), Geom::LDS_BYTES, st, A)
     if (lin) {
-        if (lean) { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LEAN_LIN, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LEAN_LIN, AO_BLOCK); }
-        else { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LIN, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LIN, AO_BLOCK); }
+        if (lean) { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LEAN_LIN); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LEAN_LIN); }
+        else { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LIN); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LIN); }
     } else {
-        if (lean) { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LEAN, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LEAN, AO_BLOCK); }
-        else { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE, AO_BLOCK); else CF_AI_LAUNCH(false, SOLVER_SEAICE, AO_BLOCK); }
+        if (lean) { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE_LEAN); else CF_AI_LAUNCH(false, SOLVER_SEAICE_LEAN); }
+        else { if (coare) CF_AI_LAUNCH(true, SOLVER_SEAICE); else CF_AI_LAUNCH(false, SOLVER_SEAICE); }
     }
 #undef CF_AI_LAUNCH
     return hipGetLastError();

@@ -24,43 +24,20 @@
 //   * a batch's loads and stores are uniform base + 32-bit offset (gload / gstore): `global_* v_off, s[base]`.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdlib>
 #include <cstring>
-
-
-namespace coflux {
-
-// per-wave time stamps (scratch/phases_lean.py; -DCF_LEAN_STAMPS builds only): 0 entry, 1 everything requested, 2 my
-// requests have landed, 3 behind the barrier (batches begin), 4 batches done, 5 exit, 6 Σ cycles inside the iteration,
-// 7 batches taken
-#ifdef CF_LEAN_STAMPS
-__device__ unsigned long long g_lean_stamp[4096 * 8];
-#define LEAN_STAMP(q) do { if (lane == 0) g_lean_stamp[((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * 8 + (q)] = __builtin_readcyclecounter(); } while (0)
-#define LEAN_STAMP_SET(q, v) do { if (lane == 0) g_lean_stamp[((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * 8 + (q)] = (v); } while (0)
-extern "C" int cf_debug_phase_read(unsigned long long* out, int n) {
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lean_stamp), sizeof(unsigned long long) * n);
-    return 0;
-}
-#else
-#define LEAN_STAMP(q) do { } while (0)
-#define LEAN_STAMP_SET(q, v) do { } while (0)
-#endif
-}  // namespace coflux
 
 #include "coflux_lean_kernel.hpp"
 
 namespace coflux {
 
 template <bool COARE, bool FUSE, bool TAIL = false, bool CERT = false>
-__global__ __launch_bounds__(AO_BLOCK, CF_LEAN_WAVES) void ao_lean_kernel(LeanArgs unused_by_name) {
+__global__ __launch_bounds__(AO_BLOCK, LEAN_WAVES) void ao_lean_kernel(LeanArgs unused_by_name) {
     ao_lean_body<COARE, FUSE, TAIL, CERT>((LeanArgsPtr)__builtin_amdgcn_kernarg_segment_ptr(), (int)blockIdx.x);
 }
 
 // the stepping loop's exact-path launch with the step's peer-direct halo rows as rider workgroups (ao_lean_body, HALO)
 template <bool COARE>
-__global__ __launch_bounds__(AO_BLOCK, CF_LEAN_WAVES) void ao_lean_halo_kernel(LeanArgs unused_by_name) {
+__global__ __launch_bounds__(AO_BLOCK, LEAN_WAVES) void ao_lean_halo_kernel(LeanArgs unused_by_name) {
     ao_lean_body<COARE, true, true, false, false, true>((LeanArgsPtr)__builtin_amdgcn_kernarg_segment_ptr(), (int)blockIdx.x);
 }
 
@@ -154,18 +131,9 @@ static hipError_t fill_lean_args(const LaunchCfg& L, const DevParams& P, const L
     A.T_offset = P.T_offset;
     A.wx_reciprocal = row_reciprocal(G.nx + 2 * G.ring);
     A.sort_enabled = L.lean_hints;
-    if (L.lean_hints > 1) {
-        static const int windows = [] {  // (experiments: COFLUX_EXPERIMENTS=1 COFLUX_SORT_WINDOWS=1|2|4|8, read once)
-            const char* e = experiment_knob("COFLUX_SORT_WINDOWS");
-            return e ? std::max(1, std::min(8, std::atoi(e))) : 0;
-        }();
-        if (windows > 0) A.sort_enabled = windows;
-    }
     if (net) {  // the fused form: the epilogue also writes the cell-local net ocean fluxes (constant ocean albedo only)
-        if (ice) A.I = IceIn{ice->concentration, ice->interface_heat, ice->salt_flux, ice->x_stress, ice->y_stress, nullptr};
-        A.I.land = land;
-        A.N = NetOut{net->u, net->v, net->T, net->S, net->shortwave_surface_flux, net->upwelling_longwave, net->downwelling_longwave,
-                     net->downwelling_shortwave};
+        A.I = make_ice_in(ice, land);
+        A.N = make_net_out(net);
     }
     return hipSuccess;
 }
@@ -188,7 +156,7 @@ hipError_t launch_ao_fluxes_lean(hipStream_t st, const LaunchCfg& L, const DevPa
                                  const cf_ocean_surface* o, const cf_exchange_fields* e, const cf_interface_fluxes* f,
                                  const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* net, const double* land,
                                  const cf_atmos_source* next_src, const cf_interp_weights* w, const cf_exchange_fields* next_out,
-                                 int tail_rows, int tail_blocks, int tail_pos, const HaloRider* halo) {
+                                 int tail_rows, int tail_blocks, const HaloRider* halo) {
     LeanArgs A{};
     if (hipError_t err = fill_lean_args(L, P, C, G, o, e, f, ice, net, land, A)) return err;
     const bool coare = P.similarity_form == CF_SIMILARITY_COARE_LOGARITHMIC;
@@ -207,7 +175,7 @@ hipError_t launch_ao_fluxes_lean(hipStream_t st, const LaunchCfg& L, const DevPa
         A.tail_blocks = tail_blocks;
         A.tail_rows = tail_rows;
         A.tail_cap = L.interp_cap;
-        A.tail_pos = tail_pos < 0 || tail_pos > L.n_chunks ? L.n_chunks : tail_pos;
+        A.tail_pos = L.n_chunks;
         blocks += tail_blocks;
     }
     const bool riders = halo != nullptr && halo->blocks > 0;

@@ -13,10 +13,7 @@ namespace coflux {
 
 constexpr int TABLE_BYTES = TABLE_DOUBLES * 8;
 constexpr int AO_BLOCK = 256;
-#ifndef CF_AO_CHUNK
-#define CF_AO_CHUNK 1280
-#endif
-constexpr int AO_CHUNK = CF_AO_CHUNK;  // capacity of a narrow workgroup's wet-cell list = the most wet cells a chunk can hold
+constexpr int AO_CHUNK = 1280;  // capacity of a narrow workgroup's wet-cell list = the most wet cells a chunk can hold
 constexpr int AO_BINS = 64;    // trip-count bins of the per-chunk counting sort (one wave scans them)
 constexpr int AO_WET_COST = 64;
 

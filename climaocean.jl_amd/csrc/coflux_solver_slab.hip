@@ -21,8 +21,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#define LEAN_STAMP(q) do { } while (0)
-#define LEAN_STAMP_SET(q, v) do { } while (0)
 #include "coflux_lean_kernel.hpp"
 
 namespace coflux {

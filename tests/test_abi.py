@@ -42,8 +42,7 @@ def test_library_exports_no_undeclared_cf_symbol():
         name = line.split()[-1]
         if " T " in line and re.match(r"^cf_[a-z0-9_]+$", name):
             exported.add(name)
-    allowed = {"cf_debug_phase_read"}  # per-wave stamp reader of the instrumented scratch builds (absent from the product)
-    assert exported - _header_symbols() - allowed == set(), exported - _header_symbols() - allowed
+    assert exported - _header_symbols() == set(), exported - _header_symbols()
     listed = set(re.findall(r"`(cf_[a-z0-9_]+)`", open(os.path.join(ROOT, "INTEGRATION.md")).read()))
     types = set(re.findall(r"\b(cf_[a-z0-9_]+)\b(?=\s*[;{]|\s+\w+[;,)\[])", open(os.path.join(ROOT, "include", "coflux.h")).read()))
     functions = {n for n in listed if not n.endswith(("_params", "_fields", "_fluxes", "_surface", "_state", "_source", "_weights", "_schedule", "_ctx", "_grid", "_roughness"))}

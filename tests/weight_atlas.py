@@ -1,7 +1,7 @@
 """A designed atlas of interpolation weight maps, an exact reference and a NumPy model of the tiled kernel's footprint
 (test infrastructure of tests/test_weight_atlas.py; CPU only, nothing here imports the library).
 
-interpolate_atmosphere_state! exists in four hand-written copies on the device (interp_corners, interpolate_tiles<ROWS>,
+interpolate_atmosphere_state! exists in three hand-written copies on the device (interpolate_tiles<ROWS>,
 interpolate_gather_kernel, interpolate_land_kernel), the tiled one in three instantiations and four launches.  Geographic
 weight maps leave most of their index logic untouched: no latitude clamp, hardly a negative index, one fold.  The atlas
 holds maps that each FORCE one situation (a seam inside a staged tile, a tile that sees the whole circle, exact nodes, signed
