@@ -27,6 +27,12 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _is_field(t, ctx, dtype=torch.float64):
+    """A contiguous device array of the context's shape and of `dtype` (None: any): what every ocean-grid array handed to
+    the library is."""
+    return t.is_cuda and t.is_contiguous() and tuple(t.shape) == ctx.shape and dtype in (None, t.dtype)
+
+
 class FluxContext:
     """One libcoflux context bound to `device` (cuda:N)."""
 
@@ -492,32 +498,55 @@ TERM_KINDS = dict(field=abi.TERM_FIELD, product=abi.TERM_PRODUCT, center_x=abi.T
                   kinetic_energy=abi.TERM_KINETIC_ENERGY, east=abi.TERM_EAST, north=abi.TERM_NORTH)
 
 
-class TimeAverager:
+class _ChildHandle:
+    """What TimeAverager, SurfaceIntegrator, SurfaceRegridder and SnapshotWindow share: a handle `_h` made on the context
+    `ctx` that may outlive it (the library then fails every call but the `_destroy` one with "… has been destroyed")."""
+    _destroy = None   # name of the cf_*_destroy entry point
+
+    def _adopt(self, ctx):
+        self.ctx, self.lib, self._h = ctx, ctx.lib, C.c_void_p()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise CofluxError(f"{what} failed ({rc}): {self.lib.cf_last_error(None).decode()}")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(self.lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TimeAverager(_ChildHandle):
     """cf_average_*: after collections of weights w₁ … wₙ every `means[k]` holds Σ w f / Σ w of `sources[k]` on the interior
     (halos untouched), accumulated on the device in one launch per collection.  The library borrows the pointers: the tensors
     are kept alive here."""
+    _destroy = "cf_average_destroy"
 
     def __init__(self, ctx, sources, means):
-        self.ctx, self.lib = ctx, ctx.lib
+        self._adopt(ctx)
         self.sources, self.means = list(sources), list(means)
         if len(self.sources) != len(self.means):
             raise ValueError(f"{len(self.sources)} sources, {len(self.means)} means")
         for t in self.sources + self.means:
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == ctx.shape):
+            if not _is_field(t, ctx):
                 raise ValueError(f"averaged fields are contiguous float64 device arrays of shape {ctx.shape}")
         n = len(self.sources)
         src = (C.c_void_p * n)(*[t.data_ptr() for t in self.sources])
         dst = (C.c_void_p * n)(*[t.data_ptr() for t in self.means])
-        h = C.c_void_p()
-        ctx._check(self.lib.cf_average_create(ctx._h, n, src, dst, C.byref(h)), "cf_average_create")
-        self._h = h
+        ctx._check(self.lib.cf_average_create(ctx._h, n, src, dst, C.byref(self._h)), "cf_average_create")
 
     @classmethod
     def derived(cls, ctx, terms, cos_rotation=None, sin_rotation=None, max_workgroups=0):
         """cf_average_create_derived (FluxContext.derived_average): `sources` are the distinct input fields, rotation
         arrays included, `terms` the table as given."""
         self = cls.__new__(cls)
-        self.ctx, self.lib = ctx, ctx.lib
+        self._adopt(ctx)
         self.terms = [tuple(t) for t in terms]
         if len(self.terms) > abi.AVERAGE_MAX_FIELDS:
             raise ValueError(f"{len(self.terms)} terms (at most {abi.AVERAGE_MAX_FIELDS})")
@@ -527,7 +556,7 @@ class TimeAverager:
         def pointer(t, what):
             if t is None:
                 return None
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == ctx.shape):
+            if not _is_field(t, ctx):
                 raise ValueError(f"{what} is a contiguous float64 device array of shape {ctx.shape}")
             if what != "mean" and not any(t is s for s in self.sources):
                 self.sources.append(t)
@@ -540,14 +569,8 @@ class TimeAverager:
             self.means.append(mean)
         desc = abi.AverageDesc(C.sizeof(abi.AverageDesc), len(self.terms), table, pointer(cos_rotation, "cos_rotation"),
                                pointer(sin_rotation, "sin_rotation"), int(max_workgroups), 0)
-        h = C.c_void_p()
-        ctx._check(self.lib.cf_average_create_derived(ctx._h, C.byref(desc), C.byref(h)), "cf_average_create_derived")
-        self._h = h
+        ctx._check(self.lib.cf_average_create_derived(ctx._h, C.byref(desc), C.byref(self._h)), "cf_average_create_derived")
         return self
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise CofluxError(f"{what} failed ({rc}): {self.lib.cf_last_error(None).decode()}")
 
     def collect(self, weight):
         self._check(self.lib.cf_average_collect(self._h, float(weight)), "cf_average_collect")
@@ -561,28 +584,18 @@ class TimeAverager:
         self._check(self.lib.cf_average_weight(self._h, C.byref(total), C.byref(samples)), "cf_average_weight")
         return total.value, samples.value
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.cf_average_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 INTEGRAND_KINDS = dict(one=abi.INTEGRAND_ONE, field=abi.INTEGRAND_FIELD, product=abi.INTEGRAND_PRODUCT, above=abi.INTEGRAND_ABOVE)
 
 
-class SurfaceIntegrator:
+class SurfaceIntegrator(_ChildHandle):
     """cf_integrals_*: every collect(time) appends one record — entry e is Σ A·x over the wet interior cells that carry the
     entry's region bit — to a series kept on the device, in one pass over the interior; read() is the only host
     synchronisation.  The library borrows the pointers: the tensors are kept alive here."""
+    _destroy = "cf_integrals_destroy"
 
     def __init__(self, ctx, entries, area=None, mask=None, region=None, capacity=1024, max_workgroups=0):
-        self.ctx, self.lib = ctx, ctx.lib
+        self._adopt(ctx)
         self.n_entries, self.capacity = len(entries), int(capacity)
         if self.n_entries > abi.INTEGRALS_MAX_ENTRIES:
             raise ValueError(f"{self.n_entries} entries (at most {abi.INTEGRALS_MAX_ENTRIES})")
@@ -592,7 +605,7 @@ class SurfaceIntegrator:
         for name, t, dtype in (("area", area, torch.float64), ("mask", mask, None), ("region", region, torch.uint8)):
             if t is None:
                 continue
-            if not (t.is_cuda and t.is_contiguous() and tuple(t.shape) == ctx.shape and dtype in (None, t.dtype)):
+            if not _is_field(t, ctx, dtype):
                 raise ValueError(f"{name} is a contiguous device array of shape {ctx.shape}" + (f" and dtype {dtype}" if dtype else ""))
             setattr(desc, name, t.data_ptr())
         for e, entry in enumerate(entries):
@@ -603,17 +616,11 @@ class SurfaceIntegrator:
             for key, t in (("a", a), ("b", b)):
                 if t is None:
                     continue
-                if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == ctx.shape):
+                if not _is_field(t, ctx):
                     raise ValueError(f"entry {e}: {key} is a contiguous float64 device array of shape {ctx.shape}")
                 setattr(E, key, t.data_ptr())
                 self._keep.append(t)
-        h = C.c_void_p()
-        ctx._check(self.lib.cf_integrals_create(ctx._h, C.byref(desc), self.capacity, C.byref(h)), "cf_integrals_create")
-        self._h = h
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise CofluxError(f"{what} failed ({rc}): {self.lib.cf_last_error(None).decode()}")
+        ctx._check(self.lib.cf_integrals_create(ctx._h, C.byref(desc), self.capacity, C.byref(self._h)), "cf_integrals_create")
 
     def collect(self, time=0.0):
         self._check(self.lib.cf_integrals_collect(self._h, float(time)), "cf_integrals_collect")
@@ -634,34 +641,24 @@ class SurfaceIntegrator:
     def reset(self):
         self._check(self.lib.cf_integrals_reset(self._h), "cf_integrals_reset")
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.cf_integrals_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 REGRID_MODES = dict(mean=abi.REGRID_MEAN, sum=abi.REGRID_SUM)
 
 
-class SurfaceRegridder:
+class SurfaceRegridder(_ChildHandle):
     """cf_regrid_*: apply(sources) → one dense device tensor of n_rows doubles per source, dst[r] = Σ w x / Σ w over the wet
     entries of row r ("mean"; NaN where no entry is wet) or Σ w x ("sum"), and `coverage` = Σ w — one pass for all sources, no
     host synchronisation.  The operator is copied to the device at construction; the mask is borrowed and kept alive here."""
+    _destroy = "cf_regrid_destroy"
 
     def __init__(self, ctx, row_ptr, col, weight, mask=None, mode="mean", max_workgroups=0):
-        self.ctx, self.lib = ctx, ctx.lib
+        self._adopt(ctx)
         row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
         col = np.ascontiguousarray(col, dtype=np.int32)
         weight = np.ascontiguousarray(weight, dtype=np.float64)
         if row_ptr.ndim != 1 or row_ptr.size < 2 or col.ndim != 1 or col.shape != weight.shape:
             raise ValueError("regridder: row_ptr (n_rows + 1 entries, n_rows ≥ 1), col and weight (nnz entries each) are 1-D arrays")
-        if mask is not None and not (mask.is_cuda and mask.is_contiguous() and tuple(mask.shape) == ctx.shape):
+        if mask is not None and not _is_field(mask, ctx, None):
             raise ValueError(f"mask is a contiguous device array of shape {ctx.shape}")
         self.n_rows, self.nnz, self.mask = row_ptr.size - 1, col.size, mask
         self.mode = REGRID_MODES[mode] if isinstance(mode, str) else int(mode)
@@ -669,14 +666,8 @@ class SurfaceRegridder:
         desc.struct_size, desc.mode, desc.n_rows, desc.nnz = C.sizeof(abi.RegridDesc), self.mode, self.n_rows, self.nnz
         desc.row_ptr, desc.col, desc.weight = row_ptr.ctypes.data, col.ctypes.data, weight.ctypes.data
         desc.mask, desc.max_workgroups = (mask.data_ptr() if mask is not None else None), int(max_workgroups)
-        h = C.c_void_p()
-        ctx._check(self.lib.cf_regrid_create(ctx._h, C.byref(desc), C.byref(h)), "cf_regrid_create")
-        self._h = h
+        ctx._check(self.lib.cf_regrid_create(ctx._h, C.byref(desc), C.byref(self._h)), "cf_regrid_create")
         self.coverage = None
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise CofluxError(f"{what} failed ({rc}): {self.lib.cf_last_error(None).decode()}")
 
     def apply(self, sources, out=None, coverage=True):
         """Regrids `sources` (ocean-grid float64 device fields) into `out` (device tensors of at least n_rows doubles; new ones
@@ -684,7 +675,7 @@ class SurfaceRegridder:
         a tensor: written there)."""
         sources = list(sources)
         for t in sources:
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == self.ctx.shape):
+            if not _is_field(t, self.ctx):
                 raise ValueError(f"regridded fields are contiguous float64 device arrays of shape {self.ctx.shape}")
         n = len(sources)
         if out is None:
@@ -705,34 +696,17 @@ class SurfaceRegridder:
         self.coverage = coverage
         return out
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.cf_regrid_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SnapshotWindow:
+class SnapshotWindow(_ChildHandle):
     """JRA55PrescribedAtmosphere(arch; time_indices_in_memory = n_slots, prefetch = true): cf_window_* —
     `n_slots` snapshots of the nine JRA55 variables in HBM, refilled asynchronously from pinned staging
     buffers on a copy stream (atmosphere.jl:20-29).  Snapshot t lives in slot t mod n_slots."""
+    _destroy = "cf_window_destroy"
 
     def __init__(self, ctx, ns_x, ns_y, n_slots):
-        self.ctx, self.lib = ctx, ctx.lib
+        self._adopt(ctx)
         self.ns_x, self.ns_y, self.n_slots = ns_x, ns_y, n_slots
-        h = C.c_void_p()
-        ctx._check(self.lib.cf_window_create(ctx._h, ns_x, ns_y, n_slots, C.byref(h)), "cf_window_create")
-        self._h = h
-
-    def close(self):
-        if self._h:
-            self.lib.cf_window_destroy(self._h)
-            self._h = None
+        ctx._check(self.lib.cf_window_create(ctx._h, ns_x, ns_y, n_slots, C.byref(self._h)), "cf_window_create")
 
     def host_view(self, slot, variable):
         """NumPy view (ns_y, ns_x) float32 of the pinned staging buffer of (slot, variable)."""
@@ -743,10 +717,10 @@ class SnapshotWindow:
         return np.ctypeslib.as_array(p, shape=(self.ns_y, self.ns_x))
 
     def wait_slot(self, slot):
-        self.ctx._check(self.lib.cf_window_wait_slot(self._h, slot), "cf_window_wait_slot")
+        self._check(self.lib.cf_window_wait_slot(self._h, slot), "cf_window_wait_slot")
 
     def commit(self, slot, time_index):
-        self.ctx._check(self.lib.cf_window_commit(self._h, slot, time_index), "cf_window_commit")
+        self._check(self.lib.cf_window_commit(self._h, slot, time_index), "cf_window_commit")
 
     def upload(self, time_index, snapshot):
         """snapshot: dict variable -> float32 (ns_y, ns_x) host array."""
@@ -754,14 +728,14 @@ class SnapshotWindow:
         for a in keep:
             assert a.shape == (self.ns_y, self.ns_x), a.shape
         ptrs = (C.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
-        self.ctx._check(self.lib.cf_window_upload(self._h, time_index, ptrs), "cf_window_upload")
+        self._check(self.lib.cf_window_upload(self._h, time_index, ptrs), "cf_window_upload")
 
     def find(self, time_index):
         return self.lib.cf_window_find(self._h, time_index)
 
     def source(self, n1, n2, time_fraction):
         s = abi.AtmosSource()
-        self.ctx._check(self.lib.cf_window_source(self._h, n1, n2, float(time_fraction), C.byref(s)), "cf_window_source")
+        self._check(self.lib.cf_window_source(self._h, n1, n2, float(time_fraction), C.byref(s)), "cf_window_source")
         return s
 
 

@@ -222,37 +222,31 @@ static int ensure_chunk_table(cf_ctx* ctx, const void* mask) {
         ctx->chunk_z_surface == d.z_surface)
         return CF_OK;
     const int ncells = (ctx->grid.nx + 2 * ctx->grid.ring) * (ctx->grid.ny + 2 * ctx->grid.ring);
-    if (!ctx->d_chunk_sums) {
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_chunk_sums, sizeof(int) * chunk_sums_capacity(ncells)));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_chunk_begins, sizeof(int) * chunk_table_capacity(ncells)));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_chunk_meta, sizeof(int) * 4));
-    }
+    if (!ctx->d_chunk_sums) HIP_TRY(ctx, ctx->d_chunk_sums.create(sizeof(int) * chunk_sums_capacity(ncells)));
+    if (!ctx->d_chunk_begins) HIP_TRY(ctx, ctx->d_chunk_begins.create(sizeof(int) * chunk_table_capacity(ncells)));
+    if (!ctx->d_chunk_meta) HIP_TRY(ctx, ctx->d_chunk_meta.create(sizeof(int) * 4));
+    int *const d_chunk_begins = ctx->d_chunk_begins.get(), *const d_chunk_meta = ctx->d_chunk_meta.get();
     int wet = 0, n = 0;
     // (a context whose steps carry tail workgroups gets the plan made for them)
     // (not with a sea-ice formulation: there the riders sit in the interface solve's tail, and both solves do best on the
     // arrival layers — measured 293 vs 283 µs per step)
     const int plan = (ctx->launch.ao_chunk == 0 && ctx->merged_prefetch == 2 && !ctx->ice_ready) ? AO_PLAN_TAIL : ctx->launch.ao_chunk;
-    HIP_TRY(ctx, build_chunk_table(ctx->stream, ctx->d_params, ctx->grid, mask, ctx->launch.cu_count, plan,
-                                   ctx->d_chunk_sums, ctx->d_chunk_begins, ctx->d_chunk_meta, &wet, &n));
+    HIP_TRY(ctx, build_chunk_table(ctx->stream, ctx->d_params.get(), ctx->grid, mask, ctx->launch.cu_count, plan,
+                                   ctx->d_chunk_sums.get(), d_chunk_begins, d_chunk_meta, &wet, &n));
     {   // the lists' storage: n chunks at the geometry's fixed stride (grown when a rebuild needs more)
         const size_t want = std::max(wet_list_capacity(ncells), (size_t)(n + 1) * wet_list_stride());
-        if (want > ctx->wet_list_entries) {
+        if (want > ctx->wet.entries) {
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(ctx->d_wet_pos);
-            (void)hipFree(ctx->d_trip);
-            (void)hipFree(ctx->d_trip_ice);
-            (void)hipFree(ctx->d_lean_sorted);
-            (void)hipFree(ctx->d_lean_info);
-            ctx->d_wet_pos = ctx->d_lean_sorted = nullptr;
-            ctx->d_lean_info = nullptr;
-            ctx->d_trip = ctx->d_trip_ice = nullptr;
-            ctx->wet_list_entries = 0;
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_wet_pos, sizeof(uint32_t) * want));
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_lean_sorted, sizeof(uint32_t) * want));
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_lean_info, sizeof(int) * 4 * (size_t)chunk_table_capacity(ncells)));
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_trip, want));
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_trip_ice, want));
-            ctx->wet_list_entries = want;
+            ctx->wet = cf_ctx::WetLists{};   // the old lists go first: the new ones may need their room
+            ctx->chunk_valid = false;        // (the launch views name them: nothing launches before a rebuild has completed)
+            cf_ctx::WetLists lists;
+            HIP_TRY(ctx, lists.d_wet_pos.create(sizeof(uint32_t) * want));
+            HIP_TRY(ctx, lists.d_lean_sorted.create(sizeof(uint32_t) * want));
+            HIP_TRY(ctx, lists.d_lean_info.create(sizeof(int) * 4 * (size_t)chunk_table_capacity(ncells)));
+            HIP_TRY(ctx, lists.d_trip.create(want));
+            HIP_TRY(ctx, lists.d_trip_ice.create(want));
+            lists.entries = want;
+            ctx->wet = std::move(lists);
         }
     }
     if (n <= 0 || n + 1 > chunk_table_capacity(ncells)) return fail(ctx, CF_ERR_HIP, "chunk table of %d entries is invalid", n);
@@ -261,12 +255,12 @@ static int ensure_chunk_table(cf_ctx* ctx, const void* mask) {
     ctx->chunk_z_surface = d.z_surface;
     ctx->chunk_wet = wet;
     ctx->chunk_valid = true;
-    ctx->launch.d_chunk_begins = ctx->d_chunk_begins;
+    ctx->launch.d_chunk_begins = d_chunk_begins;
     ctx->launch.n_chunks = n;
     {   // which chunks hold cells that read halo rows of the ocean state (HaloRider): the ring rows south of the interior read
         // rows j < 0; the last interior row and the ring rows north of it read row j + 1 ≥ ny (ℑy v)
         std::vector<int> begins((size_t)n + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(begins.data(), ctx->d_chunk_begins, sizeof(int) * begins.size(), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(begins.data(), d_chunk_begins, sizeof(int) * begins.size(), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         const long wx = ctx->grid.nx + 2 * ctx->grid.ring, south_cells = (long)ctx->grid.ring * wx,
                    north_from = (long)(ctx->grid.ny - 1 + ctx->grid.ring) * wx;
@@ -277,17 +271,18 @@ static int ensure_chunk_table(cf_ctx* ctx, const void* mask) {
         ctx->launch.chunk_north = cn;
     }
     int overflow = 0;
-    HIP_TRY(ctx, build_wet_lists(ctx->stream, ctx->d_params, ctx->grid, mask, n, ctx->d_chunk_begins, ctx->d_wet_pos,
-                                 ctx->d_trip, ctx->d_chunk_meta, &overflow));
-    ctx->launch.d_wet_pos = overflow ? nullptr : ctx->d_wet_pos;
+    const cf_ctx::WetLists& W = ctx->wet;
+    HIP_TRY(ctx, build_wet_lists(ctx->stream, ctx->d_params.get(), ctx->grid, mask, n, d_chunk_begins, W.d_wet_pos.get(),
+                                 W.d_trip.get(), d_chunk_meta, &overflow));
+    ctx->launch.d_wet_pos = overflow ? nullptr : W.d_wet_pos.get();
     // the lean ocean kernel's lists: the static lists in index order until the first call has run
     ctx->launch.d_lean_sorted = nullptr;
     ctx->launch.d_lean_info = nullptr;
-    if (!overflow) HIP_TRY(ctx, build_lean_lists(ctx->stream, n, ctx->d_wet_pos, ctx->d_chunk_begins, ctx->d_lean_sorted, ctx->d_lean_info));
-    ctx->launch.d_lean_sorted = ctx->d_lean_sorted;
-    ctx->launch.d_lean_info = ctx->d_lean_info;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_trip_ice, 0, (size_t)n * wet_list_stride(), ctx->stream));
-    ctx->launch.d_trip = ctx->trip_hints ? ctx->d_trip : nullptr;
+    if (!overflow) HIP_TRY(ctx, build_lean_lists(ctx->stream, n, W.d_wet_pos.get(), d_chunk_begins, W.d_lean_sorted.get(), W.d_lean_info.get()));
+    ctx->launch.d_lean_sorted = W.d_lean_sorted.get();
+    ctx->launch.d_lean_info = W.d_lean_info.get();
+    HIP_TRY(ctx, hipMemsetAsync(W.d_trip_ice.get(), 0, (size_t)n * wet_list_stride(), ctx->stream));
+    ctx->launch.d_trip = ctx->trip_hints ? W.d_trip.get() : nullptr;
     if (std::getenv("COFLUX_DEBUG"))
         std::fprintf(stderr, "[coflux] chunk table: %d chunks of %d wet cells (%d CUs)\n", n, wet, ctx->launch.cu_count);
     return CF_OK;
@@ -300,23 +295,41 @@ static int install_params(cf_ctx* ctx, const cf_flux_params* params) {
     if (ctx->tables_kind != d.stability) {
         std::vector<double> t = build_solver_tables(d.stability);
         if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, CF_ERR_HIP, "hipSetDevice(%d) failed", ctx->device);
-        if (!ctx->d_tables && hipMalloc((void**)&ctx->d_tables, sizeof(double) * TABLE_DOUBLES) != hipSuccess)
+        if (!ctx->d_tables && ctx->d_tables.create(sizeof(double) * TABLE_DOUBLES) != hipSuccess)
             return fail(ctx, CF_ERR_HIP, "hipMalloc of the solver tables failed");
-        if (hipMemcpy(ctx->d_tables, t.data(), sizeof(double) * TABLE_DOUBLES, hipMemcpyHostToDevice) != hipSuccess)
+        if (hipMemcpy(ctx->d_tables.get(), t.data(), sizeof(double) * TABLE_DOUBLES, hipMemcpyHostToDevice) != hipSuccess)
             return fail(ctx, CF_ERR_HIP, "upload of the solver tables failed");
         ctx->tables_kind = d.stability;
-        ctx->launch.d_tables = ctx->d_tables;
+        ctx->launch.d_tables = ctx->d_tables.get();
     }
     ctx->params = *params;
     ctx->dev = d;
     ctx->fast = loop_params(*params, d);
     ctx->fast.cert_budget = ctx->certified_budget / CERT_SAFETY;
-    if (!ctx->d_params && hipMalloc((void**)&ctx->d_params, sizeof(DevParams)) != hipSuccess)
+    if (!ctx->d_params && ctx->d_params.create(sizeof(DevParams)) != hipSuccess)
         return fail(ctx, CF_ERR_HIP, "hipMalloc of the device parameter block failed");
-    if (hipMemcpy(ctx->d_params, &d, sizeof(DevParams), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(ctx->d_params.get(), &d, sizeof(DevParams), hipMemcpyHostToDevice) != hipSuccess)
         return fail(ctx, CF_ERR_HIP, "upload of the device parameter block failed");
-    ctx->launch.d_params = ctx->d_params;
+    ctx->launch.d_params = ctx->d_params.get();
     ctx->chunk_valid = false;
+    return CF_OK;
+}
+
+// `launches` launches between two events on the context's stream, behind one untimed launch (code load)
+template <class Launch>
+static int time_launches(cf_ctx* ctx, int launches, double* ms_per_launch, Launch launch) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    cf::Event t0, t1;
+    HIP_TRY(ctx, t0.create(hipEventDefault));
+    HIP_TRY(ctx, t1.create(hipEventDefault));
+    CHECK(launch());
+    HIP_TRY(ctx, hipEventRecord(t0.get(), ctx->stream));
+    for (int n = 0; n < launches; ++n) CHECK(launch());
+    HIP_TRY(ctx, hipEventRecord(t1.get(), ctx->stream));
+    HIP_TRY(ctx, hipEventSynchronize(t1.get()));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, t0.get(), t1.get()));
+    *ms_per_launch = (double)ms / launches;
     return CF_OK;
 }
 
@@ -442,7 +455,7 @@ int cf_create(cf_ctx** out, int device, const cf_grid* grid, const cf_flux_param
     cf_ctx* ctx = new cf_ctx();   // (every validation of the grid is above: nothing below returns without deleting it)
     ctx->device = device;
     ctx->grid = GridDesc{grid->nx, grid->ny, grid->hx, grid->hy, grid->ring, grid->nx + 2 * grid->hx};
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || ctx->own_stream.create() != hipSuccess) {
         delete ctx;
         return fail(nullptr, CF_ERR_HIP, "cannot create a stream on device %d", device);
     }
@@ -462,59 +475,20 @@ int cf_create(cf_ctx** out, int device, const cf_grid* grid, const cf_flux_param
         ctx->launch.cu_count = prop.multiProcessorCount;
         ctx->launch.latency_layout = 1;  // CF_OPT_LATENCY_LAYOUT: automatic
     }
-    ctx->stream = ctx->own_stream;
+    ctx->stream = ctx->own_stream.get();
     *out = ctx;
     return CF_OK;
 }
 
 int cf_destroy(cf_ctx* ctx) {
     if (!ctx) return CF_OK;
-    average_forget_context(ctx);
-    integrals_forget_context(ctx);
-    regrid_forget_context(ctx);
+    (void)hipSetDevice(ctx->device);
+    orphan_children(ctx);
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
-    for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
-    if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-    if (ctx->comm_stream) {
-        (void)hipStreamSynchronize(ctx->comm_stream);
-        (void)hipStreamDestroy(ctx->comm_stream);
-        (void)hipEventDestroy(ctx->ev_main_idle);
-        (void)hipEventDestroy(ctx->ev_comm_done);
-    }
-    if (ctx->aux_stream) {
-        (void)hipStreamSynchronize(ctx->aux_stream);
-        (void)hipStreamDestroy(ctx->aux_stream);
-        (void)hipEventDestroy(ctx->ev_aux_gate);
-        for (auto& p : ctx->prefetch)
-            if (p.done) (void)hipEventDestroy(p.done);
-    }
-    if (ctx->peer_south_mapped) (void)hipIpcCloseMemHandle(ctx->peer.south);
-    if (ctx->peer_north_mapped) (void)hipIpcCloseMemHandle(ctx->peer.north);
-    if (ctx->peer.mine) {
-        cf_peer_forget_local(ctx->peer.mine);
-        (void)hipFree(ctx->peer.mine);
-    }
-    if (ctx->d_peer_status) (void)hipFree(ctx->d_peer_status);
-    if (ctx->d_halo_counters) (void)hipFree(ctx->d_halo_counters);
-    if (ctx->d_trip) (void)hipFree(ctx->d_trip);
-    if (ctx->d_trip_ice) (void)hipFree(ctx->d_trip_ice);
-    if (ctx->d_wet_pos) (void)hipFree(ctx->d_wet_pos);
-    if (ctx->d_lean_sorted) (void)hipFree(ctx->d_lean_sorted);
-    if (ctx->d_lean_info) (void)hipFree(ctx->d_lean_info);
-    if (ctx->d_chunk_sums) (void)hipFree(ctx->d_chunk_sums);
-    if (ctx->d_chunk_begins) (void)hipFree(ctx->d_chunk_begins);
-    if (ctx->d_chunk_meta) (void)hipFree(ctx->d_chunk_meta);
-    if (ctx->d_ice_albedo) (void)hipFree(ctx->d_ice_albedo);
-    if (ctx->d_ice_tables) (void)hipFree(ctx->d_ice_tables);
-    if (ctx->d_ice_params) (void)hipFree(ctx->d_ice_params);
-    if (ctx->d_reduce) (void)hipFree(ctx->d_reduce);
-    if (ctx->d_params) (void)hipFree(ctx->d_params);
-    if (ctx->own_stream) {
-        hipSetDevice(ctx->device);
-        hipStreamSynchronize(ctx->own_stream);
-        hipStreamDestroy(ctx->own_stream);
-    }
-    delete ctx;
+    for (hipStream_t s : {ctx->comm_lane.stream.get(), ctx->aux.stream.get(), ctx->own_stream.get()})
+        if (s) (void)hipStreamSynchronize(s);
+    if (ctx->peer_mine) cf_peer_forget_local(ctx->peer_mine.get());
+    delete ctx;   // every member releases itself (coflux_owned.hpp)
     return CF_OK;
 }
 
@@ -548,7 +522,7 @@ int cf_set_option(cf_ctx* ctx, int option, int value) {
             if (ctx->launch.lean_hints != (value == 1 ? 1 : (value == 3 ? 4 : 0))) ctx->chunk_valid = false;  // another window layout: start from index order
             ctx->trip_hints = value != 0;
             ctx->lean_hints = value == 1 || value == 3;
-            ctx->launch.d_trip = ctx->trip_hints ? ctx->d_trip : nullptr;
+            ctx->launch.d_trip = ctx->trip_hints ? ctx->wet.d_trip.get() : nullptr;
             ctx->launch.lean_hints = value == 1 ? 1 : (value == 3 ? 4 : 0);
             return CF_OK;
         case CF_OPT_FUSED_NET:
@@ -578,8 +552,10 @@ int cf_set_option(cf_ctx* ctx, int option, int value) {
             if (value < 0 || value > 1) return fail(ctx, CF_ERR_INVALID, "halo rows in the solver launch %d: 0 (the exchange kernel of its own) or 1", value);
             if (value && !ctx->d_halo_counters) {
                 HIP_TRY(ctx, hipSetDevice(ctx->device));
-                HIP_TRY(ctx, hipMalloc((void**)&ctx->d_halo_counters, 4 * sizeof(unsigned long long)));
-                HIP_TRY(ctx, hipMemset(ctx->d_halo_counters, 0, 4 * sizeof(unsigned long long)));
+                cf::DeviceBuffer<unsigned long long> counters;
+                HIP_TRY(ctx, counters.create(4 * sizeof(unsigned long long)));
+                HIP_TRY(ctx, hipMemset(counters.get(), 0, 4 * sizeof(unsigned long long)));
+                ctx->d_halo_counters = std::move(counters);
             }
             ctx->halo_in_launch = value;
             return CF_OK;
@@ -614,7 +590,7 @@ int cf_debug_eval(cf_ctx* ctx, int function, int n, const double* d_x, double* d
 int cf_set_stream(cf_ctx* ctx, void* hip_stream) {
     if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
     hipStream_t next = hip_stream == CF_STREAM_LEGACY ? nullptr  // the null stream handle: legacy default-stream semantics in every HIP call
-                       : (hip_stream ? (hipStream_t)hip_stream : ctx->own_stream);
+                       : (hip_stream ? (hipStream_t)hip_stream : ctx->own_stream.get());
     if (next != ctx->stream) {
         // a requested-ahead atmosphere state that was launched ON the old stream is consumed by stream order alone (no event):
         // the new stream has to wait for it
@@ -622,11 +598,10 @@ int cf_set_stream(cf_ctx* ctx, void* hip_stream) {
         for (auto& p : ctx->prefetch) pending |= p.valid && p.on_main;
         if (pending) {
             HIP_TRY(ctx, hipSetDevice(ctx->device));
-            hipEvent_t ev = nullptr;
-            HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            HIP_TRY(ctx, hipEventRecord(ev, ctx->stream));
-            HIP_TRY(ctx, hipStreamWaitEvent(next, ev, 0));
-            HIP_TRY(ctx, hipEventDestroy(ev));
+            cf::Event ev;
+            HIP_TRY(ctx, ev.create(hipEventDisableTiming));
+            HIP_TRY(ctx, hipEventRecord(ev.get(), ctx->stream));
+            HIP_TRY(ctx, hipStreamWaitEvent(next, ev.get(), 0));
         }
     }
     ctx->stream = next;
@@ -639,14 +614,14 @@ int cf_sync(cf_ctx* ctx) {
     if (int rc = wait_for_halos(ctx)) return rc;
     CHECK(cf_flush_deferred_prefetch(ctx));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->aux_stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream));
+    if (ctx->aux.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux.stream.get()));
     if (ctx->d_peer_status && ctx->peer_seq) {  // a peer-direct exchange whose neighbour never arrived
         int st = 0;
-        HIP_TRY(ctx, hipMemcpy(&st, ctx->d_peer_status, sizeof st, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(&st, ctx->d_peer_status.get(), sizeof st, hipMemcpyDeviceToHost));
         if (st) {
             // reported ONCE: the caller may fall back to another exchange (bench.py does) and go on with this context — the
             // mailbox protocol's sequence numbers only grow, a late arrival of the missed step disturbs nothing
-            HIP_TRY(ctx, hipMemset(ctx->d_peer_status, 0, sizeof st));
+            HIP_TRY(ctx, hipMemset(ctx->d_peer_status.get(), 0, sizeof st));
             return fail(ctx, CF_ERR_COMM, "peer-direct halo exchange timed out waiting for the %s neighbour's rows",
                         st == 1 ? "south" : "north");
         }
@@ -729,7 +704,7 @@ static int check_net(cf_ctx* ctx, const cf_net_ocean_fluxes* n, const cf_interp_
 // Ocean-reading kernels must see the halo rows of a preceding cf_halo_exchange_rows.
 static int wait_for_halos(cf_ctx* ctx) {
     if (ctx->comm_pending) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_comm_done, 0));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->comm_lane.ev_comm_done.get(), 0));
         ctx->comm_pending = false;
     }
     return CF_OK;
@@ -757,9 +732,9 @@ int cf_debug_chunk_table(cf_ctx* ctx, int* begins, int* wet_counts, int capacity
         return fail(ctx, CF_ERR_INVALID, "cf_debug_chunk_table: %d ints are too few for %d chunks", capacity, n);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<int> info((size_t)4 * n, 0);
-    HIP_TRY(ctx, hipMemcpyAsync(begins, ctx->d_chunk_begins, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->d_lean_info)
-        HIP_TRY(ctx, hipMemcpyAsync(info.data(), ctx->d_lean_info, sizeof(int) * info.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(begins, ctx->d_chunk_begins.get(), sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->wet.d_lean_info)
+        HIP_TRY(ctx, hipMemcpyAsync(info.data(), ctx->wet.d_lean_info.get(), sizeof(int) * info.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int c = 0; c < n; ++c) wet_counts[c] = info[(size_t)4 * c];
     return CF_OK;
@@ -892,8 +867,8 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     // solver to the interpolation's tile geometry and LDS footprint; measured slower, see DESIGN.md.)
     CHECK(ensure_chunk_table(ctx, ocean->mask));
     const bool rec = ctx->prof_count < ctx->prof_capacity;
-    hipEvent_t* ev = rec ? &ctx->prof_events[4 * (size_t)ctx->prof_count] : nullptr;
-    if (rec) HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
+    const cf::Event* ev = rec ? &ctx->prof_events[4 * (size_t)ctx->prof_count] : nullptr;
+    if (rec) HIP_TRY(ctx, hipEventRecord(ev[0].get(), ctx->stream));
     // a prefetched atmosphere state (cf_prefetch_atmosphere_state) for exactly this step and this set of exchange
     // fields is already on its way on the auxiliary stream: wait for it instead of interpolating again
     bool prefetched = false;
@@ -909,7 +884,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     // kernel follows — bitwise the same numbers as the three-launch sequence (shared arithmetic, contraction off).
     const bool fuse = net_fluxes_fused(ctx);
     if (!prefetched) HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, src, w, atmos));
-    if (rec) HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
+    if (rec) HIP_TRY(ctx, hipEventRecord(ev[1].get(), ctx->stream));
     CHECK(wait_for_halos(ctx));  // the interpolation above overlapped the halo rows
     // CF_OPT_MERGED_PREFETCH = 2: a requested next-step interpolation becomes the TAIL workgroups of this solver launch
     const bool tail_lean = ctx->launch.d_lean_info && ctx->fast.specialization == SOLVER_OCEAN_LEAN && ctx->launch.solver == CF_SOLVER_TABLES;
@@ -929,7 +904,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
             HaloRider& H = halo_rider;
             H.M = ctx->peer;
             H.F = ctx->halo_request.F;
-            H.counters = ctx->d_halo_counters;
+            H.counters = ctx->d_halo_counters.get();
             H.seq = ++ctx->peer_seq;
             ++ctx->halo_in_launch_count;
             for (int dir = 0; dir < 2; ++dir)
@@ -941,7 +916,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
                 H.expect_sent[dir] = ctx->halo_expect_sent[dir];
                 H.expect_done[dir] = ctx->halo_expect_done[dir];
             }
-            H.status = ctx->d_peer_status;
+            H.status = ctx->d_peer_status.get();
             H.rows = ctx->halo_request.rows;
             H.blocks = 2 * H.F.n;
             H.chunk_south = ctx->launch.chunk_south;
@@ -976,7 +951,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     const bool merge = fuse && !hold_tail_work && ctx->merged_prefetch == 1 && ctx->deferred.valid && interp_tile_fits(ctx, 65536) &&
                        ctx->deferred.out.u != atmos->u;
     if (ctx->merged_prefetch == 0) CHECK(cf_flush_deferred_prefetch(ctx));
-    if (rec) HIP_TRY(ctx, hipEventRecord(ev[2], ctx->stream));
+    if (rec) HIP_TRY(ctx, hipEventRecord(ev[2].get(), ctx->stream));
     if (merge) {
         HIP_TRY(ctx, launch_interpolate_and_stress(ctx->stream, ctx->launch, ctx->dev, ctx->grid, &ctx->deferred.src, &ctx->deferred.w,
                                                    &ctx->deferred.out, ocean, fluxes, ice, net));
@@ -988,7 +963,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     else
         HIP_TRY(ctx, launch_net_fluxes(ctx->stream, ctx->dev, ctx->grid, ocean, atmos, fluxes, ice, w, net, ctx->d_land_freshwater));
     if (rec) {
-        HIP_TRY(ctx, hipEventRecord(ev[3], ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ev[3].get(), ctx->stream));
         ++ctx->prof_count;
     }
     if (!hold_tail_work && ctx->merged_prefetch != 0 && ctx->deferred.valid && ctx->deferred.out.u != atmos->u) {
@@ -1008,12 +983,12 @@ int cf_update_state(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_wei
 
 int cf_profile_enable(cf_ctx* ctx, int max_records) {
     if (!ctx || max_records < 0) return fail(ctx, CF_ERR_INVALID, "cf_profile_enable: bad arguments");
-    for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
-    ctx->prof_events.clear();
-    ctx->prof_capacity = ctx->prof_count = 0;
-    ctx->prof_events.resize(4 * (size_t)max_records);
-    for (auto& e : ctx->prof_events) HIP_TRY(ctx, hipEventCreate(&e));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<cf::Event> events(4 * (size_t)max_records);
+    for (cf::Event& e : events) HIP_TRY(ctx, e.create(hipEventDefault));
+    ctx->prof_events = std::move(events);   // (the recorder of an earlier call goes)
     ctx->prof_capacity = max_records;
+    ctx->prof_count = 0;
     return CF_OK;
 }
 
@@ -1023,8 +998,8 @@ int cf_profile_read(cf_ctx* ctx, int kernel, double* avg_ms, int* records) {
     double sum = 0.0;
     for (int n = 0; n < ctx->prof_count; ++n) {
         float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->prof_events[4 * (size_t)n + kernel],
-                                        ctx->prof_events[4 * (size_t)n + kernel + 1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->prof_events[4 * (size_t)n + kernel].get(),
+                                        ctx->prof_events[4 * (size_t)n + kernel + 1].get()));
         sum += ms;
     }
     *avg_ms = ctx->prof_count ? sum / ctx->prof_count : 0.0;
@@ -1048,39 +1023,16 @@ int cf_time_stage(cf_ctx* ctx, int stage, int launches, const cf_atmos_source* s
                   const cf_ocean_surface* ocean, const cf_exchange_fields* atmos, const cf_interface_fluxes* fluxes,
                   const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* net, double* ms_per_launch) {
     if (!ctx || !ms_per_launch || launches <= 0) return fail(ctx, CF_ERR_INVALID, "cf_time_stage: bad arguments");
-    hipEvent_t t0, t1;
-    HIP_TRY(ctx, hipEventCreate(&t0));
-    HIP_TRY(ctx, hipEventCreate(&t1));
-    CHECK(run_stage(ctx, stage, src, w, ocean, atmos, fluxes, ice, net));  // one untimed launch (code load)
-    HIP_TRY(ctx, hipEventRecord(t0, ctx->stream));
-    for (int n = 0; n < launches; ++n) CHECK(run_stage(ctx, stage, src, w, ocean, atmos, fluxes, ice, net));
-    HIP_TRY(ctx, hipEventRecord(t1, ctx->stream));
-    HIP_TRY(ctx, hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, t0, t1));
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
-    *ms_per_launch = (double)ms / launches;
-    return CF_OK;
+    return time_launches(ctx, launches, ms_per_launch, [&] { return run_stage(ctx, stage, src, w, ocean, atmos, fluxes, ice, net); });
 }
 
 int cf_time_copy(cf_ctx* ctx, void* d_dst, const void* d_src, size_t bytes, int launches, double* ms_per_launch) {
     if (!ctx || !ms_per_launch || launches <= 0 || !d_dst || !d_src)
         return fail(ctx, CF_ERR_INVALID, "cf_time_copy: bad arguments");
-    hipEvent_t t0, t1;
-    HIP_TRY(ctx, hipEventCreate(&t0));
-    HIP_TRY(ctx, hipEventCreate(&t1));
-    HIP_TRY(ctx, launch_copy(ctx->stream, d_dst, d_src, bytes));
-    HIP_TRY(ctx, hipEventRecord(t0, ctx->stream));
-    for (int n = 0; n < launches; ++n) HIP_TRY(ctx, launch_copy(ctx->stream, d_dst, d_src, bytes));
-    HIP_TRY(ctx, hipEventRecord(t1, ctx->stream));
-    HIP_TRY(ctx, hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, t0, t1));
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
-    *ms_per_launch = (double)ms / launches;
-    return CF_OK;
+    return time_launches(ctx, launches, ms_per_launch, [&]() -> int {
+        HIP_TRY(ctx, launch_copy(ctx->stream, d_dst, d_src, bytes));
+        return CF_OK;
+    });
 }
 
 // ---- RCCL halo rows ---------------------------------------------------------------------------
@@ -1200,11 +1152,11 @@ int cf_set_sea_ice_formulation(cf_ctx* ctx, const cf_flux_params* ice_fluxes, co
         return fail(ctx, CF_ERR_INVALID, "the atmosphere-sea-ice interface takes SimilarityTheoryFluxes");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (!ctx->d_ice_tables) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_ice_tables, sizeof(double) * TABLE_DOUBLES));
-    if (!ctx->d_ice_params) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_ice_params, sizeof(DevParams)));
+    if (!ctx->d_ice_tables) HIP_TRY(ctx, ctx->d_ice_tables.create(sizeof(double) * TABLE_DOUBLES));
+    if (!ctx->d_ice_params) HIP_TRY(ctx, ctx->d_ice_params.create(sizeof(DevParams)));
     std::vector<double> t = build_solver_tables(d.stability);
-    HIP_TRY(ctx, hipMemcpy(ctx->d_ice_tables, t.data(), sizeof(double) * TABLE_DOUBLES, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_ice_params, &d, sizeof(DevParams), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_ice_tables.get(), t.data(), sizeof(double) * TABLE_DOUBLES, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_ice_params.get(), &d, sizeof(DevParams), hipMemcpyHostToDevice));
     ctx->ice_params = *ice_fluxes;
     ctx->ice_props = *ice;
     ctx->ice_dev = d;
@@ -1268,7 +1220,7 @@ int cf_set_sea_ice_albedo(cf_ctx* ctx, const cf_sea_ice_albedo_params* params) {
     CHECK(check_albedo_params(ctx, params));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->d_ice_albedo)
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_ice_albedo, sizeof(double) * (size_t)ctx->grid.sj * (ctx->grid.ny + 2 * ctx->grid.hy)));
+        HIP_TRY(ctx, ctx->d_ice_albedo.create(sizeof(double) * (size_t)ctx->grid.sj * (ctx->grid.ny + 2 * ctx->grid.hy)));
     ctx->ice_albedo = *params;
     ctx->ice_albedo_ccsm3 = true;
     return CF_OK;
@@ -1289,8 +1241,8 @@ static int resolve_ice_albedo(cf_ctx* ctx, const cf_sea_ice_state* in, cf_sea_ic
     if (in->albedo || !ctx->ice_albedo_ccsm3) return CF_OK;
     if (!in->thickness || !in->top_temperature) return fail(ctx, CF_ERR_INVALID, "SeaIceAlbedo(hi, hs, Ts) needs ice thickness and top temperature");
     HIP_TRY(ctx, launch_sea_ice_albedo(ctx->stream, ctx->ice_albedo, ctx->grid, in->thickness, in->snow_thickness, in->top_temperature,
-                                       ctx->d_ice_albedo));
-    out->albedo = ctx->d_ice_albedo;
+                                       ctx->d_ice_albedo.get()));
+    out->albedo = ctx->d_ice_albedo.get();
     return CF_OK;
 }
 
@@ -1346,7 +1298,7 @@ static int atmosphere_sea_ice_fluxes_impl(cf_ctx* ctx, const cf_sea_ice_state* i
     CHECK(wait_for_halos(ctx));
     CHECK(ensure_chunk_table(ctx, ocean->mask));
     HIP_TRY(ctx, launch_ai_fluxes(ctx->stream, ctx->launch, ctx->ice_dev, ctx->ice_loop, ctx->ice_kernel, ctx->grid, ice, ocean,
-                                  atmos, out, ctx->d_ice_tables, ctx->d_ice_params, ctx->trip_hints ? ctx->d_trip_ice : nullptr, tail, net_ice));
+                                  atmos, out, ctx->d_ice_tables.get(), ctx->d_ice_params.get(), ctx->trip_hints ? ctx->wet.d_trip_ice.get() : nullptr, tail, net_ice));
     return CF_OK;
 }
 
@@ -1471,12 +1423,12 @@ int cf_normalize_salinity_flux(cf_ctx* ctx, double* d_flux, const double* d_addi
     HIP_TRY(ctx, hipSetDevice(ctx->device));  // one process may drive several contexts / devices
     if (ctx->dev.mask_kind != CF_MASK_NONE && !d_mask)
         return fail(ctx, CF_ERR_INVALID, "mask_kind = %d but the mask is NULL", ctx->dev.mask_kind);
-    if (!ctx->d_reduce) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_reduce, sizeof(double) * (2 * SALINITY_PARTIAL_BLOCKS + 2)));
-    double* sums = ctx->d_reduce + 2 * SALINITY_PARTIAL_BLOCKS;
+    if (!ctx->d_reduce) HIP_TRY(ctx, ctx->d_reduce.create(sizeof(double) * (2 * SALINITY_PARTIAL_BLOCKS + 2)));
+    double* sums = ctx->d_reduce.get() + 2 * SALINITY_PARTIAL_BLOCKS;
     const int ncells = ctx->grid.nx * ctx->grid.ny;
     const int nblocks = std::max(1, std::min(SALINITY_PARTIAL_BLOCKS, (ncells + 255) / 256));
     HIP_TRY(ctx, launch_salinity_partial_sums(ctx->stream, ctx->dev, ctx->grid, d_flux, d_additional, d_area, d_mask,
-                                              ctx->d_reduce, nblocks, sums));
+                                              ctx->d_reduce.get(), nblocks, sums));
     if (ctx->comm && ctx->nranks > 1)  // the only collective near the path: two doubles
         NCCL_TRY(ctx, g_rccl.AllReduce(sums, sums, 2, ncclFloat64, ncclSum, ctx->comm, ctx->stream));
     HIP_TRY(ctx, launch_salinity_subtract(ctx->stream, ctx->grid, d_flux, sums, d_mean_out));
@@ -1496,17 +1448,19 @@ int cf_halo_exchange_rows(cf_ctx* ctx, double* const* d_fields, int nfields, int
     // that needs the rows comes next — and the two events each way would only be four queue packets (≈ 3 µs each,
     // measured on the event this round removed from the step): the exchange goes onto the context's own stream.
     const bool own_stream = ctx->merged_prefetch != 2;
-    if (own_stream && !ctx->comm_stream) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_main_idle, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_comm_done, hipEventDisableTiming));
+    if (own_stream && !ctx->comm_lane.stream) {
+        cf_ctx::CommLane lane;
+        HIP_TRY(ctx, lane.stream.create());
+        HIP_TRY(ctx, lane.ev_main_idle.create(hipEventDisableTiming));
+        HIP_TRY(ctx, lane.ev_comm_done.create(hipEventDisableTiming));
+        ctx->comm_lane = std::move(lane);
     }
     hipStream_t cs = ctx->stream;
     if (own_stream) {
         // the rows may only be overwritten once everything already queued on the main stream has read them
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_main_idle, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->comm_stream, ctx->ev_main_idle, 0));
-        cs = ctx->comm_stream;
+        HIP_TRY(ctx, hipEventRecord(ctx->comm_lane.ev_main_idle.get(), ctx->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->comm_lane.stream.get(), ctx->comm_lane.ev_main_idle.get(), 0));
+        cs = ctx->comm_lane.stream.get();
     }
     NCCL_TRY(ctx, g_rccl.GroupStart());
     for (int f = 0; f < nfields; ++f) {
@@ -1526,7 +1480,7 @@ int cf_halo_exchange_rows(cf_ctx* ctx, double* const* d_fields, int nfields, int
     }
     NCCL_TRY(ctx, g_rccl.GroupEnd());
     if (own_stream) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_comm_done, cs));
+        HIP_TRY(ctx, hipEventRecord(ctx->comm_lane.ev_comm_done.get(), cs));
         ctx->comm_pending = true;  // consumed by the next ocean-reading launch (or cf_sync)
     }
     return CF_OK;

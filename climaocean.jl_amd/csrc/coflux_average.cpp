@@ -19,18 +19,6 @@ int average_collect(cf_average* a, double weight) {
     return CF_OK;
 }
 
-void average_forget_context(cf_ctx* ctx) {
-    for (cf_average* a : ctx->averages) a->ctx = nullptr;
-    ctx->averages.clear();
-    ctx->average = nullptr;
-}
-
-static int live(cf_average* a, const char* what) {
-    if (!a) return fail(nullptr, CF_ERR_INVALID, "%s: averager is NULL", what);
-    if (!a->ctx) return fail(nullptr, CF_ERR_INVALID, "%s: the averager's context has been destroyed", what);
-    return CF_OK;
-}
-
 extern "C" {
 
 int cf_average_create(cf_ctx* ctx, int nfields, const double* const* d_sources, double* const* d_means, cf_average** out) {
@@ -40,11 +28,7 @@ int cf_average_create(cf_ctx* ctx, int nfields, const double* const* d_sources, 
     if (nfields < 1 || nfields > CF_AVERAGE_MAX_FIELDS)
         return fail(ctx, CF_ERR_INVALID, "cf_average_create: %d fields (1…%d)", nfields, CF_AVERAGE_MAX_FIELDS);
     const GridDesc& G = ctx->grid;
-    const uintptr_t bytes = (uintptr_t)G.sj * (uintptr_t)(G.ny + 2 * G.hy) * sizeof(double);
-    auto overlap = [&](const void* p, const void* q) {
-        const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
-        return x < y + bytes && y < x + bytes;
-    };
+    auto overlap = [&](const void* p, const void* q) { return fields_overlap(G, p, q); };
     for (int f = 0; f < nfields; ++f)
         if (!d_sources[f] || !d_means[f]) return fail(ctx, CF_ERR_INVALID, "cf_average_create: field %d has a NULL pointer", f);
     for (int f = 0; f < nfields; ++f)
@@ -55,43 +39,40 @@ int cf_average_create(cf_ctx* ctx, int nfields, const double* const* d_sources, 
                 return fail(ctx, CF_ERR_INVALID, "cf_average_create: means %d and %d overlap", f, g);
         }
     cf_average* a = new cf_average();
-    a->ctx = ctx;
     a->nfields = nfields;
     for (int f = 0; f < nfields; ++f) {
         a->fields.src[f] = d_sources[f];
         a->fields.mean[f] = d_means[f];
     }
-    ctx->averages.push_back(a);
+    child_adopt(ctx, a);
     *out = a;
     return CF_OK;
 }
 
 int cf_average_destroy(cf_average* a) {
     if (!a) return CF_OK;
-    if (cf_ctx* ctx = a->ctx) {
-        if (ctx->average == a) ctx->average = nullptr;
-        ctx->averages.erase(std::remove(ctx->averages.begin(), ctx->averages.end(), a), ctx->averages.end());
-    }
+    if (a->ctx && a->ctx->average == a) a->ctx->average = nullptr;
+    child_leave(a);
     delete a;
     return CF_OK;
 }
 
 int cf_average_reset(cf_average* a) {
-    CHECK(live(a, "cf_average_reset"));
+    CHECK(live(a, "cf_average_reset", "averager"));
     a->total = 0.0;
     a->samples = 0;
     return CF_OK;
 }
 
 int cf_average_collect(cf_average* a, double weight) {
-    CHECK(live(a, "cf_average_collect"));
+    CHECK(live(a, "cf_average_collect", "averager"));
     if (!(weight > 0.0) || !std::isfinite(weight) || !std::isfinite(a->total + weight))
         return fail(a->ctx, CF_ERR_INVALID, "cf_average_collect: weight %g (> 0 and finite)", weight);
     return average_collect(a, weight);
 }
 
 int cf_average_weight(cf_average* a, double* total, int64_t* samples) {
-    CHECK(live(a, "cf_average_weight"));
+    CHECK(live(a, "cf_average_weight", "averager"));
     if (total) *total = a->total;
     if (samples) *samples = a->samples;
     return CF_OK;

@@ -20,6 +20,7 @@
 #include "coflux_fast.hpp"
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
+#include "coflux_owned.hpp"
 #include "coflux_tables.h"
 
 using namespace coflux;
@@ -40,15 +41,25 @@ struct RcclApi {
     ncclResult_t (*CommCuDevice)(const ncclComm_t, int*) = nullptr;
 };
 
+// What averagers, integrators, regridders and snapshot windows share: a handle made on a context may outlive it.  cf_destroy
+// orphans every child (orphan_children); calls that need the context then fail through live(), destroy still works.
+struct cf_child {
+    cf_ctx* ctx = nullptr;   // NULL once the context is destroyed
+    int device = 0;
+};
+
+// Ownership: every stream, event, device buffer and IPC mapping below is a cf:: owner (coflux_owned.hpp) and releases itself
+// with the context; LaunchCfg, PeerMailbox and the kernels' arguments carry raw pointers filled from get().  Resources that
+// only make sense together sit in one struct, built aside and moved in only when all of it was created.
 struct cf_ctx {
     int device = 0;
     GridDesc grid{};
     cf_flux_params params{};
     DevParams dev{};
-    hipStream_t own_stream = nullptr;
+    cf::Stream own_stream;
     hipStream_t stream = nullptr;
     LoopParams fast{};
-    DevParams* d_params = nullptr;
+    cf::DeviceBuffer<DevParams> d_params;
     LaunchCfg launch = [] {
         LaunchCfg L{};
         L.solver = CF_SOLVER_TABLES;
@@ -56,25 +67,27 @@ struct cf_ctx {
         L.cu_count = 256;
         return L;
     }();
-    uint8_t* d_trip = nullptr;       // trip count of the previous call per wet-list entry
-    uint32_t* d_wet_pos = nullptr;   // static wet lists of the solver's chunks
-    uint32_t* d_lean_sorted = nullptr;  // the lean ocean kernel's sorted lists (same capacity as d_wet_pos)
-    int* d_lean_info = nullptr;         // per chunk: listed wet cells + fingerprint (4 ints)
+    struct WetLists {                          // regrown as a unit by ensure_chunk_table
+        cf::DeviceBuffer<uint8_t> d_trip;          // trip count of the previous call per wet-list entry
+        cf::DeviceBuffer<uint32_t> d_wet_pos;      // static wet lists of the solver's chunks
+        cf::DeviceBuffer<uint32_t> d_lean_sorted;  // the lean ocean kernel's sorted lists (same capacity as d_wet_pos)
+        cf::DeviceBuffer<int> d_lean_info;         // per chunk: listed wet cells + fingerprint (4 ints)
+        cf::DeviceBuffer<uint8_t> d_trip_ice;      // trip counts of the sea-ice interface solve per wet-list entry
+        size_t entries = 0;                        // entries allocated in d_wet_pos / d_trip / d_trip_ice
+    } wet;
     bool trip_hints = true;
     bool lean_hints = false;         // the lean ocean kernel sorts its lists by trip count only when CF_OPT_TRIP_HINTS = 1
     int merged_prefetch = 0;         // CF_OPT_MERGED_PREFETCH: a requested next-step interpolation rides in the face-stress launch
     double certified_budget = 8e-7;  // CF_OPT_CERTIFIED_BUDGET
     int fused_net = 2;               // cf_update_state: net fluxes in the solver's epilogue + a stress kernel: 0 never, 1 when possible, 2 with the lean ocean kernel
     // cost-balanced chunk table of the solver, rebuilt when the wet mask (pointer / kind / surface z) changes
-    int* d_chunk_sums = nullptr;
-    int* d_chunk_begins = nullptr;
-    int* d_chunk_meta = nullptr;
+    cf::DeviceBuffer<int> d_chunk_sums, d_chunk_begins, d_chunk_meta;
     const void* chunk_mask = nullptr;
     int chunk_mask_kind = -1;
     double chunk_z_surface = 0.0;
     int chunk_wet = 0;      // wet cells per chunk actually used
     bool chunk_valid = false;
-    double* d_reduce = nullptr;  // [2·SALINITY_PARTIAL_BLOCKS partial sums][2 totals]
+    cf::DeviceBuffer<double> d_reduce;  // [2·SALINITY_PARTIAL_BLOCKS partial sums][2 totals]
     // atmosphere–sea-ice formulation (cf_set_sea_ice_formulation)
     bool ice_ready = false;
     cf_flux_params ice_params{};
@@ -87,29 +100,32 @@ struct cf_ctx {
     const double* d_land_freshwater = nullptr;   // cf_set_land_freshwater (borrowed)
     bool ice_albedo_ccsm3 = false;   // cf_set_sea_ice_albedo: SeaIceAlbedo(hi, hs, Ts) wherever no albedo field is given
     cf_sea_ice_albedo_params ice_albedo{};
-    double* d_ice_albedo = nullptr;  // the albedo field of the current step (computed by the library)
-    uint8_t* d_trip_ice = nullptr;   // trip counts of the sea-ice interface solve per wet-list entry
-    size_t wet_list_entries = 0;     // entries allocated in d_wet_pos / d_trip / d_trip_ice
-    double* d_ice_tables = nullptr;
-    DevParams* d_ice_params = nullptr;
+    cf::DeviceBuffer<double> d_ice_albedo;  // the albedo field of the current step (computed by the library)
+    cf::DeviceBuffer<double> d_ice_tables;
+    cf::DeviceBuffer<DevParams> d_ice_params;
     // halo rows travel on their own stream so that they overlap the interpolation kernel, which
     // does not read the ocean state; consumers of the ocean fields wait on ev_comm_done
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_main_idle = nullptr, ev_comm_done = nullptr;
+    struct CommLane {
+        cf::Stream stream;
+        cf::Event ev_main_idle, ev_comm_done;
+    } comm_lane;
     bool comm_pending = false;
-    double* d_tables = nullptr;
+    cf::DeviceBuffer<double> d_tables;
     int tables_kind = -1;
     std::string error;
     std::mutex error_mutex;  // cf_window_wait_slot may fail on a reader thread while the stepping thread reads the text
     // auxiliary stream: the next step's interpolation runs here while the current step's solver runs on `stream`
     // (cf_prefetch_atmosphere_state); one record per exchange-field set, matched by cf_update_state
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_aux_gate = nullptr;
+    struct AuxLane {
+        cf::Stream stream;
+        cf::Event ev_gate;
+        cf::Event done[2];   // prefetch[k].done views done[k]
+    } aux;
     struct Prefetch {
         const double* key = nullptr;  // exchange set, identified by its u pointer
         int level1 = 0, level2 = 0;
         double tf = 0.0;
-        hipEvent_t done = nullptr;
+        hipEvent_t done = nullptr;    // a view of aux.done[k]: NULL until the auxiliary lane exists
         bool valid = false;
         bool on_main = false;         // launched on the main stream (merged with the face stresses): stream order, no event
     } prefetch[2];
@@ -117,24 +133,24 @@ struct cf_ctx {
     // that the solver's workgroups are dispatched first and the interpolation only fills what they leave free
     struct Deferred {
         bool valid = false;
-        bool gated = false;  // ev_aux_gate was recorded when the request was made (not with merged_prefetch: the request
+        bool gated = false;  // aux.ev_gate was recorded when the request was made (not with merged_prefetch: the request
                              // normally leaves on the main stream, where stream order gates it; a flush records it late)
         cf_atmos_source src{};
         cf_interp_weights w{};
         cf_exchange_fields out{};
     } deferred;
     // peer-direct halo rows (coflux_halo.hip)
-    PeerMailbox peer{};
-    size_t peer_bytes = 0;
+    PeerMailbox peer{};                                  // raw views of the three below
+    cf::DeviceBuffer<char> peer_mine;                    // this context's mailbox (fine-grained)
+    cf::IpcMapping peer_south_map, peer_north_map;       // a neighbour's, where it was opened through HIP IPC
     int peer_max_fields = 0, peer_max_rows = 0;
     bool peer_connected = false;
-    bool peer_south_mapped = false, peer_north_mapped = false;  // opened through HIP IPC (to be closed)
     unsigned long long peer_seq = 0;
-    int* d_peer_status = nullptr;
+    cf::DeviceBuffer<int> d_peer_status;
     // the peer-direct exchange as riders of the solver launch (CF_OPT_HALO_IN_SOLVER_LAUNCH; coflux_lean_kernel.hpp, HALO)
     int halo_in_launch = 0;
     unsigned long long halo_in_launch_count = 0;            // exchanges that rode in a solver launch (cf_peer_halo_stats)
-    unsigned long long* d_halo_counters = nullptr;          // [0,1] fields sent south / north, [2,3] fields received from there
+    cf::DeviceBuffer<unsigned long long> d_halo_counters;   // [0,1] fields sent south / north, [2,3] fields received from there
     unsigned long long halo_expect_sent[2] = {0, 0}, halo_expect_done[2] = {0, 0};
     struct HaloRequest {                                    // cf_time_steps asked for this step's rows: the next solver launch carries
         bool valid = false;                                 // them, or cf_update_state issues the stand-alone kernel in front of it
@@ -145,25 +161,21 @@ struct cf_ctx {
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
     // per-kernel event recorder (cf_profile_enable): 4 events per recorded update_state
-    std::vector<hipEvent_t> prof_events;
+    std::vector<cf::Event> prof_events;
     int prof_capacity = 0, prof_count = 0;
-    // time averages (coflux_average.cpp): every averager made on this context (cf_destroy orphans them), and the one
-    // cf_time_steps collects (cf_attach_average)
-    std::vector<cf_average*> averages;
+    // every averager, integrator, regridder and window made on this context (cf_destroy orphans them)
+    std::vector<cf_child*> children;
+    // time averages (coflux_average.cpp): the one cf_time_steps collects (cf_attach_average)
     cf_average* average = nullptr;
     int32_t average_stride = 1;
     double average_step_weight = 0.0;
-    // surface integrals (coflux_integrals.cpp): the same pair for the integrators (cf_attach_integrals)
-    std::vector<cf_integrals*> integrators;
+    // surface integrals (coflux_integrals.cpp): the same for the integrators (cf_attach_integrals)
     cf_integrals* integrals = nullptr;
     int32_t integrals_stride = 1;
     double integrals_time_origin = 0.0, integrals_step_seconds = 0.0;
-    // surface regridders (coflux_regrid.cpp): every one made on this context (cf_destroy orphans them)
-    std::vector<cf_regrid*> regridders;
 };
 
-struct cf_average {
-    cf_ctx* ctx = nullptr;   // NULL once the context is destroyed
+struct cf_average : cf_child {
     int nfields = 0;
     AverageFields fields{};
     double total = 0.0;      // the window's total weight
@@ -172,23 +184,19 @@ struct cf_average {
     DerivedArgs terms{};
 };
 
-struct cf_integrals {
-    cf_ctx* ctx = nullptr;       // NULL once the context is destroyed
-    int device = 0;
+struct cf_integrals : cf_child {
     IntegralArgs args{};
     int max_blocks = 0;
     int64_t capacity = 0, count = 0;
     std::vector<double> times;   // of the records, host side
-    double* d_series = nullptr;  // [capacity][n_entries]; the partial sums and the entries' descriptors lie behind it
+    cf::DeviceBuffer<double> d_series;  // [capacity][n_entries]; the partial sums and the entries' descriptors lie behind it
 };
 
-struct cf_regrid {
-    cf_ctx* ctx = nullptr;       // NULL once the context is destroyed
-    int device = 0;
+struct cf_regrid : cf_child {
     RegridTables tables{};
     int64_t n_rows = 0;
     int max_blocks = 0;
-    void* d_block = nullptr;     // the one allocation behind every table
+    cf::DeviceBuffer<unsigned char> d_block;  // the one allocation behind every table
 };
 
 // sets the thread-local and the context's last-error text and returns `code`
@@ -212,15 +220,37 @@ int cf_fail(cf_ctx* ctx, int code, const char* fmt, ...);
 extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows);
 // coflux_average.cpp: one collection of `a` (cf_average_collect without the argument checks of the ABI entry)
 int average_collect(cf_average* a, double weight);
-// coflux_average.cpp: cf_destroy orphans the context's averagers
-void average_forget_context(cf_ctx* ctx);
 // coflux_integrals.cpp: one collection of `q` (the series must have room: integrals_room)
 int integrals_collect(cf_integrals* q, double time);
 // coflux_integrals.cpp: CF_ERR_INVALID unless the attached integrator's series has room for what cf_time_steps(first_step, nsteps) collects
 int integrals_room(cf_ctx* ctx, int64_t first_step, int nsteps);
-// coflux_integrals.cpp: cf_destroy orphans the context's integrators
-void integrals_forget_context(cf_ctx* ctx);
-// coflux_regrid.cpp: cf_destroy orphans the context's regridders
-void regrid_forget_context(cf_ctx* ctx);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state)
 extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx);
+
+// whether two ocean-grid fields (halos included) at p and q share bytes: what the averagers refuse between a mean and anything else
+inline bool fields_overlap(const GridDesc& G, const void* p, const void* q) {
+    const uintptr_t bytes = (uintptr_t)G.sj * (uintptr_t)(G.ny + 2 * G.hy) * sizeof(double), x = (uintptr_t)p, y = (uintptr_t)q;
+    return x < y + bytes && y < x + bytes;
+}
+
+// The child handles: `child` joins ctx's list / leaves it (a no-op once orphaned) / cf_destroy orphans them all
+inline void child_adopt(cf_ctx* ctx, cf_child* child) {
+    child->ctx = ctx;
+    child->device = ctx->device;
+    ctx->children.push_back(child);
+}
+inline void child_leave(cf_child* child) {
+    if (cf_ctx* ctx = child->ctx) ctx->children.erase(std::remove(ctx->children.begin(), ctx->children.end(), child), ctx->children.end());
+}
+inline void orphan_children(cf_ctx* ctx) {
+    for (cf_child* child : ctx->children) child->ctx = nullptr;
+    ctx->children.clear();
+    ctx->average = nullptr;
+    ctx->integrals = nullptr;
+}
+// CF_ERR_INVALID unless `child` is a handle whose context is alive: live(a, "cf_average_reset", "averager")
+inline int live(const cf_child* child, const char* fn, const char* kind) {
+    if (!child) return fail(nullptr, CF_ERR_INVALID, "%s: %s is NULL", fn, kind);
+    if (!child->ctx) return fail(nullptr, CF_ERR_INVALID, "%s: the %s's context has been destroyed", fn, kind);
+    return CF_OK;
+}

@@ -76,11 +76,7 @@ extern "C" int cf_average_create_derived(cf_ctx* ctx, const cf_average_desc* des
         if (an) A.need_y |= 1u << a;
         if (bn) A.need_y |= 1u << b;
     }
-    const uintptr_t bytes = (uintptr_t)G.sj * (uintptr_t)(G.ny + 2 * G.hy) * sizeof(double);
-    auto overlap = [&](const void* p, const void* q) {
-        const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
-        return x < y + bytes && y < x + bytes;
-    };
+    auto overlap = [&](const void* p, const void* q) { return fields_overlap(G, p, q); };
     for (int t = 0; t < n; ++t) {
         for (int s = 0; s < A.n_src; ++s)
             if (overlap(A.mean[t], A.src[s]))
@@ -89,11 +85,10 @@ extern "C" int cf_average_create_derived(cf_ctx* ctx, const cf_average_desc* des
             if (overlap(A.mean[t], A.mean[u])) return fail(ctx, CF_ERR_INVALID, "cf_average_create_derived: means %d and %d overlap", u, t);
     }
     cf_average* a = new cf_average();
-    a->ctx = ctx;
     a->nfields = n;
     a->derived = true;
     a->terms = A;
-    ctx->averages.push_back(a);
+    child_adopt(ctx, a);
     *out = a;
     return CF_OK;
 }

@@ -9,7 +9,7 @@ int integrals_collect(cf_integrals* q, double time) {
     if (q->count >= q->capacity)
         return fail(ctx, CF_ERR_INVALID, "cf_integrals_collect: the series is full (%lld records)", (long long)q->capacity);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_integrals(ctx->stream, q->args, ctx->grid, q->d_series + (size_t)q->count * (size_t)q->args.n_entries,
+    HIP_TRY(ctx, launch_integrals(ctx->stream, q->args, ctx->grid, q->d_series.get() + (size_t)q->count * (size_t)q->args.n_entries,
                                   q->max_blocks));
     q->times[(size_t)q->count] = time;
     ++q->count;
@@ -24,18 +24,6 @@ int integrals_room(cf_ctx* ctx, int64_t first_step, int nsteps) {
     if (q->count + collections > q->capacity)
         return fail(ctx, CF_ERR_INVALID, "cf_time_steps: the attached integrator's series holds %lld of %lld records and this call "
                     "would add %lld", (long long)q->count, (long long)q->capacity, (long long)collections);
-    return CF_OK;
-}
-
-void integrals_forget_context(cf_ctx* ctx) {
-    for (cf_integrals* q : ctx->integrators) q->ctx = nullptr;
-    ctx->integrators.clear();
-    ctx->integrals = nullptr;
-}
-
-static int live(cf_integrals* q, const char* what) {
-    if (!q) return fail(nullptr, CF_ERR_INVALID, "%s: integrator is NULL", what);
-    if (!q->ctx) return fail(nullptr, CF_ERR_INVALID, "%s: the integrator's context has been destroyed", what);
     return CF_OK;
 }
 
@@ -90,56 +78,48 @@ int cf_integrals_create(cf_ctx* ctx, const cf_integrals_desc* desc, int32_t capa
     // one allocation: [capacity][n_entries] series | [tiles][bucket] partial sums | thresholds | entry descriptors
     const size_t n_series = (size_t)capacity * (size_t)K.n_entries;
     const size_t n_partial = (size_t)integrals_tiles(ctx->grid) * (size_t)integrals_bucket(K.n_entries);
-    double* d_series = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d_series, (n_series + n_partial + CF_INTEGRALS_MAX_ENTRIES) * sizeof(double) + sizeof(entry)));
-    K.partial = d_series + n_series;
-    double* d_threshold = d_series + n_series + n_partial;
+    cf::DeviceBuffer<double> series;
+    HIP_TRY(ctx, series.create((n_series + n_partial + CF_INTEGRALS_MAX_ENTRIES) * sizeof(double) + sizeof(entry)));
+    K.partial = series.get() + n_series;
+    double* d_threshold = series.get() + n_series + n_partial;
     K.threshold = d_threshold;
     K.entry = reinterpret_cast<const uint32_t*>(d_threshold + CF_INTEGRALS_MAX_ENTRIES);
-    hipError_t up = hipMemcpy(d_threshold, threshold, sizeof(threshold), hipMemcpyHostToDevice);
-    if (up == hipSuccess) up = hipMemcpy(d_threshold + CF_INTEGRALS_MAX_ENTRIES, entry, sizeof(entry), hipMemcpyHostToDevice);
-    if (up != hipSuccess) {
-        (void)hipFree(d_series);
-        HIP_TRY(ctx, up);
-    }
+    HIP_TRY(ctx, hipMemcpy(d_threshold, threshold, sizeof(threshold), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_threshold + CF_INTEGRALS_MAX_ENTRIES, entry, sizeof(entry), hipMemcpyHostToDevice));
     cf_integrals* q = new cf_integrals();
-    q->ctx = ctx;
-    q->device = ctx->device;
     q->args = K;
     q->max_blocks = desc->max_workgroups;
     q->capacity = capacity;
     q->times.assign((size_t)capacity, 0.0);
-    q->d_series = d_series;
-    ctx->integrators.push_back(q);
+    q->d_series = std::move(series);
+    child_adopt(ctx, q);
     *out = q;
     return CF_OK;
 }
 
 int cf_integrals_destroy(cf_integrals* q) {
     if (!q) return CF_OK;
-    if (cf_ctx* ctx = q->ctx) {
-        if (ctx->integrals == q) ctx->integrals = nullptr;
-        ctx->integrators.erase(std::remove(ctx->integrators.begin(), ctx->integrators.end(), q), ctx->integrators.end());
-    }
-    // hipFree waits for the device: a collection still in flight has finished before its buffers go
-    if (hipSetDevice(q->device) == hipSuccess) (void)hipFree(q->d_series);
+    if (q->ctx && q->ctx->integrals == q) q->ctx->integrals = nullptr;
+    child_leave(q);
+    // hipFree (in the delete; it needs no current device) waits for the buffer's device: a collection still in flight has finished before its buffers go
+    (void)hipSetDevice(q->device);
     delete q;
     return CF_OK;
 }
 
 int cf_integrals_collect(cf_integrals* q, double time) {
-    CHECK(live(q, "cf_integrals_collect"));
+    CHECK(live(q, "cf_integrals_collect", "integrator"));
     return integrals_collect(q, time);
 }
 
 int cf_integrals_count(cf_integrals* q, int64_t* records) {
-    CHECK(live(q, "cf_integrals_count"));
+    CHECK(live(q, "cf_integrals_count", "integrator"));
     if (records) *records = q->count;
     return CF_OK;
 }
 
 int cf_integrals_read(cf_integrals* q, int64_t first, int64_t n, double* h_values, double* h_times) {
-    CHECK(live(q, "cf_integrals_read"));
+    CHECK(live(q, "cf_integrals_read", "integrator"));
     cf_ctx* ctx = q->ctx;
     if (first < 0 || n < 0 || first + n > q->count || (n > 0 && !h_values))
         return fail(ctx, CF_ERR_INVALID, "cf_integrals_read: records %lld … %lld of %lld", (long long)first, (long long)(first + n),
@@ -147,7 +127,7 @@ int cf_integrals_read(cf_integrals* q, int64_t first, int64_t n, double* h_value
     if (n == 0) return CF_OK;
     const size_t ne = (size_t)q->args.n_entries;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(h_values, q->d_series + (size_t)first * ne, (size_t)n * ne * sizeof(double), hipMemcpyDeviceToHost,
+    HIP_TRY(ctx, hipMemcpyAsync(h_values, q->d_series.get() + (size_t)first * ne, (size_t)n * ne * sizeof(double), hipMemcpyDeviceToHost,
                                 ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (h_times) std::copy(q->times.begin() + first, q->times.begin() + first + n, h_times);
@@ -155,7 +135,7 @@ int cf_integrals_read(cf_integrals* q, int64_t first, int64_t n, double* h_value
 }
 
 int cf_integrals_reset(cf_integrals* q) {
-    CHECK(live(q, "cf_integrals_reset"));
+    CHECK(live(q, "cf_integrals_reset", "integrator"));
     q->count = 0;
     return CF_OK;
 }

@@ -5,11 +5,6 @@
 // operator has rows of several segments.
 #include "coflux_ctx.hpp"
 
-void regrid_forget_context(cf_ctx* ctx) {
-    for (cf_regrid* rg : ctx->regridders) rg->ctx = nullptr;
-    ctx->regridders.clear();
-}
-
 namespace {
 
 // the device block is laid out piece by piece, every piece 16-byte aligned
@@ -103,21 +98,14 @@ int cf_regrid_create(cf_ctx* ctx, const cf_regrid_desc* desc, cf_regrid** out) {
     if (!short_rows.empty()) std::memcpy(host.data() + at_short, short_rows.data(), short_rows.size() * sizeof(uint32_t));
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    unsigned char* d = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d, std::max<size_t>(L.bytes, 16)));
-    if (upload > 0) {
-        const hipError_t up = hipMemcpy(d, host.data(), upload, hipMemcpyHostToDevice);
-        if (up != hipSuccess) {
-            (void)hipFree(d);
-            HIP_TRY(ctx, up);
-        }
-    }
+    cf::DeviceBuffer<unsigned char> block;
+    HIP_TRY(ctx, block.create(std::max<size_t>(L.bytes, 16)));
+    unsigned char* const d = block.get();
+    if (upload > 0) HIP_TRY(ctx, hipMemcpy(d, host.data(), upload, hipMemcpyHostToDevice));
     cf_regrid* rg = new cf_regrid();
-    rg->ctx = ctx;
-    rg->device = ctx->device;
     rg->n_rows = n_rows;
     rg->max_blocks = desc->max_workgroups;
-    rg->d_block = d;
+    rg->d_block = std::move(block);
     RegridTables& T = rg->tables;
     T.weight = reinterpret_cast<const double*>(d + at_weight);
     T.segments = reinterpret_cast<const RegridSegment*>(d + at_segments);
@@ -133,25 +121,23 @@ int cf_regrid_create(cf_ctx* ctx, const cf_regrid_desc* desc, cf_regrid** out) {
     T.n_segments = (uint32_t)segments.size();
     T.n_long_rows = (uint32_t)long_rows.size();
     T.mode = desc->mode;
-    ctx->regridders.push_back(rg);
+    child_adopt(ctx, rg);
     *out = rg;
     return CF_OK;
 }
 
 int cf_regrid_destroy(cf_regrid* rg) {
     if (!rg) return CF_OK;
-    if (cf_ctx* ctx = rg->ctx)
-        ctx->regridders.erase(std::remove(ctx->regridders.begin(), ctx->regridders.end(), rg), ctx->regridders.end());
-    // hipFree waits for the device: an apply still in flight has finished before its tables go
-    if (hipSetDevice(rg->device) == hipSuccess) (void)hipFree(rg->d_block);
+    child_leave(rg);
+    // hipFree (in the delete; it needs no current device) waits for the buffer's device: an apply still in flight has finished before its tables go
+    (void)hipSetDevice(rg->device);
     delete rg;
     return CF_OK;
 }
 
 int cf_regrid_apply(cf_regrid* rg, int32_t n_fields, const double* const* src, double* const* dst, double* coverage) {
-    if (!rg) return fail(nullptr, CF_ERR_INVALID, "cf_regrid_apply: regridder is NULL");
+    CHECK(live(rg, "cf_regrid_apply", "regridder"));
     cf_ctx* ctx = rg->ctx;
-    if (!ctx) return fail(nullptr, CF_ERR_INVALID, "cf_regrid_apply: the regridder's context has been destroyed");
     if (n_fields < 1 || n_fields > CF_REGRID_MAX_FIELDS)
         return fail(ctx, CF_ERR_INVALID, "cf_regrid_apply: %d fields (1…%d)", n_fields, CF_REGRID_MAX_FIELDS);
     if (!src || !dst) return fail(ctx, CF_ERR_INVALID, "cf_regrid_apply: NULL src or dst");

@@ -13,17 +13,19 @@
 static std::mutex g_peer_mutex;
 static std::map<std::string, std::pair<char*, int>> g_peer_local;  // handle bytes → (mailbox, device)
 
-
 static int ensure_aux_stream(cf_ctx* ctx) {
-    if (ctx->aux_stream) return CF_OK;
+    if (ctx->aux.stream) return CF_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_aux_gate, hipEventDisableTiming));
-    for (auto& p : ctx->prefetch) HIP_TRY(ctx, hipEventCreateWithFlags(&p.done, hipEventDisableTiming));
+    cf_ctx::AuxLane lane;
+    HIP_TRY(ctx, lane.stream.create());
+    HIP_TRY(ctx, lane.ev_gate.create(hipEventDisableTiming));
+    for (cf::Event& e : lane.done) HIP_TRY(ctx, e.create(hipEventDisableTiming));
+    ctx->aux = std::move(lane);
+    for (int k = 0; k < 2; ++k) ctx->prefetch[k].done = ctx->aux.done[k].get();
     return CF_OK;
 }
 
-// Launch the interpolation of `src` into `out` on the auxiliary stream, gated on ev_aux_gate (recorded by the caller
+// Launch the interpolation of `src` into `out` on the auxiliary stream, gated on the lane's gate event (recorded by the caller
 // on the main stream at the point after which `out` is free to be overwritten).
 int cf_launch_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w, const cf_exchange_fields* out) {
     cf_ctx::Prefetch* rec = nullptr;
@@ -33,13 +35,13 @@ int cf_launch_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_
         for (auto& p : ctx->prefetch)
             if (!p.valid) rec = &p;
     if (!rec) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
-    if (!ctx->deferred.gated) HIP_TRY(ctx, hipEventRecord(ctx->ev_aux_gate, ctx->stream));  // (a later gate than needed: still ordered)
+    if (!ctx->deferred.gated) HIP_TRY(ctx, hipEventRecord(ctx->aux.ev_gate.get(), ctx->stream));  // (a later gate than needed: still ordered)
     ctx->deferred.gated = false;
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_aux_gate, 0));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux.stream.get(), ctx->aux.ev_gate.get(), 0));
     // the LDS-free gather kernel (≤ 56 VGPRs, no LDS): it is resident BESIDE the solver's workgroups, which fill
     // the CU's LDS and 456 of 512 registers per SIMD; the tiled kernel would wait for them to retire
-    HIP_TRY(ctx, launch_interpolate_background(ctx->aux_stream, ctx->grid, src, w, out));
-    HIP_TRY(ctx, hipEventRecord(rec->done, ctx->aux_stream));
+    HIP_TRY(ctx, launch_interpolate_background(ctx->aux.stream.get(), ctx->grid, src, w, out));
+    HIP_TRY(ctx, hipEventRecord(rec->done, ctx->aux.stream.get()));
     rec->key = out->u;
     rec->level1 = src->level1;
     rec->level2 = src->level2;
@@ -95,7 +97,7 @@ static int request_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_in
     // With CF_OPT_MERGED_PREFETCH the request leaves inside a main-stream launch (stream order is the gate) and an event
     // per step would only put a barrier packet into the queue; the rare flush to the auxiliary stream records it then.
     ctx->deferred.gated = !(defer && ctx->merged_prefetch != 0);
-    if (ctx->deferred.gated) HIP_TRY(ctx, hipEventRecord(ctx->ev_aux_gate, ctx->stream));
+    if (ctx->deferred.gated) HIP_TRY(ctx, hipEventRecord(ctx->aux.ev_gate.get(), ctx->stream));
     if (!defer) return cf_launch_prefetch(ctx, src, w, out);
     ctx->deferred.src = *src;
     ctx->deferred.w = *w;
@@ -121,52 +123,51 @@ int cf_peer_halo_export(cf_ctx* ctx, int max_fields, int max_rows, void* handle_
                     PEER_MAX_FIELDS, max_rows, ctx->grid.hy);
     static_assert(sizeof(hipIpcMemHandle_t) <= CF_PEER_HANDLE_BYTES, "HIP IPC handle does not fit the ABI blob");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->peer.mine) return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_export: this context already has a mailbox");
+    if (ctx->peer_mine) return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_export: this context already has a mailbox");
     const size_t slot = (size_t)max_fields * max_rows * ctx->grid.sj;
     const size_t bytes = PEER_FLAG_BYTES + 4 * slot * sizeof(double);
-    void* p = nullptr;
+    cf::DeviceBuffer<char> mailbox;
+    cf::DeviceBuffer<int> status;
     // fine-grained: stores arriving over xGMI and the owner's polling loads must meet in memory, not in a cache.
     // Mandatory: on coarse-grained memory the flag poll can spin to its timeout and — worse — the rows read
     // behind the flag can come from stale L2 lines, a silently wrong halo.  The caller falls back to the RCCL exchange.
-    {
-        const hipError_t e = hipExtMallocWithFlags(&p, bytes, hipDeviceMallocFinegrained);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, CF_ERR_COMM, "cf_peer_halo_export: no fine-grained device memory for the halo mailbox (%s); use cf_halo_exchange_rows (RCCL)",
-                        hipGetErrorString(e));
-        }
+    hipError_t e = mailbox.create_fine_grained(bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, CF_ERR_COMM, "cf_peer_halo_export: no fine-grained device memory for the halo mailbox (%s); use cf_halo_exchange_rows (RCCL)",
+                    hipGetErrorString(e));
     }
-    HIP_TRY(ctx, hipMemset(p, 0, bytes));
+    HIP_TRY(ctx, hipMemset(mailbox.get(), 0, bytes));
     if (!ctx->d_peer_status) {
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_peer_status, sizeof(int)));
-        HIP_TRY(ctx, hipMemset(ctx->d_peer_status, 0, sizeof(int)));
+        HIP_TRY(ctx, status.create(sizeof(int)));
+        HIP_TRY(ctx, hipMemset(status.get(), 0, sizeof(int)));
     }
     HIP_TRY(ctx, hipDeviceSynchronize());
     hipIpcMemHandle_t h;
     std::memset(&h, 0, sizeof h);
-    hipError_t e = hipIpcGetMemHandle(&h, p);
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return fail(ctx, CF_ERR_HIP, "hipIpcGetMemHandle on the halo mailbox: %s", hipGetErrorString(e));
-    }
-    ctx->peer.mine = (char*)p;
+    e = hipIpcGetMemHandle(&h, mailbox.get());
+    if (e != hipSuccess) return fail(ctx, CF_ERR_HIP, "hipIpcGetMemHandle on the halo mailbox: %s", hipGetErrorString(e));
+    // everything succeeded: the context takes the mailbox (and a status word it did not have yet)
+    if (status) ctx->d_peer_status = std::move(status);
+    ctx->peer_mine = std::move(mailbox);
+    ctx->peer.mine = ctx->peer_mine.get();
     ctx->peer.data_offset = PEER_FLAG_BYTES;
     ctx->peer.slot_doubles = slot;
-    ctx->peer_bytes = bytes;
     ctx->peer_max_fields = max_fields;
     ctx->peer_max_rows = max_rows;
     std::memset(handle_out, 0, CF_PEER_HANDLE_BYTES);
     std::memcpy(handle_out, &h, sizeof h);
     {
         std::lock_guard<std::mutex> lock(g_peer_mutex);
-        g_peer_local[std::string((const char*)handle_out, CF_PEER_HANDLE_BYTES)] = {(char*)p, ctx->device};
+        g_peer_local[std::string((const char*)handle_out, CF_PEER_HANDLE_BYTES)] = {ctx->peer.mine, ctx->device};
     }
     return CF_OK;
 }
 
-static int map_mailbox(cf_ctx* ctx, const void* handle, char** out, bool* opened) {
+// `*out`: the neighbour's mailbox behind `handle` (NULL without one); `*mapping` owns it where HIP IPC had to open it
+static int map_mailbox(cf_ctx* ctx, const void* handle, char** out, cf::IpcMapping* mapping) {
     *out = nullptr;
-    *opened = false;
+    mapping->reset();
     if (!handle) return CF_OK;
     {
         std::lock_guard<std::mutex> lock(g_peer_mutex);
@@ -188,23 +189,21 @@ static int map_mailbox(cf_ctx* ctx, const void* handle, char** out, bool* opened
     }
     hipIpcMemHandle_t h;
     std::memcpy(&h, handle, sizeof h);
-    void* p = nullptr;
-    hipError_t e = hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess);
+    hipError_t e = mapping->create(h);
     if (e != hipSuccess) return fail(ctx, CF_ERR_COMM, "hipIpcOpenMemHandle on a neighbour's halo mailbox: %s", hipGetErrorString(e));
-    *out = (char*)p;
-    *opened = true;
+    *out = (char*)mapping->get();
     return CF_OK;
 }
 
 int cf_peer_halo_connect(cf_ctx* ctx, const void* south_handle, const void* north_handle, int rank, int nranks) {
     if (!ctx || nranks <= 0 || rank < 0 || rank >= nranks) return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: bad arguments");
-    if (!ctx->peer.mine) return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: call cf_peer_halo_export first");
+    if (!ctx->peer_mine) return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: call cf_peer_halo_export first");
     if ((rank > 0) != (south_handle != nullptr) || (rank < nranks - 1) != (north_handle != nullptr))
         return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: rank %d of %d needs %s south and %s north handle", rank, nranks,
                     rank > 0 ? "a" : "no", rank < nranks - 1 ? "a" : "no");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    CHECK(map_mailbox(ctx, south_handle, &ctx->peer.south, &ctx->peer_south_mapped));
-    CHECK(map_mailbox(ctx, north_handle, &ctx->peer.north, &ctx->peer_north_mapped));
+    CHECK(map_mailbox(ctx, south_handle, &ctx->peer.south, &ctx->peer_south_map));
+    CHECK(map_mailbox(ctx, north_handle, &ctx->peer.north, &ctx->peer_north_map));
     ctx->rank = rank;
     ctx->nranks = nranks;
     ctx->peer_connected = true;
@@ -230,7 +229,7 @@ int cf_halo_exchange_rows_peer(cf_ctx* ctx, double* const* d_fields, int nfields
 
 int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows) {
     ++ctx->peer_seq;  // every rank counts its exchanges: the same number names the same step everywhere
-    HIP_TRY(ctx, launch_peer_halo(ctx->stream, ctx->peer, *F, ctx->grid, rows, ctx->peer_seq, ctx->d_peer_status));
+    HIP_TRY(ctx, launch_peer_halo(ctx->stream, ctx->peer, *F, ctx->grid, rows, ctx->peer_seq, ctx->d_peer_status.get()));
     return CF_OK;
 }
 

@@ -569,6 +569,8 @@ int cf_update_state(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_wei
  * ordered against the context's compute stream with events in both directions: a slot is not overwritten
  * before the interpolations already queued have read it, and an interpolation does not start before the two
  * snapshots it brackets have landed.  Reading the files (NetCDF) stays on the host side of this boundary.
+ * A window outlived by its context may still be destroyed, and cf_window_find / cf_window_host_buffer still answer
+ * (cf_window_wait_slot, _commit, _upload and _source on it fail with CF_ERR_INVALID).
  * ---------------------------------------------------------------------------------------- */
 typedef struct cf_window cf_window;
 int cf_window_create(cf_ctx* ctx, int32_t ns_x, int32_t ns_y, int32_t n_slots, cf_window** out);

@@ -477,3 +477,73 @@ def test_ice_free_cells_zero_mode_changes_nothing_where_there_is_ice():
     for k in ("sensible_heat", "latent_heat", "water_vapor", "x_momentum", "y_momentum"):
         assert np.all(b["ai"][k][inner][water] == 0.0), k
     np.testing.assert_array_equal(b["ai"]["temperature"][inner][water], si["top_temperature"][inner][water])
+
+
+def _lifecycle_cycle():
+    """One context on which every lazily created resource comes to life, destroyed while one child of each kind is alive;
+    returns the net fluxes of its four pipelined steps and the device it ran on."""
+    from coflux.runtime import CofluxError, SnapshotWindow, comm_unique_id
+    nx, ny = 40, 12
+    ctx, states, src, w, _ = _setup(nx, ny)
+    ctx.set_sea_ice_formulation(ic.flux_params(ic.corrected_atmosphere_sea_ice_fluxes()))
+    ctx.set_sea_ice_albedo(ctx.default_sea_ice_albedo_params())
+    salt = ctx.to_device(np.random.default_rng(1).normal(size=ctx.shape) * 1e-6)
+    ctx.normalize_salinity_flux(salt, states[0]["mask"])
+    sets = [ctx.field_set(EXCHANGE_NAMES) for _ in range(2)]
+    fl, net = ctx.field_set(FLUX_NAMES), ctx.field_set(NET_NAMES)
+    ctx.profile_enable(2)
+    ctx.update_state(src, w, states[0], sets[0], fl, net, level1=0, level2=1, time_fraction=0.0)
+    assert ctx.profile_read(1)[1] == 1
+    # children of every kind, used once, closed only after the context
+    avg = ctx.average([net["T"]], [ctx.zeros()])
+    integ = ctx.integrals([("field", net["T"], None, 0.0, 0)], capacity=4)
+    regrid = ctx.regridder(np.array([0, 2]), np.array([0, 1], dtype=np.int32), np.array([0.5, 0.5]), mode="sum")
+    win = SnapshotWindow(ctx, 16, 8, 2)
+    avg.collect(1.0)
+    integ.collect(0.0)
+    regrid.apply([net["T"]])
+    win.upload(0, {v: np.zeros((8, 16), dtype=np.float32) for v in abi.JRA55_VARIABLES})
+    # the auxiliary lane: a requested prefetch of step 0, then four pipelined steps in the C loop
+    ctx.prefetch_atmosphere_state(src, w, sets[0], level1=0, level2=1, time_fraction=0.0)
+    sched = ctx.make_schedule(states, sets, time_fraction_increment=INC, pipeline=True)
+    ctx.time_steps(0, 4, sched, src, w, fl, net)
+    ctx.sync()
+    result = {k: v.clone() for k, v in net.items()}
+    # a prefetch that went out on the main stream is pending when the context moves to a torch side stream
+    ctx.set_option(abi.OPT_MERGED_PREFETCH, 1)
+    ctx.prefetch_atmosphere_state(src, w, sets[1], level1=0, level2=1, time_fraction=0.5)
+    ctx.update_state(src, w, states[0], sets[0], fl, net, level1=0, level2=1, time_fraction=0.25)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(device=ctx.device)
+    with torch.cuda.stream(side):
+        ctx.use_torch_stream()
+        ctx.update_state(src, w, states[1], sets[1], fl, net, level1=0, level2=1, time_fraction=0.5)
+        assert ctx.time_stage(abi.STAGE_UPDATE_STATE, 1, src=src, weights=w, ocean=states[0], atmos=sets[0], fluxes=fl, net=net) >= 0.0
+        assert ctx.time_copy(4096, launches=1) >= 0.0
+        ctx.set_option(abi.OPT_MERGED_PREFETCH, 0)
+        ctx.comm_init(comm_unique_id(), 0, 1)          # one rank: the exchange has no neighbour, the communication lane exists
+        ctx.halo_exchange_rows([states[0][k] for k in ("T", "S", "u", "v")], rows=2)
+        try:
+            ctx.peer_halo_export(4, 2)
+        except CofluxError as e:                        # CF_ERR_COMM: this card has no fine-grained memory to give
+            assert "(-4)" in str(e), e
+        ctx.sync()
+    ctx.close()
+    side.synchronize()
+    for child in (avg, integ, regrid, win):
+        child.close()
+    return result, ctx.device
+
+
+def test_teardown_with_every_lazy_resource_alive_three_cycles():
+    """cf_destroy with the sea-ice buffers, the reduction buffer, the profiler's events, the auxiliary and the communication
+    lane, the RCCL communicator and the peer mailbox all alive, and an averager, an integrator, a regridder and a window
+    that outlive the context: three such lives in one process give the same bits, and the device is usable afterwards."""
+    cycles = [_lifecycle_cycle() for _ in range(3)]
+    results, device = [c[0] for c in cycles], cycles[-1][1]
+    for other in results[1:]:
+        for k in NET_NAMES:
+            assert torch.equal(results[0][k], other[k]), k
+    x = torch.arange(8, dtype=torch.float64, device=device)
+    assert float((x + 1.0).sum()) == 36.0
+    torch.cuda.synchronize(device)

@@ -101,3 +101,26 @@ def test_sliding_window_atmosphere_equals_in_memory_atmosphere(prefetch):
     if prefetch:
         assert windowed._reader is not None
     windowed.close()
+
+
+def test_window_outlived_by_its_context():
+    """A window outlived by its context: every call that needs the context fails, find still answers, destroying it works."""
+    ctx = FluxContext(40, 12, 2, 2, ic.flux_params(), ring=1)
+    win = SnapshotWindow(ctx, 16, 8, 2)
+    snap = {v: np.full((8, 16), 1.0 + k, dtype=np.float32) for k, v in enumerate(abi.JRA55_VARIABLES)}
+    win.upload(0, snap)
+    win.upload(1, snap)
+    ctx.sync()
+    ctx.close()
+    with pytest.raises(CofluxError, match="destroyed"):
+        win.wait_slot(0)
+    with pytest.raises(CofluxError, match="destroyed"):
+        win.commit(0, 2)
+    with pytest.raises(CofluxError, match="destroyed"):
+        win.upload(2, snap)
+    with pytest.raises(CofluxError, match="destroyed"):
+        win.source(0, 1, 0.5)
+    assert win.find(0) == 0 and win.find(1) == 1 and win.find(2) == -1
+    assert win.host_view(1, "tas").shape == (8, 16)
+    win.close()
+    win.close()   # (idempotent)
