@@ -28,6 +28,8 @@ OPT_SOLVER, OPT_TRIP_HINTS, OPT_FUSED_NET, OPT_ICE_ORBIT_SHORTCUT, OPT_MERGED_PR
 OPT_INTERP_TILE_CAP, OPT_AO_CHUNK = 1, 4   # experiment options: the library accepts them only with COFLUX_EXPERIMENTS=1 in the environment
 OPT_INTERP_TILE_ROWS = 15                  # experiment option too: rows per wave tile of the tiled interpolation (0 automatic, 1, 2, 4)
 OPT_SOLVER_PATH, OPT_CERTIFIED_BUDGET, OPT_ICE_FREE_CELLS, OPT_LATENCY_LAYOUT, OPT_HALO_IN_SOLVER_LAUNCH = 10, 11, 12, 13, 14
+OPT_LAND_ZEROS = 2                         # who writes the land zeros: 0 every launch, 1 automatic (default), 2 never (experiment value)
+LAND_ZEROS_EVERY_LAUNCH, LAND_ZEROS_AUTO, LAND_ZEROS_NEVER = 0, 1, 2
 ICE_FREE_ITERATE, ICE_FREE_ZERO = 0, 1
 PIPELINE_WITHIN_CALL, PIPELINE_CONTINUING = 1, 2   # cf_run_schedule.pipeline
 AVERAGE_MAX_FIELDS = 16                            # fields of one time averager (cf_average_create)
@@ -246,7 +248,7 @@ EXPORTED_SYMBOLS = (
     "cf_interpolate_land_freshwater", "cf_set_land_freshwater", "cf_materialize_salinity_restoring",
     "cf_window_create", "cf_window_destroy", "cf_window_host_buffer", "cf_window_wait_slot", "cf_window_commit",
     "cf_window_upload", "cf_window_find", "cf_window_source",
-    "cf_ensure_chunk_table", "cf_debug_chunk_table", "cf_debug_interp_grid", "cf_solver_path", "cf_solver_iteration_path", "cf_solver_latency_layout", "cf_comm_count", "cf_build_stamp", "cf_discard_prefetched_atmosphere_state",
+    "cf_ensure_chunk_table", "cf_debug_chunk_table", "cf_debug_interp_grid", "cf_debug_land_zero_launches", "cf_solver_path", "cf_solver_iteration_path", "cf_solver_latency_layout", "cf_comm_count", "cf_build_stamp", "cf_discard_prefetched_atmosphere_state",
     "cf_average_create", "cf_average_destroy", "cf_average_reset", "cf_average_collect", "cf_average_weight", "cf_attach_average",
     "cf_average_create_derived",
     "cf_integrals_create", "cf_integrals_destroy", "cf_integrals_collect", "cf_integrals_count", "cf_integrals_read",
@@ -368,6 +370,7 @@ def load_library(path=None):
     lib.cf_ensure_chunk_table.argtypes = [vp, vp]
     lib.cf_debug_chunk_table.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.cf_debug_interp_grid.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.cf_debug_land_zero_launches.argtypes = [vp, C.POINTER(C.c_int)]
     lib.cf_solver_path.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.cf_default_sea_ice_albedo_params.argtypes = [C.POINTER(SeaIceAlbedoParams)]
     lib.cf_set_sea_ice_albedo.argtypes = [vp, C.POINTER(SeaIceAlbedoParams)]

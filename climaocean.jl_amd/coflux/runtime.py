@@ -325,6 +325,13 @@ class FluxContext:
         self._check(self.lib.cf_debug_interp_grid(self._h, C.byref(rows), C.byref(blocks)), "cf_debug_interp_grid")
         return rows.value, blocks.value
 
+    def debug_land_zero_launches(self):
+        """How many ocean-solver launches of the last time_steps call wrote the land zeros (cf_debug_land_zero_launches;
+        abi.OPT_LAND_ZEROS): 1 under the automatic mode, the step count under LAND_ZEROS_EVERY_LAUNCH."""
+        n = C.c_int()
+        self._check(self.lib.cf_debug_land_zero_launches(self._h, C.byref(n)), "cf_debug_land_zero_launches")
+        return n.value
+
     def solver_path(self):
         """(lean_kernel, fused): which kernels cf_update_state launches for the current formulation and options; fused = 0
         three launches, 1 net fluxes in the solver's epilogue, 2 the interpolation in its prologue as well."""

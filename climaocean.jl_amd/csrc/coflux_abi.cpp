@@ -576,6 +576,12 @@ int cf_set_option(cf_ctx* ctx, int option, int value) {
             ctx->launch.ao_chunk = value;
             ctx->chunk_valid = false;
             return CF_OK;
+        case CF_OPT_LAND_ZEROS:
+            if (value < 0 || value > 2) return fail(ctx, CF_ERR_INVALID, "land zeros %d: 0 (every launch), 1 (automatic: the first step of a cf_time_steps call), 2 (never)", value);
+            if (value == 2 && !experiments_enabled())
+                return fail(ctx, CF_ERR_INVALID, "CF_OPT_LAND_ZEROS = 2 is an experiment value: start the process with COFLUX_EXPERIMENTS=1");
+            ctx->land_zeros = value;
+            return CF_OK;
         default: return fail(ctx, CF_ERR_INVALID, "unknown option %d", option);
     }
 }
@@ -737,6 +743,13 @@ int cf_debug_chunk_table(cf_ctx* ctx, int* begins, int* wet_counts, int capacity
         HIP_TRY(ctx, hipMemcpyAsync(info.data(), ctx->wet.d_lean_info.get(), sizeof(int) * info.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int c = 0; c < n; ++c) wet_counts[c] = info[(size_t)4 * c];
+    return CF_OK;
+}
+
+// self-test hook: the land-zero bookkeeping of the last cf_time_steps call (tests/test_land_zeros.py)
+int cf_debug_land_zero_launches(cf_ctx* ctx, int* launches) {
+    if (!ctx || !launches) return fail(ctx, CF_ERR_INVALID, "cf_debug_land_zero_launches: bad arguments");
+    *launches = ctx->step_loop.zero_launches;
     return CF_OK;
 }
 
@@ -928,22 +941,33 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
             CHECK(cf_peer_halo_launch_now(ctx, &ctx->halo_request.F, ctx->halo_request.rows));
         }
     }
+    // CF_OPT_LAND_ZEROS: whether this step's solver and face-stress launches leave the land cells alone.  Automatic: only a step
+    // of an open cf_time_steps loop whose PREVIOUS step went the same way — the same kernel family (its land footprint: every land
+    // cell of the window, whatever the chunk plan or the tail) under the same fuse decision (the net fields on interior land)
+    // with the ocean solve in the same launch.  Tail or no tail is not part of the way: the body and its land are the same.
+    // The LIBM solver does not know the switch.  `L` is this step's copy of the launch configuration: nothing stays armed.
+    const unsigned way = 1u | (fuse ? 2u : 0u) | (ride ? 4u : 0u) | ((unsigned)ctx->fast.specialization << 3);
+    const bool knows = ctx->launch.solver == CF_SOLVER_TABLES;
+    const bool keep_land = knows && (ctx->land_zeros == 2 || (ctx->land_zeros == 1 && ctx->step_loop.open && ctx->step_loop.last_way == way));
+    LaunchCfg L = ctx->launch;
+    L.keep_land = keep_land ? 1 : 0;
     if (ride) {
-        HIP_TRY(ctx, make_ocean_rider(ctx->launch, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net, ctx->d_land_freshwater,
+        HIP_TRY(ctx, make_ocean_rider(L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net, ctx->d_land_freshwater,
                                       ocean_rider));
     } else if (tail) {
         int rows = 4, blocks = 1;
-        interpolate_grid(ctx->launch, ctx->grid, &rows, &blocks);
+        interpolate_grid(L, ctx->grid, &rows, &blocks);
         if (tail_lean)
-            HIP_TRY(ctx, launch_ao_fluxes_lean(ctx->stream, ctx->launch, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
+            HIP_TRY(ctx, launch_ao_fluxes_lean(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
                                                ctx->d_land_freshwater, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out, rows, blocks, halo));
         else
-            HIP_TRY(ctx, launch_ly_fluxes_with_tail(ctx->stream, ctx->launch, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
+            HIP_TRY(ctx, launch_ly_fluxes_with_tail(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
                                                     ctx->d_land_freshwater, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out, rows, blocks));
         CHECK(deferred_went_out_on_main(ctx));
     } else
-    HIP_TRY(ctx, launch_ao_fluxes(ctx->stream, ctx->launch, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes,
+    HIP_TRY(ctx, launch_ao_fluxes(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes,
                                   fuse ? ice : nullptr, fuse ? net : nullptr, ctx->d_land_freshwater));
+    if (ctx->step_loop.open && !keep_land) ++ctx->step_loop.zero_launches;
     // A requested next-step interpolation (cf_prefetch_atmosphere_state).  CF_OPT_MERGED_PREFETCH: it rides in THIS step's
     // face-stress launch on the main stream — two independent memory-bound kernels, one launch boundary fewer (on a
     // latitude slab a boundary is a tenth of the step).  Otherwise it goes out on the auxiliary stream right behind the
@@ -959,7 +983,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     } else if (fuse && hold_tail_work) {
         if (stress_held) *stress_held = true;   // (the caller's next launch carries them)
     } else if (fuse)
-        HIP_TRY(ctx, launch_net_stress(ctx->stream, ctx->dev, ctx->grid, ocean, fluxes, ice, net));
+        HIP_TRY(ctx, launch_net_stress(ctx->stream, ctx->dev, ctx->grid, ocean, fluxes, ice, net, keep_land));
     else
         HIP_TRY(ctx, launch_net_fluxes(ctx->stream, ctx->dev, ctx->grid, ocean, atmos, fluxes, ice, w, net, ctx->d_land_freshwater));
     if (rec) {
@@ -972,6 +996,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
         HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out));
         CHECK(deferred_went_out_on_main(ctx));
     }
+    if (ctx->step_loop.open) ctx->step_loop.last_way = way;   // (every launch of the step is queued: the next step may rely on its land)
     return CF_OK;
 }
 

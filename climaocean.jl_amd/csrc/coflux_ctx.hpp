@@ -25,6 +25,12 @@
 
 using namespace coflux;
 
+// CF_OPT_LAND_ZEROS of a fresh context: 1 = automatic; an A/B build sets 0 (tools/make_variant.sh everystep -DCF_LAND_ZEROS_DEFAULT=0)
+#ifndef CF_LAND_ZEROS_DEFAULT
+#define CF_LAND_ZEROS_DEFAULT 1
+#endif
+static_assert(CF_LAND_ZEROS_DEFAULT == 0 || CF_LAND_ZEROS_DEFAULT == 1, "the experiment value is not a default");
+
 struct RcclApi {
     void* handle = nullptr;
     ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
@@ -157,6 +163,16 @@ struct cf_ctx {
         PeerFields F{};
         int rows = 0;
     } halo_request;
+    // CF_OPT_LAND_ZEROS: which launches write zero_interface_state into the land cells.  cf_time_steps opens `step_loop` for the
+    // length of one call (LandZeroScope: closed on every way out, so that a failed call cannot leave it open for a later
+    // cf_update_state of the host); cf_update_state marks a step "land kept" only inside an open loop whose previous step went the
+    // way `last_way` says
+    int land_zeros = CF_LAND_ZEROS_DEFAULT;
+    struct StepLoop {
+        bool open = false;
+        unsigned last_way = 0;     // 0: no step of this call yet; else 1 | fused << 1 | kernel family << 2 of the previous step's solver launch
+        int zero_launches = 0;     // solver launches of the last call that wrote the land zeros (cf_debug_land_zero_launches)
+    } step_loop;
     // RCCL
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -173,6 +189,21 @@ struct cf_ctx {
     cf_integrals* integrals = nullptr;
     int32_t integrals_stride = 1;
     double integrals_time_origin = 0.0, integrals_step_seconds = 0.0;
+};
+
+// One cf_time_steps call's step loop, as CF_OPT_LAND_ZEROS sees it: open for exactly the scope's lifetime
+struct LandZeroScope {
+    cf_ctx* ctx;
+    explicit LandZeroScope(cf_ctx* c) : ctx(c) {
+        ctx->step_loop = cf_ctx::StepLoop{};
+        ctx->step_loop.open = true;
+    }
+    ~LandZeroScope() {
+        ctx->step_loop.open = false;   // (zero_launches stays: cf_debug_land_zero_launches reads the last call's)
+        ctx->step_loop.last_way = 0;
+    }
+    LandZeroScope(const LandZeroScope&) = delete;
+    LandZeroScope& operator=(const LandZeroScope&) = delete;
 };
 
 struct cf_average : cf_child {

@@ -41,6 +41,8 @@ struct LaunchCfg {
     int lean_hints;             // 1: the lean ocean kernel re-orders its lists by trip count at the end of every call
     int certified;              // CF_OPT_SOLVER_PATH: 1 = the certified reduced-iteration solve wherever it applies (lean_certified_applies)
     int latency_layout;         // CF_OPT_LATENCY_LAYOUT: 0 never, 1 automatic (COARE profile on chunk plans of at most two workgroups per CU), 2 always
+    int keep_land;              // CF_OPT_LAND_ZEROS, per launch: 1 = the ocean solve leaves the land of a chunk whose list is valid as it is.  Never
+                                // set in a context's own copy: cf_update_state sets it in the copy it hands to the launches of a marked step
 };
 
 // the exact path's kernels for one or two waves per SIMD (coflux_solver_slab.hip) carry this launch
@@ -57,7 +59,8 @@ hipError_t launch_ao_fluxes(hipStream_t st, const LaunchCfg& L, const DevParams&
                             const cf_interface_fluxes* f, const cf_sea_ice_fields* ice = nullptr,
                             const cf_net_ocean_fluxes* net = nullptr, const double* land = nullptr);
 hipError_t launch_net_stress(hipStream_t st, const DevParams& P, const GridDesc& G, const cf_ocean_surface* o,
-                             const cf_interface_fluxes* f, const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* n);
+                             const cf_interface_fluxes* f, const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* n,
+                             bool keep_land = false);   // keep_land: land cells are neither read nor written (CF_OPT_LAND_ZEROS)
 hipError_t build_wet_lists(hipStream_t st, const DevParams* d_params, const GridDesc& G, const void* mask, int nchunks,
                            const int* d_begins, uint32_t* d_wet_pos, uint8_t* d_trip, int* d_scratch, int* overflow_out);
 hipError_t build_lean_lists(hipStream_t st, int nchunks, const uint32_t* d_wet_pos, const int* d_begins, uint32_t* d_sorted, int* d_info);

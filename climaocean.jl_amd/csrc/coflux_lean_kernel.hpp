@@ -39,6 +39,8 @@ struct LeanArgs {
     long long tail_blocks, tail_rows, tail_cap;
     long long tail_pos;       // TAIL: index of the first interpolation workgroup in dispatch order (n_chunks: behind every solver workgroup)
     HaloRider H;              // HALO: the peer-direct halo rows of this step as rider workgroups at the head of the launch
+    long long keep_land;      // CF_OPT_LAND_ZEROS: != 0 = the land of a range whose list is valid keeps what it holds (the zeros of an
+                              // earlier step of the same cf_time_steps call); 0, what a launcher that does not know it leaves: written
 };
 typedef const LeanArgs __attribute__((address_space(4)))* LeanArgsPtr;
 
@@ -231,6 +233,10 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
     const int mask_kind = (mask == nullptr) ? CF_MASK_NONE : (int)K->mask_kind;
     const double z_surface = K->z_surface;
     const double T_offset = K->T_offset;
+    // (read here, with the start phase's other scalars: a load of its own at either place it is used puts a wait for the scalar
+    // cache into every workgroup's start phase — the every-step build measured 0.6 µs per step above the parent commit that
+    // way and 0.3 µs this way, profiles/land_zeros_ab.jsonl; it is dead once the batches begin)
+    const bool keep_land = K->keep_land != 0;
     const bool sorting = !CERT && use_static && K->sort_enabled != 0;
     // sort_enabled = number of WINDOWS the chunk's list is sorted in: 1 = the whole chunk by trip count (64 bins);
     // 4 = each quarter of the list separately (16 one-count bins each): a batch's cells then stay within a quarter of the
@@ -283,6 +289,7 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
         }
     }
     // a range longer than LAND_UNROLL strips (a chunk that is mostly land): the rest the plain way, zeros at once
+    // (keep_land: none here — should the fingerprint then not match, the classification below zeroes the whole range's land)
     for (int idx = range_begin + tid + LAND_UNROLL * BLOCK; idx < range_end; idx += BLOCK) {
         const int jj = row_of(idx, wx, wx_rcp);
         const size_t k = cell_index(G, idx - jj * wx - G.ring, jj - G.ring);
@@ -291,7 +298,7 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
         if (w) {
             hx ^= lean_mix((unsigned)idx);
             hy += lean_sum((unsigned)idx);
-        } else {
+        } else if (!keep_land) {
             lean_zero_cell<FUSE>(L, T_offset, G, opaque(K), k, idx - jj * wx - G.ring, jj - G.ring);
         }
     }
@@ -324,8 +331,9 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
         if (sort_windows > 1 && nwet > 0)  // windows of whole batches
             inv_window = 1.0f / (float)(((nwet + sort_windows * 64 - 1) / (sort_windows * 64)) * 64);
     }
-    if (have_list && land) {
+    if (have_list && land && !keep_land) {
         // zero_interface_state of the range's land: nothing waits for these stores but the first batch's loads
+        // (keep_land, a uniform branch: the land already holds them — a later step of a cf_time_steps call)
         LeanArgsPtr Kz = opaque(K);
 #pragma unroll
         for (int n = 0; n < LAND_UNROLL; ++n)
@@ -339,7 +347,8 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
     int begin = range_begin, end = range_end;
     for (;;) {
         if (!have_list) {
-            // ---- no (valid) sorted list: classify the piece [begin, end), zero its land (every call, unsorted) ---------
+            // ---- no (valid) sorted list: classify the piece [begin, end), zero its land (every call, unsorted; keep_land or
+            // not: a stale list is a question of time, never of what the land holds) ---------
             for (int base = begin; base < end; base += BLOCK) {
                 const int idx = base + tid;
                 bool wet = false;

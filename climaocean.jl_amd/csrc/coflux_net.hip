@@ -46,7 +46,8 @@ __global__ __launch_bounds__(NET_BLOCK) void net_flux_kernel(DevParams P, GridDe
 // cell-local fluxes (cf_update_state's fused path).  Reads ρτ of the cell and of its west / south neighbour.
 __global__ __launch_bounds__(NET_BLOCK) void net_stress_kernel(DevParams P, GridDesc G, const void* mask,
                                                                const double* __restrict__ rtx, const double* __restrict__ rty,
-                                                               IceIn I, double* __restrict__ tau_x, double* __restrict__ tau_y) {
+                                                               IceIn I, double* __restrict__ tau_x, double* __restrict__ tau_y,
+                                                               int keep_land) {
     const int ncells = G.nx * G.ny;
     const int idx = (int)blockIdx.x * NET_BLOCK + (int)threadIdx.x;
     if (idx >= ncells) return;
@@ -54,6 +55,8 @@ __global__ __launch_bounds__(NET_BLOCK) void net_stress_kernel(DevParams P, Grid
     const size_t k = cell_index(G, idx - j * G.nx, j);
     const size_t kw = k - 1, ks = k - (size_t)G.sj;
     const bool wet = cell_is_wet(P, mask, k);
+    // CF_OPT_LAND_ZEROS: land already holds its two zeros (a later step of a cf_time_steps call) — nothing is loaded or stored for it
+    if (keep_land && !wet) return;
     const double aice = I.conc ? I.conc[k] : 0.0;
     const double tx = net_face_stress(P, rtx[kw], rtx[k], I.conc ? I.conc[kw] : 0.0, aice, I.txio ? I.txio[k] : 0.0);
     const double ty = net_face_stress(P, rty[ks], rty[k], I.conc ? I.conc[ks] : 0.0, aice, I.tyio ? I.tyio[k] : 0.0);
@@ -62,12 +65,12 @@ __global__ __launch_bounds__(NET_BLOCK) void net_stress_kernel(DevParams P, Grid
 }
 
 hipError_t launch_net_stress(hipStream_t st, const DevParams& P, const GridDesc& G, const cf_ocean_surface* o,
-                             const cf_interface_fluxes* f, const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* n) {
+                             const cf_interface_fluxes* f, const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* n, bool keep_land) {
     IceIn I{};
     if (ice) I = IceIn{ice->concentration, ice->interface_heat, ice->salt_flux, ice->x_stress, ice->y_stress, nullptr};
     const int ncells = G.nx * G.ny;
     hipLaunchKernelGGL(net_stress_kernel, dim3((ncells + NET_BLOCK - 1) / NET_BLOCK), dim3(NET_BLOCK), 0, st, P, G, o->mask,
-                       f->x_momentum, f->y_momentum, I, n->u, n->v);
+                       f->x_momentum, f->y_momentum, I, n->u, n->v, keep_land ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -441,6 +441,7 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
     const int mask_kind = (mask == nullptr) ? CF_MASK_NONE : (int)K->mask_kind;
     const double z_surface = K->z_surface;
     const double T_offset = K->T_offset;
+    const bool keep_land = K->keep_land != 0;   // (with the start phase's other scalars; dead once the batches begin)
     if (use_static) {
         const size_t base = (size_t)chunk * CHUNK + tid;
         const __attribute__((address_space(1))) uint32_t* gpos = (const __attribute__((address_space(1))) uint32_t*)W.pos;
@@ -530,6 +531,7 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
             }
         }
         // a range longer than LAND_UNROLL strips (a chunk that is mostly land): the rest the plain way, zeros at once
+        // (keep_land: none here — should the list then prove stale, the classification below zeroes the whole range's land)
         for (int idx = range_begin + tid + LAND_UNROLL * BLOCK; idx < range_end; idx += BLOCK) {
             const int jj = row_of(idx, wx, wx_rcp);
             const int i = idx - jj * wx - G.ring, j = jj - G.ring;
@@ -539,7 +541,7 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
             if (w) {
                 hx ^= cell_hash_lo((unsigned)idx);
                 hy ^= cell_hash_hi((unsigned)idx);
-            } else {
+            } else if (!keep_land) {
                 SolverArgsPtr Kz = opaque(K);
                 const FluxOut F = kread(&Kz->F);
                 const NetOut N = kread(&Kz->N);
@@ -582,8 +584,8 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
         have_list = (counters[2] | counters[3]) == 0;  // the list is the range's wet set
         if (have_list) {
             // zero_interface_state of the range's land, issued behind the last barrier: nothing waits for these stores
-            // but the first batch's loads, whose latency they share
-            if (land) {
+            // but the first batch's loads, whose latency they share (keep_land: the land already holds them)
+            if (land && !keep_land) {
                 SolverArgsPtr Kz = opaque(K);
                 const FluxOut F = kread(&Kz->F);
                 const NetOut N = kread(&Kz->N);
@@ -893,9 +895,10 @@ static void launch_ao_spec(hipStream_t st, dim3 grid, const LaunchCfg& L, const 
                            const OceanIn& O, const Exchange& E, const FluxOut& F, const IceIn& I, const NetOut& N,
                            double z_surface, long long mask_kind, double T_offset) {
     // (CoefficientBasedFluxes runs a fixed trip count: no hint bytes to read, sort by or write back)
-    const SolverArgs A{C, G, O, E, F, L.d_tables, L.d_params, WetLists{L.d_wet_pos, C.specialization == SOLVER_LY ? nullptr : L.d_trip},
-                       L.d_chunk_begins, I, N, IceStateIn{}, IceParams{},
-                       z_surface, mask_kind, T_offset, row_reciprocal(G.nx + 2 * G.ring)};
+    SolverArgs A{C, G, O, E, F, L.d_tables, L.d_params, WetLists{L.d_wet_pos, C.specialization == SOLVER_LY ? nullptr : L.d_trip},
+                 L.d_chunk_begins, I, N, IceStateIn{}, IceParams{},
+                 z_surface, mask_kind, T_offset, row_reciprocal(G.nx + 2 * G.ring)};
+    A.keep_land = L.keep_land;
 #define CF_LAUNCH(COARE_, SPEC_) \
     hipLaunchKernelGGL((ao_flux_fast_kernel<COARE_, SPEC_, FUSE>), grid, dim3(AO_BLOCK), Geom::LDS_BYTES, st, A)
     // (SOLVER_OCEAN_LEAN never arrives here: launch_ao_fluxes hands it to coflux_solver_lean.hip)
@@ -928,6 +931,7 @@ hipError_t launch_ly_fluxes_with_tail(hipStream_t st, const LaunchCfg& L, const 
     A.tail_blocks = tail_blocks;
     A.tail_rows = tail_rows;
     A.tail_cap = L.interp_cap;
+    A.keep_land = L.keep_land;
     hipLaunchKernelGGL((ao_flux_fast_kernel<true, SOLVER_LY, true, true>), dim3(L.n_chunks + tail_blocks), dim3(AO_BLOCK),
                        Geom::LDS_BYTES, st, A);
     return hipGetLastError();

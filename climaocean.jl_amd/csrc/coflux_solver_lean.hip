@@ -131,6 +131,7 @@ static hipError_t fill_lean_args(const LaunchCfg& L, const DevParams& P, const L
     A.T_offset = P.T_offset;
     A.wx_reciprocal = row_reciprocal(G.nx + 2 * G.ring);
     A.sort_enabled = L.lean_hints;
+    A.keep_land = L.keep_land;
     if (net) {  // the fused form: the epilogue also writes the cell-local net ocean fluxes (constant ocean albedo only)
         A.I = make_ice_in(ice, land);
         A.N = make_net_out(net);

@@ -82,6 +82,7 @@ struct SolverArgs {
     double* tau_x;
     double* tau_y;
     NetIceOut NI;   // the sea-ice interface launch: compute_net_sea_ice_fluxes! in its epilogue
+    long long keep_land;  // CF_OPT_LAND_ZEROS: != 0 = the land of a range whose list is valid keeps what it holds (LeanArgs::keep_land)
 };
 typedef const SolverArgs __attribute__((address_space(4)))* SolverArgsPtr;
 

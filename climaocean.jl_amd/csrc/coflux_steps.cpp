@@ -341,6 +341,9 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
             }
         }
     }
+    // CF_OPT_LAND_ZEROS: the steps below are one loop over fixed outputs, one mask pointer and one chunk table (checked above) —
+    // cf_update_state may leave the land cells to the first of them.  Closed on every way out of this function.
+    const LandZeroScope land_zero_scope(ctx);
     for (int64_t step = first_step; step < first_step + nsteps; ++step) {
         const cf_ocean_surface* o = &S->ocean_states[step % S->n_ocean_states];
         double* rows[4] = {const_cast<double*>(o->T), const_cast<double*>(o->S), const_cast<double*>(o->u),

@@ -150,6 +150,10 @@ solver_latency_layout(b) = (p = Ref{Cint}(0); check(b.ctx, ccall((:cf_solver_lat
 # CF_OPT_HALO_IN_SOLVER_LAUNCH: a step's peer-direct halo rows as rider workgroups of its solver launch (include/coflux.h)
 const CF_OPT_HALO_IN_SOLVER_LAUNCH = Cint(14)
 halo_in_solver_launch!(b, on::Bool) = set_option!(b, CF_OPT_HALO_IN_SOLVER_LAUNCH, on ? 1 : 0)
+# CF_OPT_LAND_ZEROS: 0 every launch writes the land cells' zeros, 1 (default) inside time_steps! only a call's first step does —
+# nothing else may write the flux and net-flux outputs while such a call's work is on the stream (include/coflux.h)
+const CF_OPT_LAND_ZEROS = Cint(2)
+land_zeros!(b, mode::Integer) = set_option!(b, CF_OPT_LAND_ZEROS, mode)
 function peer_halo_stats(b)
     n = Ref{Culonglong}(0); m = Ref{Culonglong}(0)
     check(b.ctx, ccall((:cf_peer_halo_stats, libcoflux), Cint, (Ptr{Cvoid}, Ref{Culonglong}, Ref{Culonglong}), b.ctx, n, m))
@@ -328,6 +332,13 @@ function debug_interp_grid(b)
     rows, blocks = Ref{Cint}(0), Ref{Cint}(0)
     check(b.ctx, ccall((:cf_debug_interp_grid, libcoflux), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}), b.ctx, rows, blocks))
     return Int(rows[]), Int(blocks[])
+end
+
+# self-test hook: how many ocean-solver launches of the last time_steps! call wrote the land zeros (CF_OPT_LAND_ZEROS)
+function debug_land_zero_launches(b)
+    n = Ref{Cint}(0)
+    check(b.ctx, ccall((:cf_debug_land_zero_launches, libcoflux), Cint, (Ptr{Cvoid}, Ref{Cint}), b.ctx, n))
+    return Int(n[])
 end
 
 # ---- run!(simulation) of a prescribed-ocean model inside the library (bench / offline forcing runs) -------------------

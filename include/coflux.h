@@ -43,7 +43,8 @@ extern "C" {
                           * value of cf_sea_ice_params.skin_temperature_scheme that older libraries reject; still 5: surface integrals and
                           * their time series (cf_integrals_*, cf_attach_integrals) are purely additive — no existing struct or
                           * entry point changed, a host finds them by symbol; likewise CF_OPT_INTERP_TILE_ROWS (an experiment option)
-                          * and cf_debug_interp_grid, and the sparse surface operator (cf_regrid_*) */
+                          * and cf_debug_interp_grid, and the sparse surface operator (cf_regrid_*); likewise CF_OPT_LAND_ZEROS and
+                          * cf_debug_land_zero_launches — with them cf_time_steps gained a contract on its outputs, stated there */
 
 /* status codes */
 #define CF_OK 0
@@ -339,14 +340,30 @@ int cf_set_flux_params(cf_ctx* ctx, const cf_flux_params* params);
 #define CF_STREAM_LEGACY ((void*)1) /* == hipStreamLegacy */
 int cf_set_stream(cf_ctx* ctx, void* hip_stream);
 
-/* Options (cf_set_option).  None of them changes what is computed beyond the stated tolerance.  TEN are part of the drop-in
+/* Options (cf_set_option).  None of them changes what is computed beyond the stated tolerance.  ELEVEN are part of the drop-in
  * surface: CF_OPT_SOLVER, _TRIP_HINTS, _FUSED_NET, _ICE_ORBIT_SHORTCUT, _MERGED_PREFETCH, _SOLVER_PATH, _CERTIFIED_BUDGET,
- * _ICE_FREE_CELLS, _LATENCY_LAYOUT, _HALO_IN_SOLVER_LAUNCH.  Three more are EXPERIMENT options, accepted only in a process started with
- * COFLUX_EXPERIMENTS=1 (measurements, and the test-suite's schedule-invariance checks): CF_OPT_INTERP_TILE_CAP, CF_OPT_AO_CHUNK,
- * CF_OPT_INTERP_TILE_ROWS.
- * Numbers 2, 5 and 8 were CF_OPT_MAX_BLOCKS, _PROFILE_STRIDE and _FUSED_INTERP (retired in ABI version 3: cf_set_option
- * answers CF_ERR_INVALID).                                                                                              */
+ * _ICE_FREE_CELLS, _LATENCY_LAYOUT, _HALO_IN_SOLVER_LAUNCH, _LAND_ZEROS.  Three more are EXPERIMENT options, accepted only in a
+ * process started with COFLUX_EXPERIMENTS=1 (measurements, and the test-suite's schedule-invariance checks): CF_OPT_INTERP_TILE_CAP,
+ * CF_OPT_AO_CHUNK, CF_OPT_INTERP_TILE_ROWS (and the value 2 of CF_OPT_LAND_ZEROS).
+ * Numbers 5 and 8 were CF_OPT_PROFILE_STRIDE and _FUSED_INTERP (retired in ABI version 3: cf_set_option answers
+ * CF_ERR_INVALID).  Number 2 was CF_OPT_MAX_BLOCKS until the same version (a host that still means that by it is refused at
+ * cf_create by its abi_version) and is CF_OPT_LAND_ZEROS now.                                                            */
 #define CF_OPT_SOLVER 0           /* CF_SOLVER_*                                                   */
+#define CF_OPT_LAND_ZEROS 2       /* which launches of cf_update_state write zero_interface_state into the LAND cells of the flux and
+                                   * net-flux outputs (six flux fields, `iterations`; J^T, J^S and the radiation diagnostics, τx, τy on
+                                   * interior land): constants that do not depend on the step.
+                                   * 0: every launch.  1 (default): every launch, except inside cf_time_steps, where only the FIRST step of a
+                                   * call writes them — a later step whose solver launch goes the same way (same kernel family, same
+                                   * CF_OPT_FUSED_NET decision) leaves the land cells of its chunks and of the face-stress launch alone:
+                                   * they hold the first step's zeros (the contract at cf_time_steps).  cf_update_state and
+                                   * cf_update_state_sea_ice called by the host always write.  A workgroup whose wet list proves stale (a
+                                   * mask rewritten in place) classifies its range and writes its land whatever this says; launches that
+                                   * do not know the option (CF_SOLVER_LIBM, un-fused net fluxes, the merged stress + interpolation launch,
+                                   * the sea-ice interface launch) write as before.  Same bits on every cell either way
+                                   * (tests/test_land_zeros.py).  2: never, not even the first step — an EXPERIMENT value
+                                   * (COFLUX_EXPERIMENTS=1): one launch then shows what the skipping branch touches; land holds whatever it
+                                   * held.  cf_debug_land_zero_launches counts.  -DCF_LAND_ZEROS_DEFAULT=0 builds a library whose default
+                                   * is 0 (A/B runs).                                                                                     */
 #define CF_OPT_INTERP_TILE_CAP 1  /* EXPERIMENT option.  Source nodes per variable in a wave's LDS JRA55 tile (128; 16…224: 4 waves × 9 variables × cap × 8 B of LDS), or 0:
                                      the LDS-free one-cell-per-lane gather kernel (≤ 56 VGPRs: small enough to run
                                      beside the resident solver workgroups from a second stream)            */
@@ -505,6 +522,10 @@ int cf_debug_chunk_plan(long long total_cost, int cu_count, int forced_wet_per_c
  * its range per call).  Returns CF_ERR_INVALID when no table is valid or `capacity` < n + 1 ints per array (*n_chunks is
  * still set then: retry with n + 1).  Changes no state. */
 int cf_debug_chunk_table(cf_ctx* ctx, int* begins, int* wet_counts, int capacity, int* n_chunks, int* lists_valid);
+/* Self-test hook (host bookkeeping only, launches nothing, changes no state): *launches = how many ocean-solver launches of the
+ * context's LAST cf_time_steps call were told to write the land zeros (CF_OPT_LAND_ZEROS): 1 of n ≥ 1 steps under the
+ * automatic mode, n under 0, 0 under 2 or before any call. */
+int cf_debug_land_zero_launches(cf_ctx* ctx, int* launches);
 /* Self-test hook (host arithmetic only, launches nothing, changes no state): the shape of the tiled interpolation on the
  * context's grid under its current options, wherever it runs (its own launch, the merged stress + interpolation launch, the
  * tail workgroups of a solver launch): *rows = rows of 64 cells per wave tile (1, 2 or 4: automatic by surface size and the
@@ -907,7 +928,13 @@ int cf_fold_north_halo(cf_ctx* ctx, double* const* d_fields, const int* location
  *     must not recommit them in between — cf_window_commit / an upload into a level a pending request reads voids it
  *     silently), and that exchange set (first_step + nsteps) mod 2 is not read after this call's last step: it is
  *     overwritten.  A caller that stops after such a call has one unused interpolation in that set.
- * All launches are stream ordered; nothing synchronises with the host.       */
+ * All launches are stream ordered; nothing synchronises with the host.
+ * Outputs (CF_OPT_LAND_ZEROS = 1, the default): the call's FIRST step writes every cell of `fluxes` and `net` that
+ * cf_update_state writes, land included; later steps of the call write the wet cells and leave the land cells alone — they
+ * hold the first step's zeros, which are what every step would write.  So nothing else may write `fluxes` or `net` while the
+ * call's work is on the stream (reading them, cf_attach_average / _integrals included, is fine), and the wet mask — one
+ * pointer per schedule — is not rewritten in between.  Between two calls anything may happen to them: every call starts over.
+ * CF_OPT_LAND_ZEROS = 0 writes the land at every step.                                                          */
 #define CF_PIPELINE_WITHIN_CALL 1
 #define CF_PIPELINE_CONTINUING 2
 #define CF_HALO_NONE 0
