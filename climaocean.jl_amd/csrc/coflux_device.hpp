@@ -301,6 +301,8 @@ __device__ __forceinline__ CellFluxes solve_cell(const DevParams& P, double ua, 
     R.Qc = -rho_u * A.cp_m * ts;
     R.rho_tau_x = A.rho * tau * du;
     R.rho_tau_y = A.rho * tau * dv;
+    // land is exactly zero, also where its inputs are not finite (0 · NaN)
+    if (zero) R.Fv = R.Qv = R.Qc = R.rho_tau_x = R.rho_tau_y = 0.0;
     R.Ts_ocean = (zero ? 0.0 : Ts) - P.T_offset;
     R.ustar = us;
     R.tstar = ts;

@@ -39,7 +39,7 @@ __device__ __forceinline__ double fsqrt1(double x) {  // x ≥ 0, ≈ 3e-15 rela
     double r = __builtin_amdgcn_rsq(x);
     double g = x * r;
     g = __builtin_fma(__builtin_fma(-g, g, x), 0.5 * r, g);
-    return x > 0.0 ? g : 0.0;
+    return x == 0.0 ? 0.0 : g;  // (not `x > 0 ? g : 0`: a NaN stays NaN — a NaN wind is not a calm cell)
 }
 
 // a / b to ~1 ulp
@@ -57,7 +57,7 @@ __device__ __forceinline__ double fsqrt(double x) {  // x ≥ 0
     h = __builtin_fma(h, e, h);
     double d = __builtin_fma(-g, g, x);
     g = __builtin_fma(d, h, g);
-    return x > 0.0 ? g : 0.0;
+    return x == 0.0 ? 0.0 : g;  // (not `x > 0 ? g : 0`: a NaN stays NaN — a NaN wind is not a calm cell)
 }
 
 // natural log of a positive normal double; `logt` = LDS table of (1/c_k, log c_k)

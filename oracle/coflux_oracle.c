@@ -462,6 +462,8 @@ static cell_result solve_cell(const cf_flux_params* P, double ua, double va, dou
         R.Fv = -rho_a * ustar * qstar;
         R.rho_tau_x = rho_a * taux;
         R.rho_tau_y = rho_a * tauy;
+        if (!wet) /* land is exactly zero, also where its inputs are not finite (0 * NaN) */
+            R.Qv = R.Qc = R.Fv = R.rho_tau_x = R.rho_tau_y = 0.0;
     } else {
         ustar = tstar = qstar = 0.0;
         Ts = 0.0; /* zero_interface_state: T = 0 K */
@@ -652,17 +654,17 @@ int oracle_compute_net_ocean_fluxes(const cf_grid* g, const cf_flux_params* P, c
             double txio = (ice && ice->x_stress) ? ice->x_stress[k] : 0.0;
             double tyio = (ice && ice->y_stress) ? ice->y_stress[k] : 0.0;
 
-            double wetf = wet ? 1.0 : 0.0; /* immersed cells carry zero flux */
-            out->u[k] = wetf * ((1.0 - ax) * txao + ax * txio);
-            out->v[k] = wetf * ((1.0 - ay) * tyao + ay * tyio);
-            out->T[k] = wetf * (JTao + JTio);
+            /* immersed cells carry zero flux: a select, so that a land cell is exactly zero whatever its inputs */
+            out->u[k] = wet ? ((1.0 - ax) * txao + ax * txio) : 0.0;
+            out->v[k] = wet ? ((1.0 - ay) * tyao + ay * tyio) : 0.0;
+            out->T[k] = wet ? (JTao + JTio) : 0.0;
             double SFl = g_land_freshwater ? -g_land_freshwater[k] * rho_f_inv : 0.0; /* rivers + calving, not ice-masked */
             double SFls = (So < P->ocean_minimum_salinity && SFl < 0.0) ? 0.0 : SFl;
-            out->S[k] = wetf * ((1.0 - aice) * JSao + Jsio + (-So * SFls));
-            if (out->shortwave_surface_flux) out->shortwave_surface_flux[k] = wetf * Qts * rho_o_inv / c_o;
-            if (out->upwelling_longwave) out->upwelling_longwave[k] = wetf * Qu;
-            if (out->downwelling_longwave) out->downwelling_longwave[k] = wetf * (-Qal);
-            if (out->downwelling_shortwave) out->downwelling_shortwave[k] = wetf * (-Qts);
+            out->S[k] = wet ? ((1.0 - aice) * JSao + Jsio + (-So * SFls)) : 0.0;
+            if (out->shortwave_surface_flux) out->shortwave_surface_flux[k] = wet ? Qts * rho_o_inv / c_o : 0.0;
+            if (out->upwelling_longwave) out->upwelling_longwave[k] = wet ? Qu : 0.0;
+            if (out->downwelling_longwave) out->downwelling_longwave[k] = wet ? (-Qal) : 0.0;
+            if (out->downwelling_shortwave) out->downwelling_shortwave[k] = wet ? (-Qts) : 0.0;
         }
     }
     return 0;
