@@ -6,6 +6,8 @@ the value the library reports and that every declared symbol is exported.
 import ctypes as C
 import os
 
+import numpy as np
+
 ABI_VERSION = 5   # 5: SKIN_LINEARISED
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
@@ -39,6 +41,8 @@ DERIVED_MAX_SOURCES = 16                           # distinct source arrays of o
 TERM_AT_CENTERS = 1                                # cf_average_term.flags (EAST / NORTH)
 INTEGRALS_MAX_ENTRIES, INTEGRALS_MAX_FIELDS = 32, 32   # entries / distinct arrays of one surface integrator (cf_integrals_create)
 INTEGRAND_ONE, INTEGRAND_FIELD, INTEGRAND_PRODUCT, INTEGRAND_ABOVE = 0, 1, 2, 3
+MONITOR_MAX_ENTRIES = 16                             # entries of one surface monitor (cf_monitor_create)
+MONITOR_VALUE, MONITOR_ABS = 0, 1                    # cf_monitor_entry.kind: y = x | y = |x|
 REGRID_MAX_FIELDS = 16                               # fields of one apply of a surface regridder (cf_regrid_apply)
 REGRID_MEAN, REGRID_SUM = 0, 1
 SOLVER_PATH_EXACT, SOLVER_PATH_CERTIFIED = 0, 1      # how the Monin–Obukhov fixed point is reached (include/coflux.h)
@@ -224,6 +228,26 @@ class IntegralsDesc(C.Structure):
                 ("entries", IntegralEntry * INTEGRALS_MAX_ENTRIES)]
 
 
+class MonitorEntry(C.Structure):
+    _fields_ = [("a", C.c_void_p), ("kind", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MonitorDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_entries", C.c_int32), ("mask", C.c_void_p), ("first_cell", C.c_int64),
+                ("max_workgroups", C.c_int32), ("reserved", C.c_int32), ("entries", MonitorEntry * MONITOR_MAX_ENTRIES)]
+
+
+class MonitorValue(C.Structure):
+    _fields_ = [("minimum", C.c_double), ("maximum", C.c_double), ("argmin", C.c_int64), ("argmax", C.c_int64),
+                ("nan_count", C.c_int64), ("inf_count", C.c_int64), ("first_nonfinite", C.c_int64), ("hash", C.c_uint64)]
+
+
+# cf_monitor_value as a numpy record: cf_monitor_read fills an array [n, n_entries] of these
+MONITOR_VALUE_DTYPE = np.dtype([("minimum", "<f8"), ("maximum", "<f8"), ("argmin", "<i8"), ("argmax", "<i8"), ("nan_count", "<i8"),
+                                ("inf_count", "<i8"), ("first_nonfinite", "<i8"), ("hash", "<u8")])
+assert MONITOR_VALUE_DTYPE.itemsize == C.sizeof(MonitorValue) == 64
+
+
 class RegridDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("mode", C.c_int32), ("n_rows", C.c_int64), ("nnz", C.c_int64),
                 ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("weight", C.c_void_p), ("mask", C.c_void_p),
@@ -253,6 +277,8 @@ EXPORTED_SYMBOLS = (
     "cf_average_create_derived",
     "cf_integrals_create", "cf_integrals_destroy", "cf_integrals_collect", "cf_integrals_count", "cf_integrals_read",
     "cf_integrals_reset", "cf_attach_integrals",
+    "cf_monitor_create", "cf_monitor_destroy", "cf_monitor_collect", "cf_monitor_count", "cf_monitor_read", "cf_monitor_status",
+    "cf_monitor_reset", "cf_attach_monitor",
     "cf_regrid_create", "cf_regrid_destroy", "cf_regrid_apply",
 )
 
@@ -404,6 +430,14 @@ def load_library(path=None):
     lib.cf_integrals_read.argtypes = [vp, C.c_int64, C.c_int64, c_double_p, c_double_p]
     lib.cf_integrals_reset.argtypes = [vp]
     lib.cf_attach_integrals.argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double]
+    lib.cf_monitor_create.argtypes = [vp, C.POINTER(MonitorDesc), C.c_int32, C.POINTER(vp)]
+    lib.cf_monitor_destroy.argtypes = [vp]
+    lib.cf_monitor_collect.argtypes = [vp, C.c_double]
+    lib.cf_monitor_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.cf_monitor_read.argtypes = [vp, C.c_int64, C.c_int64, vp, c_double_p]
+    lib.cf_monitor_status.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]
+    lib.cf_monitor_reset.argtypes = [vp]
+    lib.cf_attach_monitor.argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double]
     lib.cf_regrid_create.argtypes = [vp, C.POINTER(RegridDesc), C.POINTER(vp)]
     lib.cf_regrid_destroy.argtypes = [vp]
     lib.cf_regrid_apply.argtypes = [vp, C.c_int32, C.POINTER(vp), C.POINTER(vp), vp]

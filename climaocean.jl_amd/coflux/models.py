@@ -19,6 +19,8 @@ them (model.interfaces.net_fluxes.ocean.{u,v,T,S}, omip_diagnostics.jl:77-80).
 The atmosphere holds a window of snapshots in HBM filled from a provider: synthetic in tests/bench, or the raw
 Float32 plane files of coflux/jra55.py (`omip_forcing`; NetCDF decoding itself is not possible in this image).
 """
+import logging
+import time
 from dataclasses import dataclass, field
 from types import SimpleNamespace
 from typing import Optional
@@ -664,20 +666,44 @@ class Simulation:
     stop_time: float = float("inf")
     stop_iteration: int = 2 ** 62
     output_writers: dict = field(default_factory=dict)   # simulation.output_writers[:surface] = … (omip_diagnostics.jl:152-158)
+    callbacks: dict = field(default_factory=dict)        # name → Callback: add_callback!(simulation, f, schedule)
+    running: bool = True                                 # a callback stops run! by setting it False (NaNChecker does)
+
+
+@dataclass
+class Callback:
+    func: object       # func(simulation)
+    schedule: object   # .actuate(iteration)
+
+
+def add_callback(simulation, callback, schedule=None, name=None):
+    """add_callback!(simulation, callback, schedule = IterationInterval(1); name): run! calls callback(simulation) after the
+    output writers of every iteration at which `schedule` actuates (omip_simulation.jl:392)."""
+    schedule = IterationInterval(schedule) if isinstance(schedule, int) else (schedule or IterationInterval(1))
+    name = name or f"callback{len(simulation.callbacks) + 1}"
+    simulation.callbacks[name] = Callback(callback, schedule)
+    return name
 
 
 def run(simulation):
-    """run!(simulation) — README.md:77.  After every time_step! each of `simulation.output_writers` is given the clock."""
+    """run!(simulation) — README.md:77.  After every time_step! each of `simulation.output_writers` is given the clock, then
+    each of `simulation.callbacks` whose schedule actuates is called; the loop ends early when one of them clears
+    `simulation.running`."""
     m = simulation.model
     writers = list(simulation.output_writers.values())
+    callbacks = list(simulation.callbacks.values())
     for writer in writers:
         writer.initialize(simulation)
     m._pipeline_dt = simulation.dt   # (update_state requests every next atmosphere state: see there)
+    simulation.running = True
     try:
-        while m.clock.time < simulation.stop_time and m.clock.iteration < simulation.stop_iteration:
+        while simulation.running and m.clock.time < simulation.stop_time and m.clock.iteration < simulation.stop_iteration:
             time_step(m, simulation.dt)
             for writer in writers:
                 writer.write(m.clock)
+            for cb in callbacks:
+                if cb.schedule.actuate(m.clock.iteration):
+                    cb.func(simulation)
     finally:
         m._pipeline_dt = None
         itf = m.interfaces
@@ -1132,6 +1158,234 @@ def surface_global_means(model, **kw):
     net, ao = itf.net_fluxes._ocean_fields, itf.atmosphere_ocean_interface._fields
     fields = dict(hfds=net["T"], wfo=net["S"], hfss=ao["sensible_heat"], hfls=ao["latent_heat"], tos=st["T"], sos=st["S"])
     return SurfaceIntegrals(model, {name: ("mean", f, None, 0.0, REGION_GLOBAL) for name, f in fields.items()}, **kw)
+
+
+# ---------------------------------------------------------------------------------------------
+# extrema, non-finite counts and state hashes on the device (cf_monitor_*): the progress callbacks and the NaN checker
+# ---------------------------------------------------------------------------------------------
+MONITOR_COLUMNS = ("min", "max", "argmin", "argmax", "nan_count", "inf_count", "first_nonfinite", "hash")
+_log = logging.getLogger("coflux")
+
+
+def _model_monitor(model, fields, capacity):
+    """A SurfaceMonitor over `fields` (name → field or (field, kind)) of `model`, under its wet mask."""
+    ctx = model.interfaces.context
+    mask = model.ocean.model.wet_mask if ctx.params.mask_kind == abi.MASK_U8 else None
+    return ctx.monitor(list(fields.values()), mask=mask, capacity=capacity)
+
+
+def _cell(c, nx):
+    """(j, i) of the interior cell numbered c = j·nx + i; (−1, −1) for none"""
+    return (int(c) // nx, int(c) % nx) if c >= 0 else (-1, -1)
+
+
+class SurfaceExtrema:
+    """An output writer of extrema, non-finite counts and hashes: SurfaceExtrema(model, outputs; schedule = IterationInterval(1)).
+    `outputs`: name → field or (field, "value" | "abs").  Every collection is one record on the device (cf_monitor_collect: no
+    host synchronisation); series() reads them.  A full device series is moved to the host and started again, so `capacity`
+    bounds memory, not the length of a run."""
+
+    def __init__(self, model, outputs, schedule=None, capacity=4096):
+        self.model, self.names = model, list(outputs)
+        self.schedule = IterationInterval(schedule) if isinstance(schedule, int) else (schedule or IterationInterval(1))
+        self.nx = model.ocean.grid.size[0]
+        self.monitor = _model_monitor(model, outputs, capacity)
+        self._values, self._times = [], []
+
+    def initialize(self, simulation):
+        pass
+
+    def _drain(self):
+        values, times = self.monitor.read()
+        if len(times):
+            self._values.append(values)
+            self._times.append(times)
+            self.monitor.reset()
+
+    def write(self, clock):
+        if not self.schedule.actuate(clock.iteration):
+            return
+        if self.monitor.count() == self.monitor.capacity:
+            self._drain()
+        self.monitor.collect(clock.time)
+
+    def records(self):
+        """(values[n, n_entries] of abi.MONITOR_VALUE_DTYPE, times[n]): every record so far, in the order of `names`."""
+        self._drain()
+        if not self._times:
+            return np.zeros((0, len(self.names)), dtype=abi.MONITOR_VALUE_DTYPE), np.zeros(0)
+        self._values, self._times = [np.concatenate(self._values)], [np.concatenate(self._times)]
+        return self._values[0], self._times[0]
+
+    @property
+    def times(self):
+        return self.records()[1]
+
+    def series(self):
+        """{name: {"min", "max", "argmin", "argmax", "nan_count", "inf_count", "first_nonfinite", "hash"}}: arrays of n records;
+        the three indices are (j, i) pairs, (−1, −1) where there is none."""
+        values, _ = self.records()
+        out = {}
+        for k, name in enumerate(self.names):
+            v = values[:, k]
+            pairs = lambda c: np.array([_cell(x, self.nx) for x in c], dtype=np.int64).reshape(len(c), 2)  # noqa: E731
+            out[name] = {"min": v["minimum"].copy(), "max": v["maximum"].copy(), "argmin": pairs(v["argmin"]), "argmax": pairs(v["argmax"]),
+                         "nan_count": v["nan_count"].copy(), "inf_count": v["inf_count"].copy(),
+                         "first_nonfinite": pairs(v["first_nonfinite"]), "hash": v["hash"].copy()}
+        return out
+
+    def close(self):
+        self.monitor.close()
+
+
+def prettytime(t):
+    """Oceananigans.Utils.prettytime: the largest unit that keeps the value ≥ 1, an integer printed as one, else three decimals."""
+    if t == 0:
+        return "0 seconds"
+    for unit, name in ((365 * days, "year"), (days, "day"), (hours, "hour"), (minutes, "minute"), (1.0, "second"), (1e-3, "ms"),
+                       (1e-6, "μs"), (1e-9, "ns")):
+        if abs(t) >= unit or unit == 1e-9:
+            value = t / unit
+            break
+    if unit >= 1.0 and value != 1:
+        name += "s"
+    return f"{int(value)} {name}" if float(value).is_integer() else f"{value:.3f} {name}"
+
+
+def _julia(fmt, x):
+    """@sprintf(fmt, x) of a Float64: Julia prints NaN, Inf and -Inf where C prints nan, inf and -inf"""
+    return "NaN" if x != x else ("Inf" if x == float("inf") else ("-Inf" if x == -float("inf") else fmt % x))
+
+
+class Progress:
+    """ClimaOcean.Progress (src/ClimaOcean.jl:48-88) as a callback of run!: add_callback(simulation, Progress(), schedule).
+    One monitor over hᵢ and ℵ (when the model has sea ice with a thickness) and T, S, u, v is collected once per call — one
+    pass on the device, 64 bytes per field read back; no field is copied to the host.  The message is the reference's, format
+    strings included; it is logged (logger "coflux", INFO), kept in `message` and returned.  maximum and minimum follow Julia:
+    NaN when the field holds a NaN on a wet cell.  The extrema are over the wet surface cells.  The surface mirror has no w:
+    the velocity part prints two components, maximum(u): (umax, vmax), where the reference prints three."""
+
+    def __init__(self):
+        self.wall_time = time.perf_counter()
+        self.monitor, self.message, self.record = None, None, None
+
+    def _fields(self, model):
+        st, si = model.ocean.surface_state(), model.sea_ice
+        fields = {}
+        if si is not None and getattr(si, "thickness", None) is not None:
+            fields.update({"h": si.thickness, "ℵ": si.concentration})   # (a literal key: a keyword ℵ would be NFKC-normalised)
+        fields.update(T=st["T"], S=st["S"], u=st["u"], v=st["v"])
+        return fields
+
+    def _collect(self, model):
+        """{name: (maximum, minimum, value)} of one collection at the model's clock"""
+        if self.monitor is None:
+            self.names = list(self._fields(model))
+            self.monitor = _model_monitor(model, self._fields(model), 1)
+        self.monitor.reset()
+        self.monitor.collect(model.clock.time)
+        values, _ = self.monitor.read()
+        self.record = dict(zip(self.names, values[0]))
+        nan = float("nan")
+        return {k: (nan if v["nan_count"] > 0 else float(v["maximum"]), nan if v["nan_count"] > 0 else float(v["minimum"]))
+                for k, v in self.record.items()}
+
+    def _head(self, sim):
+        return "time: %s, iteration: %d, Δt: %s, " % (prettytime(sim.model.clock.time), sim.model.clock.iteration, prettytime(sim.dt))
+
+    def _ice(self, x):
+        return "max(h): %s m, max(ℵ): %s " % (_julia("%.2e", x["h"][0]), _julia("%.2e", x["ℵ"][0])) if "h" in x else ""
+
+    def _emit(self, message):
+        self.message = message
+        _log.info(message)
+        self.wall_time = time.perf_counter()
+        return message
+
+    def __call__(self, sim):
+        x = self._collect(sim.model)
+        step_time = time.perf_counter() - self.wall_time
+        msg4 = "extrema(T, S): (%s, %s) ᵒC, (%s, %s) psu, " % tuple(_julia("%.2f", v) for v in x["T"] + x["S"])   # (max, min)
+        msg5 = "maximum(u): (%s, %s) m/s, " % (_julia("%.2e", x["u"][0]), _julia("%.2e", x["v"][0]))
+        msg6 = "wall time: %s \n" % prettytime(step_time)
+        return self._emit(self._head(sim) + self._ice(x) + msg4 + msg5 + msg6)
+
+    def close(self):
+        if self.monitor is not None:
+            self.monitor.close()
+
+
+class OmipProgress(Progress):
+    """omip_progress_callback (OMIPConfigurations/omip_simulation.jl:644-691): the same collection as Progress with that
+    callback's message — extrema(T, S) as (Tmin, Tmax), (Smin, Smax) — and, at iterations 1, 5, 100 and 1000, the determinism
+    probe `STATE_HASH iter=%d  T=%016x  S=%016x  u=%016x  h=%016x` (:671-683).  The four words are the hashes of the SAME
+    record (include/coflux.h, cf_monitor_value.hash: the library's hash, not Julia's hash(::Array)), so no field is copied to
+    the host; h is 0 for a model without sea-ice thickness.  `hashes` keeps {iteration: line}."""
+    HASH_ITERATIONS = (1, 5, 100, 1000)
+
+    def __init__(self):
+        super().__init__()
+        self.hashes = {}
+
+    def __call__(self, sim):
+        x = self._collect(sim.model)
+        step_time = time.perf_counter() - self.wall_time
+        (Tmax, Tmin), (Smax, Smin) = x["T"], x["S"]
+        msg3 = "extrema(T, S): (%s, %s) ᵒC, (%s, %s) psu " % tuple(_julia("%.2f", v) for v in (Tmin, Tmax, Smin, Smax))
+        msg4 = "maximum(u): (%s, %s) m/s, " % (_julia("%.2e", x["u"][0]), _julia("%.2e", x["v"][0]))
+        msg5 = "wall time: %s" % prettytime(step_time)
+        message = self._head(sim) + self._ice(x) + msg3 + msg4 + msg5
+        it = sim.model.clock.iteration
+        if it in self.HASH_ITERATIONS:
+            r = self.record
+            line = "STATE_HASH iter=%d  T=%016x  S=%016x  u=%016x  h=%016x" % (it, int(r["T"]["hash"]), int(r["S"]["hash"]), int(r["u"]["hash"]),
+                                                                              int(r["h"]["hash"]) if "h" in r else 0)
+            self.hashes[it] = line
+            _log.info(line)
+        return self._emit(message)
+
+
+def omip_progress_callback():
+    """omip_progress_callback(wall_time) of the reference: a callback for add_callback(simulation, …, IterationInterval(1))."""
+    return OmipProgress()
+
+
+class NaNChecker:
+    """Oceananigans' NaNChecker as a callback: NaNChecker(fields; schedule = IterationInterval(100)), added with
+    add_callback(simulation, checker, checker.schedule).  `fields`: name → ocean-grid field; default: the ocean's net fluxes
+    (u, v, T, S) and the surface temperature T.  One collection per call and 16 bytes read back (cf_monitor_status); on a
+    non-finite wet cell it clears `simulation.running` and keeps `first` = (iteration, name, (j, i)) — the first such field in
+    the order of `fields` and its first such cell.  Deviation: it also stops on ±Inf, where Oceananigans looks for NaN only."""
+
+    def __init__(self, fields=None, schedule=None):
+        self.fields = fields
+        self.schedule = IterationInterval(schedule) if isinstance(schedule, int) else (schedule or IterationInterval(100))
+        self.monitor, self.first = None, None
+
+    def __call__(self, sim):
+        model = sim.model
+        if self.monitor is None:
+            if self.fields is None:
+                net = model.interfaces.net_fluxes._ocean_fields
+                self.fields = {"net_" + k: net[k] for k in ("u", "v", "T", "S")}
+                self.fields["T"] = model.ocean.surface_state()["T"]
+            self.names = list(self.fields)
+            self.monitor = _model_monitor(model, self.fields, 1)
+        self.monitor.reset()
+        self.monitor.collect(model.clock.time)
+        record, entries = self.monitor.status()
+        if record < 0:
+            return
+        e = (entries & -entries).bit_length() - 1          # the lowest entry that had one
+        value = self.monitor.read()[0][0, e]
+        if self.first is None:
+            self.first = (model.clock.iteration, self.names[e], _cell(value["first_nonfinite"], model.ocean.grid.size[0]))
+        _log.error("NaNChecker: %s is not finite at %s, iteration %d: the simulation stops", self.names[e], self.first[2], model.clock.iteration)
+        sim.running = False
+
+    def close(self):
+        if self.monitor is not None:
+            self.monitor.close()
 
 
 class JRA55PrescribedLand:

@@ -448,6 +448,21 @@ class FluxContext:
         self._check(self.lib.cf_attach_integrals(self._h, h, int(stride), float(time_origin), float(step_seconds)),
                     "cf_attach_integrals")
 
+    # -- surface monitor --------------------------------------------------------------------------
+    def monitor(self, entries, mask=None, first_cell=0, capacity=1024, max_workgroups=0):
+        """A device-side time series of extrema, non-finite counts and state hashes (cf_monitor_create).  `entries`: up to
+        abi.MONITOR_MAX_ENTRIES ocean-grid float64 fields or (field, "value" | "abs") pairs (abi.MONITOR_* work too);
+        `mask`: the context's wet mask; `first_cell`: the global index of this slab's interior cell (0, 0)."""
+        return SurfaceMonitor(self, entries, mask, first_cell, capacity, max_workgroups)
+
+    def attach_monitor(self, monitor, stride=1, time_origin=0.0, step_seconds=1.0):
+        """time_steps() appends a record of `monitor` after every step s with (s + 1) % stride == 0, stamped
+        time_origin + (s + 1) · step_seconds (cf_attach_monitor), after the attached averager and integrator; None detaches."""
+        h = monitor._h if monitor is not None else None
+        self._attached_monitor = monitor
+        self._check(self.lib.cf_attach_monitor(self._h, h, int(stride), float(time_origin), float(step_seconds)),
+                    "cf_attach_monitor")
+
     # -- sparse surface operators -----------------------------------------------------------------
     def regridder(self, row_ptr, col, weight, mask=None, mode="mean", max_workgroups=0):
         """A fixed sparse surface operator on the device (cf_regrid_create): CSR over destination rows — row_ptr (n_rows + 1),
@@ -506,7 +521,7 @@ TERM_KINDS = dict(field=abi.TERM_FIELD, product=abi.TERM_PRODUCT, center_x=abi.T
 
 
 class _ChildHandle:
-    """What TimeAverager, SurfaceIntegrator, SurfaceRegridder and SnapshotWindow share: a handle `_h` made on the context
+    """What TimeAverager, SurfaceIntegrator, SurfaceMonitor, SurfaceRegridder and SnapshotWindow share: a handle `_h` made on the context
     `ctx` that may outlive it (the library then fails every call but the `_destroy` one with "… has been destroyed")."""
     _destroy = None   # name of the cf_*_destroy entry point
 
@@ -647,6 +662,67 @@ class SurfaceIntegrator(_ChildHandle):
 
     def reset(self):
         self._check(self.lib.cf_integrals_reset(self._h), "cf_integrals_reset")
+
+
+MONITOR_KINDS = dict(value=abi.MONITOR_VALUE, abs=abi.MONITOR_ABS)
+
+
+class SurfaceMonitor(_ChildHandle):
+    """cf_monitor_*: every collect(time) appends one record — per entry the minimum and maximum over the wet interior cells
+    that are not NaN with the smallest cell index of each, the counts of NaN and ±Inf wet cells with the first of them, and a
+    64-bit hash of all interior cells — to a series kept on the device; read() and status() are the only host
+    synchronisations.  The library borrows the pointers: the tensors are kept alive here."""
+    _destroy = "cf_monitor_destroy"
+
+    def __init__(self, ctx, entries, mask=None, first_cell=0, capacity=1024, max_workgroups=0):
+        self._adopt(ctx)
+        entries = [tuple(e) if isinstance(e, (tuple, list)) else (e, "value") for e in entries]
+        self.n_entries, self.capacity, self.first_cell = len(entries), int(capacity), int(first_cell)
+        if self.n_entries > abi.MONITOR_MAX_ENTRIES:
+            raise ValueError(f"{self.n_entries} entries (at most {abi.MONITOR_MAX_ENTRIES})")
+        desc = abi.MonitorDesc()
+        desc.struct_size, desc.n_entries, desc.max_workgroups = C.sizeof(abi.MonitorDesc), self.n_entries, int(max_workgroups)
+        desc.first_cell = self.first_cell
+        self._keep = [mask]
+        if mask is not None:
+            if not _is_field(mask, ctx, None):
+                raise ValueError(f"mask is a contiguous device array of shape {ctx.shape}")
+            desc.mask = mask.data_ptr()
+        for e, (a, kind) in enumerate(entries):
+            E = desc.entries[e]
+            E.kind = MONITOR_KINDS[kind] if isinstance(kind, str) else int(kind)
+            if a is not None:
+                if not _is_field(a, ctx):
+                    raise ValueError(f"entry {e}: a is a contiguous float64 device array of shape {ctx.shape}")
+                E.a = a.data_ptr()
+                self._keep.append(a)
+        ctx._check(self.lib.cf_monitor_create(ctx._h, C.byref(desc), self.capacity, C.byref(self._h)), "cf_monitor_create")
+
+    def collect(self, time=0.0):
+        self._check(self.lib.cf_monitor_collect(self._h, float(time)), "cf_monitor_collect")
+
+    def count(self):
+        n = C.c_int64()
+        self._check(self.lib.cf_monitor_count(self._h, C.byref(n)), "cf_monitor_count")
+        return n.value
+
+    def read(self, first=0, n=None):
+        """(values[n, n_entries] of abi.MONITOR_VALUE_DTYPE, times[n]) of records first … first + n − 1 (n = None: to the end)."""
+        n = self.count() - first if n is None else n
+        values, times = np.zeros((max(n, 0), self.n_entries), dtype=abi.MONITOR_VALUE_DTYPE), np.zeros(max(n, 0))
+        self._check(self.lib.cf_monitor_read(self._h, int(first), int(n), values.ctypes.data, times.ctypes.data_as(abi.c_double_p)),
+                    "cf_monitor_read")
+        return values, times
+
+    def status(self):
+        """(index of the first record since the last reset with a non-finite wet cell, bit mask of the entries that had one in
+        it); (−1, 0) when every record is clean.  Synchronises the stream and reads 16 bytes."""
+        first, entries = C.c_int64(), C.c_uint32()
+        self._check(self.lib.cf_monitor_status(self._h, C.byref(first), C.byref(entries)), "cf_monitor_status")
+        return first.value, entries.value
+
+    def reset(self):
+        self._check(self.lib.cf_monitor_reset(self._h), "cf_monitor_reset")
 
 
 REGRID_MODES = dict(mean=abi.REGRID_MEAN, sum=abi.REGRID_SUM)

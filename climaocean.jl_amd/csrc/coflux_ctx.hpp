@@ -47,7 +47,7 @@ struct RcclApi {
     ncclResult_t (*CommCuDevice)(const ncclComm_t, int*) = nullptr;
 };
 
-// What averagers, integrators, regridders and snapshot windows share: a handle made on a context may outlive it.  cf_destroy
+// What averagers, integrators, monitors, regridders and snapshot windows share: a handle made on a context may outlive it.  cf_destroy
 // orphans every child (orphan_children); calls that need the context then fail through live(), destroy still works.
 struct cf_child {
     cf_ctx* ctx = nullptr;   // NULL once the context is destroyed
@@ -179,7 +179,7 @@ struct cf_ctx {
     // per-kernel event recorder (cf_profile_enable): 4 events per recorded update_state
     std::vector<cf::Event> prof_events;
     int prof_capacity = 0, prof_count = 0;
-    // every averager, integrator, regridder and window made on this context (cf_destroy orphans them)
+    // every averager, integrator, monitor, regridder and window made on this context (cf_destroy orphans them)
     std::vector<cf_child*> children;
     // time averages (coflux_average.cpp): the one cf_time_steps collects (cf_attach_average)
     cf_average* average = nullptr;
@@ -189,6 +189,10 @@ struct cf_ctx {
     cf_integrals* integrals = nullptr;
     int32_t integrals_stride = 1;
     double integrals_time_origin = 0.0, integrals_step_seconds = 0.0;
+    // surface monitor (coflux_monitor.cpp): the same for the monitors (cf_attach_monitor)
+    cf_monitor* monitor = nullptr;
+    int32_t monitor_stride = 1;
+    double monitor_time_origin = 0.0, monitor_step_seconds = 0.0;
 };
 
 // One cf_time_steps call's step loop, as CF_OPT_LAND_ZEROS sees it: open for exactly the scope's lifetime
@@ -223,6 +227,14 @@ struct cf_integrals : cf_child {
     cf::DeviceBuffer<double> d_series;  // [capacity][n_entries]; the partial sums and the entries' descriptors lie behind it
 };
 
+struct cf_monitor : cf_child {
+    MonitorArgs args{};
+    int max_blocks = 0;
+    int64_t capacity = 0, count = 0;
+    std::vector<double> times;   // of the records, host side
+    cf::DeviceBuffer<cf_monitor_value> d_series;  // [capacity][n_entries]; the partials, the entries' device copies and the status lie behind it
+};
+
 struct cf_regrid : cf_child {
     RegridTables tables{};
     int64_t n_rows = 0;
@@ -255,6 +267,10 @@ int average_collect(cf_average* a, double weight);
 int integrals_collect(cf_integrals* q, double time);
 // coflux_integrals.cpp: CF_ERR_INVALID unless the attached integrator's series has room for what cf_time_steps(first_step, nsteps) collects
 int integrals_room(cf_ctx* ctx, int64_t first_step, int nsteps);
+// coflux_monitor.cpp: one collection of `m` (the series must have room: monitor_room)
+int monitor_collect(cf_monitor* m, double time);
+// coflux_monitor.cpp: CF_ERR_INVALID unless the attached monitor's series has room for what cf_time_steps(first_step, nsteps) collects
+int monitor_room(cf_ctx* ctx, int64_t first_step, int nsteps);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state)
 extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx);
 
@@ -278,6 +294,7 @@ inline void orphan_children(cf_ctx* ctx) {
     ctx->children.clear();
     ctx->average = nullptr;
     ctx->integrals = nullptr;
+    ctx->monitor = nullptr;
 }
 // CF_ERR_INVALID unless `child` is a handle whose context is alive: live(a, "cf_average_reset", "averager")
 inline int live(const cf_child* child, const char* fn, const char* kind) {

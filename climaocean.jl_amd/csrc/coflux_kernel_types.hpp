@@ -134,6 +134,33 @@ struct FoldFields {
     int n;
 };
 
+// the surface monitor (coflux_monitor.hip)
+struct MonitorEntry {                 // device copy of an entry
+    const double* a;
+    int32_t kind, pad;
+};
+struct MonitorPartial {               // the eight running values of one (entry, slice); keys, not doubles (order_key there)
+    uint64_t key_min, key_max;        // ~0 / 0: none yet (no non-NaN double has either key)
+    int64_t argmin, argmax;           // INT64_MAX: none yet
+    int64_t nan_count, inf_count;
+    int64_t first_nonfinite;          // INT64_MAX: none
+    uint64_t hash;
+};
+static_assert(sizeof(MonitorPartial) == sizeof(cf_monitor_value), "a partial is as wide as a value");
+struct MonitorStatus {                // the 16 bytes of cf_monitor_status; all zero: clean since the last reset
+    int64_t first_bad_plus_one;       // 1 + the index of the first record with a non-finite wet cell
+    uint32_t bad_entries, pad;
+};
+struct MonitorArgs {
+    const MonitorEntry* entry;        // device, [n_entries]
+    const void* mask;
+    MonitorPartial* partial;          // device, [n_entries][slices]
+    MonitorStatus* status;            // device
+    double z_surface;
+    int64_t first_cell;
+    int32_t mask_kind, n_entries, slices, pad;
+};
+
 inline SourceDesc make_source(const cf_atmos_source* s) {
     SourceDesc S;
     for (int v = 0; v < CF_JRA55_NVARS; ++v) S.data[v] = s->data[v];

@@ -195,6 +195,17 @@ unsigned integrals_tiles(const GridDesc& G);
 // the tile kernel on min(tiles, max_blocks) workgroups (0: one per tile), then the combination into record[0 … n_entries)
 hipError_t launch_integrals(hipStream_t st, const IntegralArgs& K, const GridDesc& G, double* record, int max_blocks);
 
+// cf_monitor_collect (coflux_monitor.hip): extrema, non-finite counts and the state hash of up to CF_MONITOR_MAX_ENTRIES fields.
+// Every reduction is exact (integer keys, integer sums, a wrapping sum), so the partition of the cells is free: `slices`
+// slices of the interior per entry, one partial per (entry, slice), combined by a single-workgroup launch.
+// (the argument bundle and the partials' layout: coflux_kernel_types.hpp)
+struct MonitorArgs;
+int monitor_slices(const GridDesc& G, int n_entries);   // the library's partition (a function of the surface and the entry count)
+// the pass on min(n_entries · slices, max_blocks) workgroups (0: one per (entry, slice)), then the combination into
+// record[0 … n_entries) and the status (`record_index`: the record's number since the last reset)
+hipError_t launch_monitor(hipStream_t st, const MonitorArgs& K, const GridDesc& G, cf_monitor_value* record, int64_t record_index,
+                          int max_blocks);
+
 // cf_regrid_apply (coflux_regrid.hip): a fixed sparse surface operator on up to CF_REGRID_MAX_FIELDS fields in one pass.
 // The host (coflux_regrid.cpp) turns the CSR operator into the tables below at create; all of them are device arrays.
 constexpr int REGRID_SHORT = 64;        // rows of at most this many entries: one 16-lane group each, four rows per wave

@@ -303,6 +303,7 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         return s;
     };
     CHECK(integrals_room(ctx, first_step, nsteps));   // a series that would overflow: nothing is launched
+    CHECK(monitor_room(ctx, first_step, nsteps));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (int n = 0; n < S->n_ocean_states; ++n) {
         if (ctx->dev.mask_kind != CF_MASK_NONE && !S->ocean_states[n].mask) return fail(ctx, CF_ERR_INVALID, "ocean state %d has no mask", n);
@@ -384,6 +385,9 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         // an attached integrator (cf_attach_integrals): the same rule, one record per collected step
         if (ctx->integrals && (step + 1) % ctx->integrals_stride == 0)
             CHECK(integrals_collect(ctx->integrals, ctx->integrals_time_origin + (double)(step + 1) * ctx->integrals_step_seconds));
+        // an attached monitor (cf_attach_monitor): the same rule again, after both
+        if (ctx->monitor && (step + 1) % ctx->monitor_stride == 0)
+            CHECK(monitor_collect(ctx->monitor, ctx->monitor_time_origin + (double)(step + 1) * ctx->monitor_step_seconds));
     }
     return CF_OK;
 }

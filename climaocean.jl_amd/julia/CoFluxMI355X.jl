@@ -465,6 +465,73 @@ attach_integrals!(b, q::Union{Nothing, CoFluxIntegrals}, stride = 1, time_origin
     check(b.ctx, ccall((:cf_attach_integrals, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Float64),
                        b.ctx, isnothing(q) ? C_NULL : q.ptr, stride, time_origin, step_seconds))
 
+# ---- surface extrema, non-finite counts and state hashes on the device (ClimaOcean.jl:48-88, omip_simulation.jl:644-691) ----
+# A monitor turns up to 16 surface fields into records of CfMonitorValue (one pass per collection) and keeps the series on
+# the device: what Progress / omip_progress_callback print, the STATE_HASH words and what a NaNChecker asks, without moving a
+# field.  read_monitor and monitor_status are the only host synchronisations; attach_monitor! makes time_steps! append a
+# record every `stride` steps.  The hash is the library's own (include/coflux.h), not Base.hash.
+const CF_MONITOR_VALUE, CF_MONITOR_ABS = Int32(0), Int32(1)
+const CF_MONITOR_MAX_ENTRIES = 16
+struct CfMonitorEntry
+    a::Ptr{Float64}
+    kind::Int32; reserved::Int32
+end
+CfMonitorEntry() = CfMonitorEntry(C_NULL, CF_MONITOR_VALUE, 0)
+CfMonitorEntry(a, kind = CF_MONITOR_VALUE) = CfMonitorEntry(a, kind, 0)
+struct CfMonitorDesc
+    struct_size::Int32; n_entries::Int32
+    mask::Ptr{Cvoid}
+    first_cell::Int64
+    max_workgroups::Int32; reserved::Int32
+    entries::NTuple{16, CfMonitorEntry}
+end
+function CfMonitorDesc(entries::Vector{CfMonitorEntry}; mask = C_NULL, first_cell = 0, max_workgroups = 0)
+    length(entries) <= 16 || error("CoFluxMI355X: at most 16 monitor entries")
+    padded = ntuple(k -> k <= length(entries) ? entries[k] : CfMonitorEntry(), 16)
+    return CfMonitorDesc(sizeof(CfMonitorDesc), length(entries), mask, first_cell, max_workgroups, 0, padded)
+end
+struct CfMonitorValue      # 64 bytes
+    minimum::Float64; maximum::Float64
+    argmin::Int64; argmax::Int64          # global cell numbers first_cell + j·nx + i (0-based), -1: none
+    nan_count::Int64; inf_count::Int64
+    first_nonfinite::Int64
+    hash::UInt64
+end
+mutable struct CoFluxMonitor
+    ptr::Ptr{Cvoid}
+    backend::CoFluxBackend
+    n_entries::Int
+end
+function CoFluxMonitor(b::CoFluxBackend, desc::CfMonitorDesc, capacity)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(b.ctx, ccall((:cf_monitor_create, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfMonitorDesc}, Int32, Ref{Ptr{Cvoid}}),
+                       b.ctx, desc, capacity, out))
+    m = CoFluxMonitor(out[], b, desc.n_entries)
+    finalizer(x -> ccall((:cf_monitor_destroy, libcoflux), Cint, (Ptr{Cvoid},), x.ptr), m)
+    return m
+end
+collect!(m::CoFluxMonitor, time) = check(C_NULL, ccall((:cf_monitor_collect, libcoflux), Cint, (Ptr{Cvoid}, Float64), m.ptr, time))
+reset!(m::CoFluxMonitor) = check(C_NULL, ccall((:cf_monitor_reset, libcoflux), Cint, (Ptr{Cvoid},), m.ptr))
+function monitor_count(m::CoFluxMonitor)
+    n = Ref{Int64}(0)
+    check(C_NULL, ccall((:cf_monitor_count, libcoflux), Cint, (Ptr{Cvoid}, Ref{Int64}), m.ptr, n))
+    return n[]
+end
+function read_monitor(m::CoFluxMonitor, first = 0, n = monitor_count(m) - first)
+    values = Matrix{CfMonitorValue}(undef, m.n_entries, n); times = zeros(Float64, n)   # column r is record first + r
+    check(C_NULL, ccall((:cf_monitor_read, libcoflux), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{CfMonitorValue}, Ptr{Float64}),
+                        m.ptr, first, n, values, times))
+    return (values = values, times = times)
+end
+function monitor_status(m::CoFluxMonitor)   # (first bad record or -1, bit mask of its non-finite entries)
+    record = Ref{Int64}(-1); entries = Ref{UInt32}(0)
+    check(C_NULL, ccall((:cf_monitor_status, libcoflux), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{UInt32}), m.ptr, record, entries))
+    return (record = record[], entries = entries[])
+end
+attach_monitor!(b, m::Union{Nothing, CoFluxMonitor}, stride = 1, time_origin = 0.0, step_seconds = 1.0) =
+    check(b.ctx, ccall((:cf_attach_monitor, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Float64),
+                       b.ctx, isnothing(m) ? C_NULL : m.ptr, stride, time_origin, step_seconds))
+
 # ---- a fixed sparse surface operator on the device (visualize/cache.jl:918-937, 983-1011) ---------------------------------
 # CSR over destination rows: `row_ptr` (0-based, n_rows + 1 entries), `col` (0-based interior cell numbers j·nx + i) and
 # `weight` (≥ 0) are host arrays, copied to the device at construction — a SparseMatrixCSC of ConservativeRegridding.jl goes

@@ -44,7 +44,8 @@ extern "C" {
                           * their time series (cf_integrals_*, cf_attach_integrals) are purely additive — no existing struct or
                           * entry point changed, a host finds them by symbol; likewise CF_OPT_INTERP_TILE_ROWS (an experiment option)
                           * and cf_debug_interp_grid, and the sparse surface operator (cf_regrid_*); likewise CF_OPT_LAND_ZEROS and
-                          * cf_debug_land_zero_launches — with them cf_time_steps gained a contract on its outputs, stated there */
+                          * cf_debug_land_zero_launches — with them cf_time_steps gained a contract on its outputs, stated there;
+                          * likewise the surface monitor (cf_monitor_*, cf_attach_monitor) */
 
 /* status codes */
 #define CF_OK 0
@@ -1143,6 +1144,106 @@ int cf_integrals_read(cf_integrals* q, int64_t first, int64_t n, double* h_value
 int cf_integrals_reset(cf_integrals* q);
 /* Footprint: cf_time_steps' own, and cf_integrals_collect's at every collected step.                                   */
 int cf_attach_integrals(cf_ctx* ctx, cf_integrals* q, int32_t stride, double time_origin, double step_seconds);
+
+/* ------------------------------------------------------------------------------------------
+ * Surface extrema, non-finite counts and state hashes on the device: what the reference's progress callback looks at on
+ * every iteration — max(h), max(ℵ), extrema(T, S), maximum(u) of ClimaOcean.Progress (src/ClimaOcean.jl:48-88) and
+ * omip_progress_callback (OMIPConfigurations/omip_simulation.jl:644-691), the STATE_HASH determinism probe of the latter
+ * (:671-683) and the NaNChecker every Oceananigans Simulation carries.  A monitor holds up to CF_MONITOR_MAX_ENTRIES
+ * entries (an ocean-grid f64 field x and a kind: y = x, or y = |x| with the sign bit cleared, so |−0| = +0, |−Inf| = +Inf)
+ * and a series of `capacity` records in device memory that the library owns; one collection appends one record of
+ * n_entries values of type cf_monitor_value, 64 bytes each.  Interior cells are numbered c = first_cell + j·nx + i.
+ *   Order.  minimum / maximum are taken over the wet interior cells whose x is not NaN, in the IEEE total order of the
+ *     non-NaN doubles: −0.0 < +0.0, and ±Inf take part.  A field that holds both zeros and nothing smaller has minimum
+ *     −0.0 at the index of its first −0.0.  Ties go to the smallest c.  The device compares the order-preserving integer
+ *     key of the bits (bits ^ (sign ? all ones : the sign bit)), never with floating-point min / max instructions, whose
+ *     NaN and signed-zero behaviour is a mode, not a definition.  With no such cell: +Inf, −Inf, argmin = argmax = −1.
+ *   Counts.  nan_count / inf_count: wet interior cells with x NaN (any sign, any payload) / x = ±Inf; first_nonfinite the
+ *     smallest c of either, −1 when there is none.
+ *   Land.  Excluded cells (land, halos) are selected away: a NaN, an Inf or a huge value there reaches neither the
+ *     extrema nor the counts nor first_nonfinite.  u and v are masked by the wetness of the CENTRE cell (i, j), like
+ *     every masked quantity of this library.
+ *   Hash.  Over ALL interior cells, wet or not, of the raw bits of x (never of y; the mask does not enter):
+ *         hash = Σ_c mix64(bits(x_c) XOR (K·(c + 1) mod 2⁶⁴)) mod 2⁶⁴,      K = 0x9E3779B97F4A7C15,
+ *         mix64(z):  z = (z ^ z>>30) · 0xBF58476D1CE4E5B9;  z = (z ^ z>>27) · 0x94D049BB133111EB;  z ^ z>>31.
+ *     Known answers: the cells [0.0, −0.0, 1.0, NaN 0x7FF8000000000000, +Inf, −1.5] with first_cell = 0 hash to
+ *     0xbc9733db8e1747df, with first_cell = 1000 to 0x05c59e8be3d701d6; [0.0] to 0xe220a8397b1dcdaf; no cells to 0.
+ *     For a fixed cell mix64 is a bijection of the bits: changing any single cell always changes the hash.  The library's
+ *     own hash, not Julia's hash(::Array); it serves the same purpose, comparing two runs without moving a field.
+ *   Exactness.  Every quantity is an exact, associative and commutative reduction (integer-key min / max with an index
+ *     tie-break, integer sums, a wrapping sum): the bits of a record depend only on the interior values, the mask and
+ *     first_cell — not on the launch geometry or `max_workgroups`, the halo widths, where the arrays start in memory, the
+ *     device's CU count, or on whether the host or cf_time_steps made the collection.  No floating-point atomics.
+ *   Slabs.  Each context monitors its own slab with its first_cell.  The hash is a wrapping sum: the hashes of latitude
+ *     slabs add up, mod 2⁶⁴, to the hash of the whole surface; nan_count / inf_count add; minimum / maximum combine in
+ *     the same order with the smaller argmin / argmax on ties, first_nonfinite is the smallest that is not −1 — the
+ *     host's combination of a few words.
+ *   One collection is one pass per entry over the interior plus a single-workgroup combination launch: 8 bytes per cell
+ *   and entry, and the mask once per ENTRY (not once per cell): n_entries · (8 + mask bytes) per cell in all.
+ *   cf_monitor_create   CF_ERR_INVALID for a wrong struct_size, n_entries outside 1…CF_MONITOR_MAX_ENTRIES, a NULL `a`, an
+ *                       unknown kind, max_workgroups < 0 or capacity < 1.  The pointers are borrowed: the arrays outlive
+ *                       the monitor.  The same array may be named by several entries.
+ *   cf_monitor_destroy  detaches the monitor if it is attached; a monitor outlived by its context may still be destroyed
+ *                       (every other call on it then fails).
+ *   cf_monitor_collect  record number `count` is written, stream ordered, no host synchronisation; `time` is kept on the
+ *                       host.  CF_ERR_INVALID, and nothing is launched or written, when the series is full.
+ *   cf_monitor_count    the number of records since the last reset.
+ *   cf_monitor_read     synchronises the context's stream and copies records first … first + n − 1 (n × n_entries values,
+ *                       record-major) and their times (h_times may be NULL).  Any sub-range; reading does not consume.
+ *   cf_monitor_status   synchronises the context's stream and reads 16 bytes: the index, since the last reset, of the FIRST
+ *                       record in which any entry had nan_count + inf_count > 0, and the bit mask (bit e: entry e) of the
+ *                       entries that did in that record; −1 and 0 when there is none.  A long cf_time_steps call is
+ *                       checked without reading the series.  The status is written by one thread of the
+ *                       single-workgroup combination launch: no data race.  Either output may be NULL.
+ *   cf_monitor_reset    the series is empty again and the status is cleared; the clear is stream ordered.
+ *   cf_attach_monitor   cf_time_steps collects `m` after the cf_update_state of every step s (global index) with
+ *                       (s + 1) % stride == 0, stamped time_origin + (s + 1) · step_seconds; NULL detaches.  One monitor
+ *                       per context, independent of the averager and the integrator: all three may be attached, the
+ *                       monitor collects after both.  A run split into CF_PIPELINE_CONTINUING calls yields the same
+ *                       records as one call.  A cf_time_steps call whose collections would not fit the series fails with
+ *                       CF_ERR_INVALID before it launches anything.  CF_ERR_INVALID for stride < 1, a non-finite time
+ *                       origin or step, or a monitor of another context.
+ * Still ABI 5: additive.
+ * ---------------------------------------------------------------------------------------- */
+#define CF_MONITOR_MAX_ENTRIES 16
+#define CF_MONITOR_VALUE 0   /* y = x */
+#define CF_MONITOR_ABS 1     /* y = |x| (sign bit cleared): maximum(abs, u) */
+typedef struct cf_monitor_entry {
+    const double* a;       /* ocean-grid f64 array */
+    int32_t kind;          /* CF_MONITOR_VALUE / _ABS */
+    int32_t reserved;
+} cf_monitor_entry;
+typedef struct cf_monitor_desc {
+    int32_t struct_size;   /* sizeof(cf_monitor_desc) */
+    int32_t n_entries;     /* 1…CF_MONITOR_MAX_ENTRIES */
+    const void* mask;      /* wet mask of the context's mask kind (CF_MASK_U8 / _BOTTOM_HEIGHT); NULL or CF_MASK_NONE: all wet */
+    int64_t first_cell;    /* global index of this slab's interior cell (0, 0) */
+    int32_t max_workgroups; /* 0: the library's choice; > 0 caps the launch (scheduling only: never a bit of a record) */
+    int32_t reserved;
+    cf_monitor_entry entries[CF_MONITOR_MAX_ENTRIES];
+} cf_monitor_desc;
+typedef struct cf_monitor_value {   /* 64 bytes */
+    double minimum;           /* of y over the wet interior cells whose x is not NaN; +Inf when there is none */
+    double maximum;           /* −Inf when there is none */
+    int64_t argmin;           /* the SMALLEST c that holds the minimum; −1 when there is none */
+    int64_t argmax;
+    int64_t nan_count;        /* wet interior cells with x NaN */
+    int64_t inf_count;        /* … with x = ±Inf */
+    int64_t first_nonfinite;  /* the smallest c of those; −1 */
+    uint64_t hash;            /* over ALL interior cells, wet or not, of the raw bits of x */
+} cf_monitor_value;
+typedef struct cf_monitor cf_monitor;
+int cf_monitor_create(cf_ctx* ctx, const cf_monitor_desc* desc, int32_t capacity, cf_monitor** out);
+int cf_monitor_destroy(cf_monitor* m);
+/* Footprint: reads the entries' arrays and the mask on I; writes no caller array (the record goes to the library's own
+ * series).                                                                                                             */
+int cf_monitor_collect(cf_monitor* m, double time);
+int cf_monitor_count(cf_monitor* m, int64_t* records);
+int cf_monitor_read(cf_monitor* m, int64_t first, int64_t n, cf_monitor_value* h_values, double* h_times);
+int cf_monitor_status(cf_monitor* m, int64_t* first_bad_record, uint32_t* bad_entries);
+int cf_monitor_reset(cf_monitor* m);
+/* Footprint: cf_time_steps' own, and cf_monitor_collect's at every collected step.                                     */
+int cf_attach_monitor(cf_ctx* ctx, cf_monitor* m, int32_t stride, double time_origin, double step_seconds);
 
 /* ------------------------------------------------------------------------------------------
  * A fixed sparse surface operator applied on the device: the conservative regridding of surface fields onto the shared
