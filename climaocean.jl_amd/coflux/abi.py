@@ -423,21 +423,13 @@ def load_library(path=None):
     lib.cf_average_weight.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.cf_attach_average.argtypes = [vp, vp, C.c_int32, C.c_double]
     lib.cf_average_create_derived.argtypes = [vp, C.POINTER(AverageDesc), C.POINTER(vp)]
-    lib.cf_integrals_create.argtypes = [vp, C.POINTER(IntegralsDesc), C.c_int32, C.POINTER(vp)]
-    lib.cf_integrals_destroy.argtypes = [vp]
-    lib.cf_integrals_collect.argtypes = [vp, C.c_double]
-    lib.cf_integrals_count.argtypes = [vp, C.POINTER(C.c_int64)]
-    lib.cf_integrals_read.argtypes = [vp, C.c_int64, C.c_int64, c_double_p, c_double_p]
-    lib.cf_integrals_reset.argtypes = [vp]
-    lib.cf_attach_integrals.argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double]
-    lib.cf_monitor_create.argtypes = [vp, C.POINTER(MonitorDesc), C.c_int32, C.POINTER(vp)]
-    lib.cf_monitor_destroy.argtypes = [vp]
-    lib.cf_monitor_collect.argtypes = [vp, C.c_double]
-    lib.cf_monitor_count.argtypes = [vp, C.POINTER(C.c_int64)]
-    lib.cf_monitor_read.argtypes = [vp, C.c_int64, C.c_int64, vp, c_double_p]
+    # the two series recorders: the same entry points but for the descriptor (and the records' type, passed as an address)
+    for family, desc in (("integrals", IntegralsDesc), ("monitor", MonitorDesc)):
+        for name, args in (("create", [vp, C.POINTER(desc), C.c_int32, C.POINTER(vp)]), ("destroy", [vp]), ("collect", [vp, C.c_double]),
+                           ("count", [vp, C.POINTER(C.c_int64)]), ("read", [vp, C.c_int64, C.c_int64, vp, c_double_p]), ("reset", [vp])):
+            getattr(lib, f"cf_{family}_{name}").argtypes = args
+        getattr(lib, f"cf_attach_{family}").argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double]
     lib.cf_monitor_status.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]
-    lib.cf_monitor_reset.argtypes = [vp]
-    lib.cf_attach_monitor.argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double]
     lib.cf_regrid_create.argtypes = [vp, C.POINTER(RegridDesc), C.POINTER(vp)]
     lib.cf_regrid_destroy.argtypes = [vp]
     lib.cf_regrid_apply.argtypes = [vp, C.c_int32, C.POINTER(vp), C.POINTER(vp), vp]

@@ -1063,7 +1063,51 @@ class IterationInterval:
         return iteration % self.interval == 0
 
 
-class SurfaceIntegrals:
+class _SeriesWriter:
+    """What SurfaceIntegrals and SurfaceExtrema share: an output writer that appends one record to the device series of its
+    recorder (the runtime.SurfaceIntegrator / SurfaceMonitor in the attribute `_recorder_name`) per scheduled iteration and
+    moves a full series to the host."""
+    _recorder_name = None
+    _recorder = property(lambda self: getattr(self, self._recorder_name))
+
+    def _begin(self, schedule):
+        self.schedule = IterationInterval(schedule) if isinstance(schedule, int) else (schedule or IterationInterval(1))
+        self._values, self._times = [], []
+
+    def initialize(self, simulation):
+        pass
+
+    def _drain(self):
+        values, times = self._recorder.read()
+        if len(times):
+            self._values.append(values)
+            self._times.append(times)
+            self._recorder.reset()
+
+    def write(self, clock):
+        if not self.schedule.actuate(clock.iteration):
+            return
+        if self._recorder.count() == self._recorder.capacity:
+            self._drain()
+        self._recorder.collect(clock.time)
+
+    def records(self):
+        """(values[n, n_entries] of the recorder's record type, times[n]): every record so far, raw entries in the order given."""
+        self._drain()
+        if not self._times:
+            return np.zeros((0, self._recorder.n_entries), dtype=self._recorder._dtype), np.zeros(0)
+        self._values, self._times = [np.concatenate(self._values)], [np.concatenate(self._times)]
+        return self._values[0], self._times[0]
+
+    @property
+    def times(self):
+        return self.records()[1]
+
+    def close(self):
+        self._recorder.close()
+
+
+class SurfaceIntegrals(_SeriesWriter):
     """An output writer of scalar time series: SurfaceIntegrals(model, outputs; schedule = IterationInterval(1), regions, area).
     `outputs`: name → (kind, a[, b[, threshold[, region bit]]]) with kind "one" | "field" | "product" | "above" as in
     FluxContext.integrals, or "mean": ∫ a dA / ∫ dA over the same region, formed on the host from a "field" entry and the
@@ -1072,11 +1116,13 @@ class SurfaceIntegrals:
     started again, so `capacity` bounds memory, not the length of a run.  `regions`: uint8 region bits (default: every cell in
     bit 0), `area`: cell areas (default: grid.cell_areas()), both host or device arrays in the halo layout."""
 
+    _recorder_name = "integrator"
+
     def __init__(self, model, outputs, schedule=None, regions=None, area=None, capacity=4096):
         itf = model.interfaces
         ctx = self.ctx = itf.context
         self.model = model
-        self.schedule = IterationInterval(schedule) if isinstance(schedule, int) else (schedule or IterationInterval(1))
+        self._begin(schedule)
         on_device = lambda a: a if isinstance(a, torch.Tensor) else ctx.to_device(a)  # noqa: E731
         self.area = on_device(model.ocean.grid.cell_areas() if area is None else area)
         self.regions = None if regions is None else on_device(regions)
@@ -1096,44 +1142,11 @@ class SurfaceIntegrals:
                 entries.append((kind, a, b, threshold, bit))
         self.entries = entries
         self.integrator = ctx.integrals(entries, area=self.area, mask=mask, region=self.regions, capacity=capacity)
-        self._values, self._times = [], []
-
-    def initialize(self, simulation):
-        pass
-
-    def _drain(self):
-        values, times = self.integrator.read()
-        if len(times):
-            self._values.append(values)
-            self._times.append(times)
-            self.integrator.reset()
-
-    def write(self, clock):
-        if not self.schedule.actuate(clock.iteration):
-            return
-        if self.integrator.count() == self.integrator.capacity:
-            self._drain()
-        self.integrator.collect(clock.time)
-
-    def records(self):
-        """(values[n, n_entries], times[n]): every record so far, raw entries in the order of `entries`."""
-        self._drain()
-        if not self._times:
-            return np.zeros((0, len(self.entries))), np.zeros(0)
-        self._values, self._times = [np.concatenate(self._values)], [np.concatenate(self._times)]
-        return self._values[0], self._times[0]
-
-    @property
-    def times(self):
-        return self.records()[1]
 
     def series(self):
         """{name: np.ndarray[n]}: the integrals, and for "mean" outputs integral / integral of 1 over the same region."""
         values, _ = self.records()
         return {name: values[:, c] if one is None else values[:, c] / values[:, one] for name, (c, one) in self._columns.items()}
-
-    def close(self):
-        self.integrator.close()
 
 
 def sea_ice_integrals(model, threshold=0.15, **kw):
@@ -1179,47 +1192,19 @@ def _cell(c, nx):
     return (int(c) // nx, int(c) % nx) if c >= 0 else (-1, -1)
 
 
-class SurfaceExtrema:
+class SurfaceExtrema(_SeriesWriter):
     """An output writer of extrema, non-finite counts and hashes: SurfaceExtrema(model, outputs; schedule = IterationInterval(1)).
     `outputs`: name → field or (field, "value" | "abs").  Every collection is one record on the device (cf_monitor_collect: no
     host synchronisation); series() reads them.  A full device series is moved to the host and started again, so `capacity`
     bounds memory, not the length of a run."""
 
+    _recorder_name = "monitor"
+
     def __init__(self, model, outputs, schedule=None, capacity=4096):
         self.model, self.names = model, list(outputs)
-        self.schedule = IterationInterval(schedule) if isinstance(schedule, int) else (schedule or IterationInterval(1))
+        self._begin(schedule)
         self.nx = model.ocean.grid.size[0]
         self.monitor = _model_monitor(model, outputs, capacity)
-        self._values, self._times = [], []
-
-    def initialize(self, simulation):
-        pass
-
-    def _drain(self):
-        values, times = self.monitor.read()
-        if len(times):
-            self._values.append(values)
-            self._times.append(times)
-            self.monitor.reset()
-
-    def write(self, clock):
-        if not self.schedule.actuate(clock.iteration):
-            return
-        if self.monitor.count() == self.monitor.capacity:
-            self._drain()
-        self.monitor.collect(clock.time)
-
-    def records(self):
-        """(values[n, n_entries] of abi.MONITOR_VALUE_DTYPE, times[n]): every record so far, in the order of `names`."""
-        self._drain()
-        if not self._times:
-            return np.zeros((0, len(self.names)), dtype=abi.MONITOR_VALUE_DTYPE), np.zeros(0)
-        self._values, self._times = [np.concatenate(self._values)], [np.concatenate(self._times)]
-        return self._values[0], self._times[0]
-
-    @property
-    def times(self):
-        return self.records()[1]
 
     def series(self):
         """{name: {"min", "max", "argmin", "argmax", "nan_count", "inf_count", "first_nonfinite", "hash"}}: arrays of n records;
@@ -1233,9 +1218,6 @@ class SurfaceExtrema:
                          "nan_count": v["nan_count"].copy(), "inf_count": v["inf_count"].copy(),
                          "first_nonfinite": pairs(v["first_nonfinite"]), "hash": v["hash"].copy()}
         return out
-
-    def close(self):
-        self.monitor.close()
 
 
 def prettytime(t):

@@ -440,13 +440,16 @@ class FluxContext:
         `area`: float64 cell areas, `mask`: the context's wet mask, `region`: uint8 region bits (all ocean-grid arrays)."""
         return SurfaceIntegrator(self, entries, area, mask, region, capacity, max_workgroups)
 
+    def _attach_series(self, family, handle, stride, time_origin, step_seconds):
+        setattr(self, "_attached_" + family, handle)   # kept alive while attached
+        h = handle._h if handle is not None else None
+        self._check(getattr(self.lib, "cf_attach_" + family)(self._h, h, int(stride), float(time_origin), float(step_seconds)),
+                    "cf_attach_" + family)
+
     def attach_integrals(self, integrator, stride=1, time_origin=0.0, step_seconds=1.0):
         """time_steps() appends a record of `integrator` after every step s with (s + 1) % stride == 0, stamped
         time_origin + (s + 1) · step_seconds (cf_attach_integrals); None detaches."""
-        h = integrator._h if integrator is not None else None
-        self._attached_integrals = integrator
-        self._check(self.lib.cf_attach_integrals(self._h, h, int(stride), float(time_origin), float(step_seconds)),
-                    "cf_attach_integrals")
+        self._attach_series("integrals", integrator, stride, time_origin, step_seconds)
 
     # -- surface monitor --------------------------------------------------------------------------
     def monitor(self, entries, mask=None, first_cell=0, capacity=1024, max_workgroups=0):
@@ -458,10 +461,7 @@ class FluxContext:
     def attach_monitor(self, monitor, stride=1, time_origin=0.0, step_seconds=1.0):
         """time_steps() appends a record of `monitor` after every step s with (s + 1) % stride == 0, stamped
         time_origin + (s + 1) · step_seconds (cf_attach_monitor), after the attached averager and integrator; None detaches."""
-        h = monitor._h if monitor is not None else None
-        self._attached_monitor = monitor
-        self._check(self.lib.cf_attach_monitor(self._h, h, int(stride), float(time_origin), float(step_seconds)),
-                    "cf_attach_monitor")
+        self._attach_series("monitor", monitor, stride, time_origin, step_seconds)
 
     # -- sparse surface operators -----------------------------------------------------------------
     def regridder(self, row_ptr, col, weight, mask=None, mode="mean", max_workgroups=0):
@@ -607,14 +607,44 @@ class TimeAverager(_ChildHandle):
         return total.value, samples.value
 
 
+class _SeriesHandle(_ChildHandle):
+    """What SurfaceIntegrator and SurfaceMonitor share: a series of records [n_entries] of `_dtype` kept on the device behind
+    the entry points cf_<_family>_collect, _count, _read, _reset and _destroy."""
+    _family = None
+    _dtype = None
+
+    def _call(self, name, *args):
+        what = f"cf_{self._family}_{name}"
+        self._check(getattr(self.lib, what)(self._h, *args), what)
+
+    def collect(self, time=0.0):
+        self._call("collect", float(time))
+
+    def count(self):
+        n = C.c_int64()
+        self._call("count", C.byref(n))
+        return n.value
+
+    def read(self, first=0, n=None):
+        """(values[n, n_entries] of the family's record type, times[n]) of records first … first + n − 1 (n = None: to the end
+        of the series)."""
+        n = self.count() - first if n is None else n
+        values, times = np.zeros((max(n, 0), self.n_entries), dtype=self._dtype), np.zeros(max(n, 0))
+        self._call("read", int(first), int(n), values.ctypes.data, times.ctypes.data_as(abi.c_double_p))
+        return values, times
+
+    def reset(self):
+        self._call("reset")
+
+
 INTEGRAND_KINDS = dict(one=abi.INTEGRAND_ONE, field=abi.INTEGRAND_FIELD, product=abi.INTEGRAND_PRODUCT, above=abi.INTEGRAND_ABOVE)
 
 
-class SurfaceIntegrator(_ChildHandle):
+class SurfaceIntegrator(_SeriesHandle):
     """cf_integrals_*: every collect(time) appends one record — entry e is Σ A·x over the wet interior cells that carry the
     entry's region bit — to a series kept on the device, in one pass over the interior; read() is the only host
     synchronisation.  The library borrows the pointers: the tensors are kept alive here."""
-    _destroy = "cf_integrals_destroy"
+    _destroy, _family, _dtype = "cf_integrals_destroy", "integrals", np.float64
 
     def __init__(self, ctx, entries, area=None, mask=None, region=None, capacity=1024, max_workgroups=0):
         self._adopt(ctx)
@@ -644,35 +674,16 @@ class SurfaceIntegrator(_ChildHandle):
                 self._keep.append(t)
         ctx._check(self.lib.cf_integrals_create(ctx._h, C.byref(desc), self.capacity, C.byref(self._h)), "cf_integrals_create")
 
-    def collect(self, time=0.0):
-        self._check(self.lib.cf_integrals_collect(self._h, float(time)), "cf_integrals_collect")
-
-    def count(self):
-        n = C.c_int64()
-        self._check(self.lib.cf_integrals_count(self._h, C.byref(n)), "cf_integrals_count")
-        return n.value
-
-    def read(self, first=0, n=None):
-        """(values[n, n_entries], times[n]) of records first … first + n − 1 (n = None: to the end of the series)."""
-        n = self.count() - first if n is None else n
-        values, times = np.zeros((max(n, 0), self.n_entries)), np.zeros(max(n, 0))
-        self._check(self.lib.cf_integrals_read(self._h, int(first), int(n), values.ctypes.data_as(abi.c_double_p),
-                                               times.ctypes.data_as(abi.c_double_p)), "cf_integrals_read")
-        return values, times
-
-    def reset(self):
-        self._check(self.lib.cf_integrals_reset(self._h), "cf_integrals_reset")
-
 
 MONITOR_KINDS = dict(value=abi.MONITOR_VALUE, abs=abi.MONITOR_ABS)
 
 
-class SurfaceMonitor(_ChildHandle):
+class SurfaceMonitor(_SeriesHandle):
     """cf_monitor_*: every collect(time) appends one record — per entry the minimum and maximum over the wet interior cells
     that are not NaN with the smallest cell index of each, the counts of NaN and ±Inf wet cells with the first of them, and a
     64-bit hash of all interior cells — to a series kept on the device; read() and status() are the only host
     synchronisations.  The library borrows the pointers: the tensors are kept alive here."""
-    _destroy = "cf_monitor_destroy"
+    _destroy, _family, _dtype = "cf_monitor_destroy", "monitor", abi.MONITOR_VALUE_DTYPE
 
     def __init__(self, ctx, entries, mask=None, first_cell=0, capacity=1024, max_workgroups=0):
         self._adopt(ctx)
@@ -698,31 +709,12 @@ class SurfaceMonitor(_ChildHandle):
                 self._keep.append(a)
         ctx._check(self.lib.cf_monitor_create(ctx._h, C.byref(desc), self.capacity, C.byref(self._h)), "cf_monitor_create")
 
-    def collect(self, time=0.0):
-        self._check(self.lib.cf_monitor_collect(self._h, float(time)), "cf_monitor_collect")
-
-    def count(self):
-        n = C.c_int64()
-        self._check(self.lib.cf_monitor_count(self._h, C.byref(n)), "cf_monitor_count")
-        return n.value
-
-    def read(self, first=0, n=None):
-        """(values[n, n_entries] of abi.MONITOR_VALUE_DTYPE, times[n]) of records first … first + n − 1 (n = None: to the end)."""
-        n = self.count() - first if n is None else n
-        values, times = np.zeros((max(n, 0), self.n_entries), dtype=abi.MONITOR_VALUE_DTYPE), np.zeros(max(n, 0))
-        self._check(self.lib.cf_monitor_read(self._h, int(first), int(n), values.ctypes.data, times.ctypes.data_as(abi.c_double_p)),
-                    "cf_monitor_read")
-        return values, times
-
     def status(self):
         """(index of the first record since the last reset with a non-finite wet cell, bit mask of the entries that had one in
         it); (−1, 0) when every record is clean.  Synchronises the stream and reads 16 bytes."""
         first, entries = C.c_int64(), C.c_uint32()
         self._check(self.lib.cf_monitor_status(self._h, C.byref(first), C.byref(entries)), "cf_monitor_status")
         return first.value, entries.value
-
-    def reset(self):
-        self._check(self.lib.cf_monitor_reset(self._h), "cf_monitor_reset")
 
 
 REGRID_MODES = dict(mean=abi.REGRID_MEAN, sum=abi.REGRID_SUM)

@@ -4,7 +4,8 @@
 // weight w the buffer holds Σ w f / Σ w,
 //     m ← (m · c_prev) + (f · c_new),   c_prev = T_prev / T_cur,  c_new = w / T_cur,  T_cur = T_prev + w,
 // two products and one sum, each rounded (contraction off: numpy restates it bit for bit); the first collection of a window
-// stores m ← f without reading m (a fresh buffer may hold NaNs).  The host computes c_prev and c_new in double.
+// stores m ← f without reading m (a fresh buffer may hold NaNs).  The host computes c_prev and c_new in double.  The three
+// operations are `blend` of coflux_surface_cells.hpp, which coflux_derived.hip applies to its samples as well.
 //
 // One launch covers every field of an averager: blockIdx.y is the field, x grid-strides over (row j, slot s) of the interior,
 // AVERAGE_UNROLL slots per thread and trip.
@@ -16,6 +17,7 @@
 
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
+#include "coflux_surface_cells.hpp"
 
 namespace coflux {
 
@@ -23,11 +25,6 @@ namespace {
 
 constexpr int AVERAGE_BLOCK = 256;
 constexpr int AVERAGE_MAX_BLOCKS = 2048;   // memory-bound: cap the grid and stride the rest
-
-__device__ __forceinline__ double blend(double m, double f, double c_prev, double c_new) {
-#pragma clang fp contract(off)
-    return m * c_prev + f * c_new;
-}
 
 // slots per thread per trip of the grid-stride loop, all loaded before any is stored (bytes in flight; A/B builds may set it)
 #ifndef COFLUX_AVERAGE_UNROLL

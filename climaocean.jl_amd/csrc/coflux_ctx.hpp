@@ -1,5 +1,5 @@
-// coflux_ctx.hpp — the context object behind the C ABI and the error plumbing shared by its translation units
-// (coflux_abi.cpp, coflux_window.cpp).  Internal: nothing here crosses the ABI.
+// coflux_ctx.hpp — the context object behind the C ABI and the error plumbing shared by its translation units (every .cpp
+// of this directory but coflux_tables.cpp).  Internal: nothing here crosses the ABI.
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -52,6 +52,20 @@ struct RcclApi {
 struct cf_child {
     cf_ctx* ctx = nullptr;   // NULL once the context is destroyed
     int device = 0;
+};
+
+// What cf_time_steps knows of an attached series recorder (coflux_series.hpp; cf_attach_integrals, cf_attach_monitor).  Steps are
+// numbered globally, so a run split into several calls collects the same steps and stamps them with the same times.
+template <class Handle>
+struct SeriesAttachment {
+    Handle* handle = nullptr;
+    int32_t stride = 1;
+    double time_origin = 0.0, step_seconds = 0.0;
+    void detach() { handle = nullptr; }
+    bool collects(int64_t step) const { return handle && (step + 1) % stride == 0; }
+    double stamp(int64_t step) const { return time_origin + (double)(step + 1) * step_seconds; }
+    // of the steps [first_step, first_step + nsteps): those s with (s + 1) % stride == 0
+    int64_t collections(int64_t first_step, int nsteps) const { return (first_step + nsteps) / stride - first_step / stride; }
 };
 
 // Ownership: every stream, event, device buffer and IPC mapping below is a cf:: owner (coflux_owned.hpp) and releases itself
@@ -185,14 +199,9 @@ struct cf_ctx {
     cf_average* average = nullptr;
     int32_t average_stride = 1;
     double average_step_weight = 0.0;
-    // surface integrals (coflux_integrals.cpp): the same for the integrators (cf_attach_integrals)
-    cf_integrals* integrals = nullptr;
-    int32_t integrals_stride = 1;
-    double integrals_time_origin = 0.0, integrals_step_seconds = 0.0;
-    // surface monitor (coflux_monitor.cpp): the same for the monitors (cf_attach_monitor)
-    cf_monitor* monitor = nullptr;
-    int32_t monitor_stride = 1;
-    double monitor_time_origin = 0.0, monitor_step_seconds = 0.0;
+    // the series recorders cf_time_steps collects after it: surface integrals (cf_attach_integrals), then the monitor (cf_attach_monitor)
+    SeriesAttachment<cf_integrals> integrals;
+    SeriesAttachment<cf_monitor> monitor;
 };
 
 // One cf_time_steps call's step loop, as CF_OPT_LAND_ZEROS sees it: open for exactly the scope's lifetime
@@ -217,22 +226,6 @@ struct cf_average : cf_child {
     int64_t samples = 0;
     bool derived = false;    // made by cf_average_create_derived (coflux_derived.cpp): `terms` replaces `fields`
     DerivedArgs terms{};
-};
-
-struct cf_integrals : cf_child {
-    IntegralArgs args{};
-    int max_blocks = 0;
-    int64_t capacity = 0, count = 0;
-    std::vector<double> times;   // of the records, host side
-    cf::DeviceBuffer<double> d_series;  // [capacity][n_entries]; the partial sums and the entries' descriptors lie behind it
-};
-
-struct cf_monitor : cf_child {
-    MonitorArgs args{};
-    int max_blocks = 0;
-    int64_t capacity = 0, count = 0;
-    std::vector<double> times;   // of the records, host side
-    cf::DeviceBuffer<cf_monitor_value> d_series;  // [capacity][n_entries]; the partials, the entries' device copies and the status lie behind it
 };
 
 struct cf_regrid : cf_child {
@@ -263,14 +256,6 @@ int cf_fail(cf_ctx* ctx, int code, const char* fmt, ...);
 extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows);
 // coflux_average.cpp: one collection of `a` (cf_average_collect without the argument checks of the ABI entry)
 int average_collect(cf_average* a, double weight);
-// coflux_integrals.cpp: one collection of `q` (the series must have room: integrals_room)
-int integrals_collect(cf_integrals* q, double time);
-// coflux_integrals.cpp: CF_ERR_INVALID unless the attached integrator's series has room for what cf_time_steps(first_step, nsteps) collects
-int integrals_room(cf_ctx* ctx, int64_t first_step, int nsteps);
-// coflux_monitor.cpp: one collection of `m` (the series must have room: monitor_room)
-int monitor_collect(cf_monitor* m, double time);
-// coflux_monitor.cpp: CF_ERR_INVALID unless the attached monitor's series has room for what cf_time_steps(first_step, nsteps) collects
-int monitor_room(cf_ctx* ctx, int64_t first_step, int nsteps);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state)
 extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx);
 
@@ -293,8 +278,8 @@ inline void orphan_children(cf_ctx* ctx) {
     for (cf_child* child : ctx->children) child->ctx = nullptr;
     ctx->children.clear();
     ctx->average = nullptr;
-    ctx->integrals = nullptr;
-    ctx->monitor = nullptr;
+    ctx->integrals.detach();
+    ctx->monitor.detach();
 }
 // CF_ERR_INVALID unless `child` is a handle whose context is alive: live(a, "cf_average_reset", "averager")
 inline int live(const cf_child* child, const char* fn, const char* kind) {

@@ -13,11 +13,13 @@
 //     slot and term loops are unrolled over the bucket K (4 / 8 / 16 ≥ slots and terms), so pointers, scales and means have
 //     static indices; the per-cell values sit in K-wide register vectors that a term indexes with its (uniform) slot
 //     number — register-relative moves, no scratch, no LDS.
-// Every operation of a sample is rounded on its own (contraction off) so that NumPy restates it bit for bit.
+// Every operation of a sample is rounded on its own (contraction off) so that NumPy restates it bit for bit; the sample
+// enters the mean through `blend` of coflux_surface_cells.hpp.
 #include <algorithm>
 
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
+#include "coflux_surface_cells.hpp"
 
 namespace coflux {
 
@@ -60,11 +62,6 @@ __device__ __forceinline__ double term_value(int kind, int flags, const Operands
             return kind == CF_TERM_EAST ? p * o.c - q * o.s : p * o.s + q * o.c;
         }
     }
-}
-
-__device__ __forceinline__ double blend(double m, double f, double c_prev, double c_new) {
-#pragma clang fp contract(off)
-    return m * c_prev + f * c_new;
 }
 
 template <int K, bool STORE>

@@ -25,10 +25,12 @@
 // with static indices and the slot index only ever addresses LDS: no scratch.  The entries' descriptors live in LDS as well
 // (as kernel arguments they took a hundred scalar registers): one broadcast read and a uniform branch on the kind per entry.
 // Contraction is off throughout: a·b is one rounded product, ·A another, the sum a third, in every instantiation.
+// The pair of cells, its loads, its wet test and the butterfly (wave_sum) are coflux_surface_cells.hpp's.
 #include <algorithm>
 
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
+#include "coflux_surface_cells.hpp"
 
 namespace coflux {
 
@@ -38,22 +40,6 @@ constexpr int INTEGRALS_BLOCK = 256;
 constexpr int INTEGRALS_PAIRS = INTEGRALS_TILE / (2 * INTEGRALS_BLOCK);   // pairs of cells per thread and tile
 static_assert(INTEGRALS_PAIRS * 2 * INTEGRALS_BLOCK == INTEGRALS_TILE, "a tile is a whole number of pairs per thread");
 constexpr int INTEGRALS_WAVES = INTEGRALS_BLOCK / 64;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
-
-// the two cells of a thread from one array: k0 / k1 their element offsets, v0 / v1 whether they exist, pair: same row
-__device__ __forceinline__ double2 load_pair(const double* __restrict__ p, size_t k0, size_t k1, bool v0, bool v1, bool pair) {
-    if (pair && (((uintptr_t)(p + k0)) & 15u) == 0) return *reinterpret_cast<const double2*>(p + k0);
-    double2 r{0.0, 0.0};
-    if (v0) r.x = p[k0];
-    if (v1) r.y = p[k1];
-    return r;
-}
 
 template <int NE>
 __global__ __launch_bounds__(INTEGRALS_BLOCK) void integrals_tile_kernel(IntegralArgs K, GridDesc G, unsigned n_cells,
@@ -77,33 +63,19 @@ __global__ __launch_bounds__(INTEGRALS_BLOCK) void integrals_tile_kernel(Integra
 #pragma unroll
         for (int u = 0; u < INTEGRALS_PAIRS; ++u) {
             const unsigned c0 = tile * (unsigned)INTEGRALS_TILE + 2u * (t + (unsigned)(u * INTEGRALS_BLOCK));
-            const bool v0 = c0 < n_cells, v1 = c0 + 1u < n_cells;
-            const unsigned j0 = v0 ? c0 / (unsigned)G.nx : 0u, i0 = v0 ? c0 - j0 * (unsigned)G.nx : 0u;
-            const bool wrap = i0 + 1u == (unsigned)G.nx;
-            const unsigned j1 = wrap ? j0 + 1u : j0, i1 = wrap ? 0u : i0 + 1u;
-            const size_t k0 = (size_t)(j0 + G.hy) * (size_t)G.sj + (size_t)(i0 + G.hx);
-            const size_t k1 = v1 ? (size_t)(j1 + G.hy) * (size_t)G.sj + (size_t)(i1 + G.hx) : k0;
-            const bool pair = v1 && !wrap;
-
-            bool s0 = v0, s1 = v1;                          // wet
-            if (K.mask != nullptr && K.mask_kind == CF_MASK_U8) {
-                const uint8_t* m = (const uint8_t*)K.mask;
-                if (v0) s0 = m[k0] != 0;
-                if (v1) s1 = m[k1] != 0;
-            } else if (K.mask != nullptr && K.mask_kind == CF_MASK_BOTTOM_HEIGHT) {
-                const double2 zb = load_pair((const double*)K.mask, k0, k1, v0, v1, pair);
-                s0 = v0 && !(K.z_surface <= zb.x);
-                s1 = v1 && !(K.z_surface <= zb.y);
-            }
+            const CellPair C = cell_pair<true>(c0, n_cells, G);
+            const bool v0 = C.v0, v1 = C.v1;
+            const size_t k0 = C.k0, k1 = C.k1;
+            const PairWet wet = pair_wet(K.mask, K.mask_kind, K.z_surface, C);
             unsigned r0 = v0 ? 1u : 0u, r1 = v1 ? 1u : 0u;  // region bits
             if (K.region != nullptr) {
                 r0 = v0 ? K.region[k0] : 0u;
                 r1 = v1 ? K.region[k1] : 0u;
             }
             double2 A{1.0, 1.0};
-            if (K.area != nullptr) A = load_pair(K.area, k0, k1, v0, v1, pair);
+            if (K.area != nullptr) A = load_pair(K.area, C);
 #pragma unroll 4
-            for (int f = 0; f < K.n_fields; ++f) stage[f * INTEGRALS_BLOCK + t] = load_pair(K.field[f], k0, k1, v0, v1, pair);
+            for (int f = 0; f < K.n_fields; ++f) stage[f * INTEGRALS_BLOCK + t] = load_pair(K.field[f], C);
 
 #pragma unroll
             for (int e = 0; e < NE; ++e) {
@@ -126,8 +98,8 @@ __global__ __launch_bounds__(INTEGRALS_BLOCK) void integrals_tile_kernel(Integra
                         }
                     }
                     const unsigned bits = d >> 24;
-                    const double term0 = (s0 && (r0 & bits) != 0u) ? x.x * A.x : 0.0;
-                    const double term1 = (s1 && (r1 & bits) != 0u) ? x.y * A.y : 0.0;
+                    const double term0 = (wet.s0 && (r0 & bits) != 0u) ? x.x * A.x : 0.0;
+                    const double term1 = (wet.s1 && (r1 & bits) != 0u) ? x.y * A.y : 0.0;
                     acc[e] = (acc[e] + term0) + term1;
                 }
             }

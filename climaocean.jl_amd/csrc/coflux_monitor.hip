@@ -20,10 +20,12 @@
 // Traffic: 8 bytes per cell and entry, each field cell loaded once per collection; the mask is read once per ENTRY, not once
 // per cell (n_entries · (1 | 8) bytes per cell: the price of one entry per workgroup, which keeps the running values at 16
 // registers).  Excluded cells are selected away: only the hash reads them.
+// The pair of cells, its loads and its wet test are coflux_surface_cells.hpp's.
 #include <algorithm>
 
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
+#include "coflux_surface_cells.hpp"
 
 namespace coflux {
 
@@ -119,17 +121,6 @@ __device__ __forceinline__ void put_partial(MonitorPartial* p, const MonitorPart
     w[4] = (uint64_t)R.nan_count, w[5] = (uint64_t)R.inf_count, w[6] = (uint64_t)R.first_nonfinite, w[7] = R.hash;
 }
 
-// the two cells of a thread as raw bits: k0 / k1 their element offsets, v0 / v1 whether they exist, pair: same row
-// (the rule of load_pair in coflux_integrals.hip)
-__device__ __forceinline__ ulonglong2 load_pair_bits(const double* __restrict__ p, size_t k0, size_t k1, bool v0, bool v1, bool pair) {
-    const unsigned long long* q = reinterpret_cast<const unsigned long long*>(p);
-    if (pair && (((uintptr_t)(q + k0)) & 15u) == 0) return *reinterpret_cast<const ulonglong2*>(q + k0);
-    ulonglong2 r{0ull, 0ull};
-    if (v0) r.x = q[k0];
-    if (v1) r.y = q[k1];
-    return r;
-}
-
 __global__ __launch_bounds__(MONITOR_BLOCK) void monitor_pass_kernel(MonitorArgs K, GridDesc G, unsigned n_cells, unsigned n_pairs) {
     __shared__ MonitorPartial wave_part[MONITOR_WAVES];
     const unsigned t = threadIdx.x;
@@ -141,30 +132,16 @@ __global__ __launch_bounds__(MONITOR_BLOCK) void monitor_pass_kernel(MonitorArgs
         MonitorPartial R = empty_partial();
         for (unsigned p = slice * (unsigned)MONITOR_BLOCK + t; p < n_pairs; p += slices * (unsigned)MONITOR_BLOCK) {
             const unsigned c0 = 2u * p;                      // p < n_pairs: c0 < n_cells
-            const bool v1 = c0 + 1u < n_cells;
-            const unsigned j0 = c0 / (unsigned)G.nx, i0 = c0 - j0 * (unsigned)G.nx;
-            const bool wrap = i0 + 1u == (unsigned)G.nx;
-            const unsigned j1 = wrap ? j0 + 1u : j0, i1 = wrap ? 0u : i0 + 1u;
-            const size_t k0 = (size_t)(j0 + G.hy) * (size_t)G.sj + (size_t)(i0 + G.hx);
-            const size_t k1 = v1 ? (size_t)(j1 + G.hy) * (size_t)G.sj + (size_t)(i1 + G.hx) : k0;
-            const bool pair = v1 && !wrap;
-            const ulonglong2 x = load_pair_bits(E.a, k0, k1, true, v1, pair);
-            bool s0 = true, s1 = v1;                         // wet
-            if (K.mask != nullptr && K.mask_kind == CF_MASK_U8) {
-                const uint8_t* m = (const uint8_t*)K.mask;
-                s0 = m[k0] != 0;
-                if (v1) s1 = m[k1] != 0;
-            } else if (K.mask != nullptr && K.mask_kind == CF_MASK_BOTTOM_HEIGHT) {
-                const ulonglong2 zb = load_pair_bits((const double*)K.mask, k0, k1, true, v1, pair);
-                s0 = !(K.z_surface <= __longlong_as_double((long long)zb.x));
-                s1 = v1 && !(K.z_surface <= __longlong_as_double((long long)zb.y));
-            }
+            const CellPair C = cell_pair<false>(c0, n_cells, G);
+            const bool v1 = C.v1;
+            const ulonglong2 x = load_pair_bits(E.a, C);
+            const PairWet wet = pair_wet(K.mask, K.mask_kind, K.z_surface, C);
             const int64_t c = K.first_cell + (int64_t)c0;
             const uint64_t h0 = HASH_K * (uint64_t)(c + 1);
             R.hash += mix64(x.x ^ h0);
-            take(R, x.x, c, s0, absolute);
+            take(R, x.x, c, wet.s0, absolute);
             if (v1) R.hash += mix64(x.y ^ (h0 + HASH_K));
-            take(R, x.y, c + 1, s1, absolute);
+            take(R, x.y, c + 1, wet.s1, absolute);
         }
         R = wave_merge(R);
         if ((t & 63u) == 0u) put_partial(&wave_part[t >> 6], R);

@@ -57,6 +57,21 @@ struct DeviceBuffer : Owned<void*, hipFree> {
     T* get() const { return static_cast<T*>(Owned::get()); }
 };
 
+// One allocation carved into pieces: add() each piece's bytes in order and keep the offset it returns, create bytes, then
+// at<T>(base, offset).  Every piece starts 16-byte aligned within the allocation.
+struct Layout {
+    size_t bytes = 0;
+    size_t add(size_t n) {
+        const size_t at = bytes;
+        bytes += (n + 15) & ~(size_t)15;
+        return at;
+    }
+    template <class T>
+    static T* at(void* base, size_t offset) {
+        return reinterpret_cast<T*>(static_cast<unsigned char*>(base) + offset);
+    }
+};
+
 template <class T = void>
 struct PinnedBuffer : Owned<void*, hipHostFree> {
     hipError_t create(size_t bytes) { return keep(hipHostMalloc(fresh(), bytes, hipHostMallocDefault)); }

@@ -5,20 +5,6 @@
 // operator has rows of several segments.
 #include "coflux_ctx.hpp"
 
-namespace {
-
-// the device block is laid out piece by piece, every piece 16-byte aligned
-struct Layout {
-    size_t bytes = 0;
-    size_t add(size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 15) & ~(size_t)15;
-        return at;
-    }
-};
-
-}  // namespace
-
 extern "C" {
 
 int cf_regrid_create(cf_ctx* ctx, const cf_regrid_desc* desc, cf_regrid** out) {
@@ -75,7 +61,7 @@ int cf_regrid_create(cf_ctx* ctx, const cf_regrid_desc* desc, cf_regrid** out) {
     }
     while (short_rows.size() % 4 != 0) short_rows.push_back(REGRID_NONE);
 
-    Layout L;
+    cf::Layout L;   // the device block, piece by piece
     const size_t at_weight = L.add((size_t)nnz * sizeof(double));
     const size_t at_segments = L.add(segments.size() * sizeof(RegridSegment));
     const size_t at_long = L.add(long_rows.size() * sizeof(RegridLongRow));
@@ -107,13 +93,13 @@ int cf_regrid_create(cf_ctx* ctx, const cf_regrid_desc* desc, cf_regrid** out) {
     rg->max_blocks = desc->max_workgroups;
     rg->d_block = std::move(block);
     RegridTables& T = rg->tables;
-    T.weight = reinterpret_cast<const double*>(d + at_weight);
-    T.segments = reinterpret_cast<const RegridSegment*>(d + at_segments);
-    T.long_rows = reinterpret_cast<const RegridLongRow*>(d + at_long);
-    T.offset = reinterpret_cast<const uint32_t*>(d + at_offset);
-    T.row_start = reinterpret_cast<const uint32_t*>(d + at_row);
-    T.short_rows = reinterpret_cast<const uint32_t*>(d + at_short);
-    T.partial = reinterpret_cast<double*>(d + at_partial);
+    T.weight = cf::Layout::at<const double>(d, at_weight);
+    T.segments = cf::Layout::at<const RegridSegment>(d, at_segments);
+    T.long_rows = cf::Layout::at<const RegridLongRow>(d, at_long);
+    T.offset = cf::Layout::at<const uint32_t>(d, at_offset);
+    T.row_start = cf::Layout::at<const uint32_t>(d, at_row);
+    T.short_rows = cf::Layout::at<const uint32_t>(d, at_short);
+    T.partial = cf::Layout::at<double>(d, at_partial);
     T.mask_kind = desc->mask ? ctx->dev.mask_kind : CF_MASK_NONE;
     T.mask = T.mask_kind == CF_MASK_NONE ? nullptr : desc->mask;
     T.z_surface = ctx->dev.z_surface;

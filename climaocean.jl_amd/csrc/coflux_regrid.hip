@@ -23,11 +23,13 @@
 //
 // The field loop is unrolled over the compile-time bucket KB (1 / 4 / 8 / 16), so the accumulators and the field pointers
 // have static indices: no scratch.  No LDS, no barrier: a wave never waits for another.
+// The butterfly is coflux_surface_cells.hpp's butterfly_sum<W>.
 #include <algorithm>
 #include <cmath>
 
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
+#include "coflux_surface_cells.hpp"
 
 namespace coflux {
 
@@ -37,14 +39,6 @@ constexpr int REGRID_BLOCK = 256;
 constexpr int REGRID_WAVES = REGRID_BLOCK / 64;
 constexpr int REGRID_TERMS = 4;          // entries per lane of a group (16 lanes · 4 = REGRID_SHORT) or segment (64 · 4)
 static_assert(16 * REGRID_TERMS == REGRID_SHORT && 64 * REGRID_TERMS == REGRID_SEGMENT, "a lane owns four entries");
-
-template <int W>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int off = W / 2; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
 
 // Lane g of W adds its four entries of [start, start + count) — count ≤ 4 W — and the group is combined: N[f], D.
 template <int KB, int W>
@@ -67,7 +61,7 @@ __device__ __forceinline__ void regrid_span(const RegridTables& T, const RegridF
     double d = 0.0;
 #pragma unroll
     for (int u = 0; u < REGRID_TERMS; ++u) d = d + (wet[u] ? w[u] : 0.0);
-    D = group_sum<W>(d);
+    D = butterfly_sum<W>(d);
 #pragma unroll
     for (int f = 0; f < KB; ++f) {
         N[f] = 0.0;
@@ -79,7 +73,7 @@ __device__ __forceinline__ void regrid_span(const RegridTables& T, const RegridF
             double a = 0.0;
 #pragma unroll
             for (int u = 0; u < REGRID_TERMS; ++u) a = a + (wet[u] ? w[u] * t[u] : 0.0);
-            N[f] = group_sum<W>(a);
+            N[f] = butterfly_sum<W>(a);
         }
     }
 }

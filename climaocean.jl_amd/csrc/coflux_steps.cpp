@@ -5,7 +5,7 @@
 //   * cf_time_steps: run!(simulation) of a prescribed-ocean coupled model without returning to the host language.
 #include <map>
 
-#include "coflux_ctx.hpp"
+#include "coflux_series.hpp"
 
 // Mailboxes exported by contexts of THIS process: a handle that comes back to the process that made it cannot be
 // opened through HIP IPC (and need not be): the pointer is used as is.  Several slabs per process happen in tests
@@ -302,8 +302,8 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         s.time_fraction = total - whole;
         return s;
     };
-    CHECK(integrals_room(ctx, first_step, nsteps));   // a series that would overflow: nothing is launched
-    CHECK(monitor_room(ctx, first_step, nsteps));
+    CHECK(series_room(ctx, ctx->integrals, first_step, nsteps, "integrator"));   // a series that would overflow: nothing is launched
+    CHECK(series_room(ctx, ctx->monitor, first_step, nsteps, "monitor"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (int n = 0; n < S->n_ocean_states; ++n) {
         if (ctx->dev.mask_kind != CF_MASK_NONE && !S->ocean_states[n].mask) return fail(ctx, CF_ERR_INVALID, "ocean state %d has no mask", n);
@@ -382,12 +382,9 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         // the same steps.  Queued behind every launch of the step — the face stresses of the merged and tail forms included
         if (ctx->average && (step + 1) % ctx->average_stride == 0)
             CHECK(average_collect(ctx->average, ctx->average_stride * ctx->average_step_weight));
-        // an attached integrator (cf_attach_integrals): the same rule, one record per collected step
-        if (ctx->integrals && (step + 1) % ctx->integrals_stride == 0)
-            CHECK(integrals_collect(ctx->integrals, ctx->integrals_time_origin + (double)(step + 1) * ctx->integrals_step_seconds));
-        // an attached monitor (cf_attach_monitor): the same rule again, after both
-        if (ctx->monitor && (step + 1) % ctx->monitor_stride == 0)
-            CHECK(monitor_collect(ctx->monitor, ctx->monitor_time_origin + (double)(step + 1) * ctx->monitor_step_seconds));
+        // an attached integrator, then an attached monitor (SeriesAttachment): the same rule, one record per collected step
+        if (ctx->integrals.collects(step)) CHECK(cf_integrals_collect(ctx->integrals.handle, ctx->integrals.stamp(step)));
+        if (ctx->monitor.collects(step)) CHECK(cf_monitor_collect(ctx->monitor.handle, ctx->monitor.stamp(step)));
     }
     return CF_OK;
 }
