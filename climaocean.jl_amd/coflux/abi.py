@@ -254,6 +254,12 @@ class RegridDesc(C.Structure):
                 ("max_workgroups", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PrefetchStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("pending", C.c_int32)] + [(n, C.c_uint64) for n in (
+        "requests", "launched_aux", "launched_tail", "launched_merged", "launched_ice_tail", "launched_own",
+        "consumed", "mismatched", "voided", "superseded", "discarded", "step_interpolations")]
+
+
 # Every symbol include/coflux.h declares (tests check they are all exported).
 EXPORTED_SYMBOLS = (
     "cf_version", "cf_default_flux_params", "cf_create", "cf_destroy", "cf_last_error",
@@ -273,6 +279,7 @@ EXPORTED_SYMBOLS = (
     "cf_window_create", "cf_window_destroy", "cf_window_host_buffer", "cf_window_wait_slot", "cf_window_commit",
     "cf_window_upload", "cf_window_find", "cf_window_source",
     "cf_ensure_chunk_table", "cf_debug_chunk_table", "cf_debug_interp_grid", "cf_debug_land_zero_launches", "cf_solver_path", "cf_solver_iteration_path", "cf_solver_latency_layout", "cf_comm_count", "cf_build_stamp", "cf_discard_prefetched_atmosphere_state",
+    "cf_debug_prefetch_stats",
     "cf_average_create", "cf_average_destroy", "cf_average_reset", "cf_average_collect", "cf_average_weight", "cf_attach_average",
     "cf_average_create_derived",
     "cf_integrals_create", "cf_integrals_destroy", "cf_integrals_collect", "cf_integrals_count", "cf_integrals_read",
@@ -342,6 +349,7 @@ def load_library(path=None):
     lib.cf_solver_latency_layout.argtypes = [vp, C.POINTER(C.c_int)]
     lib.cf_peer_halo_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     lib.cf_discard_prefetched_atmosphere_state.argtypes = [vp]
+    lib.cf_debug_prefetch_stats.argtypes = [vp, C.POINTER(PrefetchStats)]
     lib.cf_comm_count.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.cf_debug_eval.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     lib.cf_debug_chunk_plan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]

@@ -386,6 +386,15 @@ class FluxContext:
         """Forget requested-ahead atmosphere states (cf_discard_prefetched_atmosphere_state): on leaving a stepping loop."""
         self._check(self.lib.cf_discard_prefetched_atmosphere_state(self._h), "cf_discard_prefetched_atmosphere_state")
 
+    def prefetch_stats(self):
+        """Which way every requested-ahead atmosphere state went since the context was made (cf_debug_prefetch_stats), as a
+        dict of ints: requests, launched_aux / _tail / _merged / _ice_tail / _own, consumed, mismatched, voided, superseded,
+        discarded, step_interpolations and pending.  requests = the five endings + pending, always."""
+        st = abi.PrefetchStats()
+        st.struct_size = C.sizeof(abi.PrefetchStats)
+        self._check(self.lib.cf_debug_prefetch_stats(self._h, C.byref(st)), "cf_debug_prefetch_stats")
+        return {n: int(getattr(st, n)) for n, _ in abi.PrefetchStats._fields_ if n != "struct_size"}
+
     def make_schedule(self, ocean_states, atmos_sets, *, first_level=0, time_fraction=0.0, time_fraction_increment=0.0,
                       pipeline=False, halo_backend=abi.HALO_NONE, halo_rows=0, fold_north=False):
         """cf_run_schedule for cf_time_steps; keeps the ctypes arrays alive on the returned object."""

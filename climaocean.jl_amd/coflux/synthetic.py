@@ -136,16 +136,18 @@ def sea_ice_state(nx, ny, hx, hy, *, ny_global=None, j_offset=0, latitude=(-70.0
     return {k: np.ascontiguousarray(a) for k, a in out.items()}
 
 
-def jra55_snapshots(n_levels=2, nsx=JRA55_NX, nsy=JRA55_NY, seed=SEED, temporal_correlation=None):
+def jra55_snapshots(n_levels=2, nsx=JRA55_NX, nsy=JRA55_NY, seed=SEED, temporal_correlation=None, rows=None):
     """Synthetic JRA55 window: dict var -> float32 [n_levels, nsy, nsx] (jra55_data_staging.jl:8).
     Default: the snapshots are independent draws (every test and golden vector uses this).  With
     `temporal_correlation` = ρ the noise of consecutive 3-hourly snapshots is correlated ρ (a rotation by
     arccos ρ per snapshot in the plane of two independent fields, so every snapshot keeps the same marginal
-    distribution): synoptic fields decorrelate over days, not hours, and bench.py steps the clock through them."""
+    distribution): synoptic fields decorrelate over days, not hours, and bench.py steps the clock through them.
+    `rows` = (first, end): only those source rows, the same values as in the whole window (every value is a function of
+    its own indices)."""
     i = np.arange(nsx)[None, :]
-    j = np.arange(nsy)[:, None]
+    j = np.arange(*(rows or (0, nsy)))[:, None]
     phi = JRA55_LAT0 + j * (2 * 89.57 / (nsy - 1)) + 0 * i
-    out = {k: np.empty((n_levels, nsy, nsx), np.float32)
+    out = {k: np.empty((n_levels, j.shape[0], nsx), np.float32)
            for k in ("tas", "huss", "psl", "uas", "vas", "rlds", "rsds", "prra", "prsn")}
     if temporal_correlation is None:
         noise = normal

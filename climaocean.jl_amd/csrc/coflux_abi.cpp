@@ -746,6 +746,18 @@ int cf_debug_chunk_table(cf_ctx* ctx, int* begins, int* wet_counts, int capacity
     return CF_OK;
 }
 
+// self-test hook: which way every atmosphere state requested ahead went (tests/test_prefetch_sequences.py)
+int cf_debug_prefetch_stats(cf_ctx* ctx, cf_prefetch_stats* out) {
+    if (!ctx || !out) return fail(ctx, CF_ERR_INVALID, "cf_debug_prefetch_stats: bad arguments");
+    if (out->struct_size != (int32_t)sizeof(cf_prefetch_stats))
+        return fail(ctx, CF_ERR_INVALID, "cf_prefetch_stats.struct_size = %d, library expects %zu", out->struct_size, sizeof(cf_prefetch_stats));
+    *out = ctx->prefetch_stats;
+    out->struct_size = (int32_t)sizeof(cf_prefetch_stats);
+    out->pending = ctx->deferred.valid ? 1 : 0;
+    for (const auto& p : ctx->prefetch) out->pending += p.valid ? 1 : 0;
+    return CF_OK;
+}
+
 // self-test hook: the land-zero bookkeeping of the last cf_time_steps call (tests/test_land_zeros.py)
 int cf_debug_land_zero_launches(cf_ctx* ctx, int* launches) {
     if (!ctx || !launches) return fail(ctx, CF_ERR_INVALID, "cf_debug_land_zero_launches: bad arguments");
@@ -842,18 +854,14 @@ int cf_compute_net_ocean_fluxes(cf_ctx* ctx, const cf_ocean_surface* ocean, cons
 
 // A deferred next-step interpolation (cf_prefetch_atmosphere_state) that has just been launched on the MAIN stream — as the
 // solver launch's tail workgroups, inside the face-stress launch, or as a plain launch: stream order replaces the event.
-int deferred_went_out_on_main(cf_ctx* ctx) {
-    cf_ctx::Prefetch* slot = nullptr;
-    for (auto& p : ctx->prefetch)
-        if (p.valid && p.key == ctx->deferred.out.u) slot = &p;
-    if (!slot)
-        for (auto& p : ctx->prefetch)
-            if (!p.valid) slot = &p;
+int deferred_went_out_on_main(cf_ctx* ctx, uint64_t* route) {
+    cf_ctx::Prefetch* slot = ctx->prefetch_slot(ctx->deferred.out.u);
+    // (never taken: the request was refused when it was made, cf_prefetch_atmosphere_state — a kernel has been launched by now)
     if (!slot) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
+    ++*route;
     slot->key = ctx->deferred.out.u;
-    slot->level1 = ctx->deferred.src.level1;
-    slot->level2 = ctx->deferred.src.level2;
-    slot->tf = ctx->deferred.src.time_fraction;
+    slot->src = ctx->deferred.src;
+    slot->w = ctx->deferred.w;
     slot->valid = true;
     slot->on_main = true;
     ctx->deferred.valid = false;
@@ -889,14 +897,18 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     for (auto& p : ctx->prefetch) {
         if (!p.valid || p.key != atmos->u) continue;
         if (!p.on_main) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p.done, 0));  // also orders a mismatched prefetch before our writes
-        prefetched = p.level1 == src->level1 && p.level2 == src->level2 && p.tf == src->time_fraction;
+        prefetched = same_interpolation(p.src, p.w, *src, *w);
         p.valid = false;
+        ++(prefetched ? ctx->prefetch_stats.consumed : ctx->prefetch_stats.mismatched);
     }
     // Fused forms.  Net fluxes: the cell-local part of compute_net_ocean_fluxes! (everything but the two face stresses,
     // which need the west / south neighbour's ρτ) is computed in the solver's epilogue from registers, and a thin stress
     // kernel follows — bitwise the same numbers as the three-launch sequence (shared arithmetic, contraction off).
     const bool fuse = net_fluxes_fused(ctx);
-    if (!prefetched) HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, src, w, atmos));
+    if (!prefetched) {
+        HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, src, w, atmos));
+        ++ctx->prefetch_stats.step_interpolations;
+    }
     if (rec) HIP_TRY(ctx, hipEventRecord(ev[1].get(), ctx->stream));
     CHECK(wait_for_halos(ctx));  // the interpolation above overlapped the halo rows
     // CF_OPT_MERGED_PREFETCH = 2: a requested next-step interpolation becomes the TAIL workgroups of this solver launch
@@ -963,7 +975,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
         else
             HIP_TRY(ctx, launch_ly_fluxes_with_tail(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
                                                     ctx->d_land_freshwater, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out, rows, blocks));
-        CHECK(deferred_went_out_on_main(ctx));
+        CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_tail));
     } else
     HIP_TRY(ctx, launch_ao_fluxes(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes,
                                   fuse ? ice : nullptr, fuse ? net : nullptr, ctx->d_land_freshwater));
@@ -979,7 +991,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     if (merge) {
         HIP_TRY(ctx, launch_interpolate_and_stress(ctx->stream, ctx->launch, ctx->dev, ctx->grid, &ctx->deferred.src, &ctx->deferred.w,
                                                    &ctx->deferred.out, ocean, fluxes, ice, net));
-        CHECK(deferred_went_out_on_main(ctx));
+        CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_merged));
     } else if (fuse && hold_tail_work) {
         if (stress_held) *stress_held = true;   // (the caller's next launch carries them)
     } else if (fuse)
@@ -994,7 +1006,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
         // neither merged form applies to this step (another solver kernel, un-fused net fluxes …): the requested interpolation
         // goes out as a launch of its own on the same stream — the sequence of an un-pipelined step, one step early
         HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out));
-        CHECK(deferred_went_out_on_main(ctx));
+        CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_own));
     }
     if (ctx->step_loop.open) ctx->step_loop.last_way = way;   // (every launch of the step is queued: the next step may rely on its land)
     return CF_OK;
@@ -1407,10 +1419,10 @@ int cf_update_state_sea_ice(cf_ctx* ctx, const cf_atmos_source* src, const cf_in
                        net_in_epilogue ? net_ice->top_heat : nullptr, net_in_epilogue ? net_ice->bottom_heat : nullptr};
     CHECK(atmosphere_sea_ice_fluxes_impl(ctx, ice_state, ocean, atmos, ai_fluxes, any_tail ? &T : nullptr, net_in_epilogue ? &NI : nullptr));
     if (stress_after) HIP_TRY(ctx, launch_net_stress(ctx->stream, ctx->dev, ctx->grid, ocean, ao_fluxes, ice_partition, net));
-    if (interp_rides) CHECK(deferred_went_out_on_main(ctx));
+    if (interp_rides) CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_ice_tail));
     if (ice_tail && ctx->deferred.valid && ctx->deferred.out.u != atmos->u) {   // (no tiled interpolation configured: a launch of its own)
         HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out));
-        CHECK(deferred_went_out_on_main(ctx));
+        CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_own));
     }
     if (net_in_epilogue) return CF_OK;
     return cf_compute_net_sea_ice_fluxes(ctx, ice_state, ocean, atmos, ai_fluxes, frazil_heat, interface_heat, net_ice);

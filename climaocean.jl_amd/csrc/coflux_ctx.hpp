@@ -143,8 +143,8 @@ struct cf_ctx {
     } aux;
     struct Prefetch {
         const double* key = nullptr;  // exchange set, identified by its u pointer
-        int level1 = 0, level2 = 0;
-        double tf = 0.0;
+        cf_atmos_source src{};        // what was interpolated: the source's arrays and shape, the levels and the fraction …
+        cf_interp_weights w{};        // … through which map (same_interpolation compares both with what a step asks for)
         hipEvent_t done = nullptr;    // a view of aux.done[k]: NULL until the auxiliary lane exists
         bool valid = false;
         bool on_main = false;         // launched on the main stream (merged with the face stresses): stream order, no event
@@ -159,6 +159,17 @@ struct cf_ctx {
         cf_interp_weights w{};
         cf_exchange_fields out{};
     } deferred;
+    // which way every request went (cf_debug_prefetch_stats): plain host counters, bumped where the decision is taken.
+    // requests = consumed + mismatched + voided + superseded + discarded + pending, at every point (`pending` is counted on demand)
+    cf_prefetch_stats prefetch_stats{};
+    // the record a state for exchange set `key` would be booked in: the one that holds that set, else a free one, else NULL
+    Prefetch* prefetch_slot(const double* key) {
+        for (auto& p : prefetch)
+            if (p.valid && p.key == key) return &p;
+        for (auto& p : prefetch)
+            if (!p.valid) return &p;
+        return nullptr;
+    }
     // peer-direct halo rows (coflux_halo.hip)
     PeerMailbox peer{};                                  // raw views of the three below
     cf::DeviceBuffer<char> peer_mine;                    // this context's mailbox (fine-grained)
@@ -256,8 +267,20 @@ int cf_fail(cf_ctx* ctx, int code, const char* fmt, ...);
 extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows);
 // coflux_average.cpp: one collection of `a` (cf_average_collect without the argument checks of the ABI entry)
 int average_collect(cf_average* a, double weight);
-// coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state)
-extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx);
+// coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state); *route is the counter of
+// ctx->prefetch_stats that names the launch it left in
+extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx, uint64_t* route);
+
+// Whether the atmosphere state requested ahead from (a, wa) is the one a step asks for with (b, wb): the same source arrays and
+// shape, levels and time fraction, through the same map.  Levels and fraction alone do not say so: two snapshot windows, a
+// re-bound in-memory atmosphere or a second weight map give another field under the same clock.
+inline bool same_interpolation(const cf_atmos_source& a, const cf_interp_weights& wa, const cf_atmos_source& b, const cf_interp_weights& wb) {
+    for (int v = 0; v < CF_JRA55_NVARS; ++v)
+        if (a.data[v] != b.data[v]) return false;
+    return a.ns_x == b.ns_x && a.ns_y == b.ns_y && a.n_levels == b.n_levels && a.level1 == b.level1 && a.level2 == b.level2 &&
+           a.time_fraction == b.time_fraction && wa.separable == wb.separable && wa.fi == wb.fi && wa.fj == wb.fj &&
+           wa.cos_rot == wb.cos_rot && wa.sin_rot == wb.sin_rot && wa.latitude == wb.latitude;
+}
 
 // whether two ocean-grid fields (halos included) at p and q share bytes: what the averagers refuse between a mean and anything else
 inline bool fields_overlap(const GridDesc& G, const void* p, const void* q) {

@@ -28,12 +28,8 @@ static int ensure_aux_stream(cf_ctx* ctx) {
 // Launch the interpolation of `src` into `out` on the auxiliary stream, gated on the lane's gate event (recorded by the caller
 // on the main stream at the point after which `out` is free to be overwritten).
 int cf_launch_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w, const cf_exchange_fields* out) {
-    cf_ctx::Prefetch* rec = nullptr;
-    for (auto& p : ctx->prefetch)
-        if (p.valid && p.key == out->u) rec = &p;
-    if (!rec)
-        for (auto& p : ctx->prefetch)
-            if (!p.valid) rec = &p;
+    cf_ctx::Prefetch* rec = ctx->prefetch_slot(out->u);
+    // (never taken: request_prefetch refuses a request that would find no record, before anything is launched or booked)
     if (!rec) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
     if (!ctx->deferred.gated) HIP_TRY(ctx, hipEventRecord(ctx->aux.ev_gate.get(), ctx->stream));  // (a later gate than needed: still ordered)
     ctx->deferred.gated = false;
@@ -42,10 +38,10 @@ int cf_launch_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_
     // the CU's LDS and 456 of 512 registers per SIMD; the tiled kernel would wait for them to retire
     HIP_TRY(ctx, launch_interpolate_background(ctx->aux.stream.get(), ctx->grid, src, w, out));
     HIP_TRY(ctx, hipEventRecord(rec->done, ctx->aux.stream.get()));
+    ++ctx->prefetch_stats.launched_aux;
     rec->key = out->u;
-    rec->level1 = src->level1;
-    rec->level2 = src->level2;
-    rec->tf = src->time_fraction;
+    rec->src = *src;
+    rec->w = *w;
     rec->valid = true;
     rec->on_main = false;
     return CF_OK;
@@ -61,6 +57,20 @@ int cf_flush_deferred_prefetch(cf_ctx* ctx) {
 
 static int request_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
                             const cf_exchange_fields* out, bool defer);
+
+// An earlier state of the exchange set `key` that no step asked for (another clock, a switch of CF_OPT_MERGED_PREFETCH in
+// between): a new request into that set supersedes it, now — the set never has two states on the books.  One that went out on
+// the auxiliary stream: whichever stream writes the set next — the main stream in the merged forms — is ordered behind that
+// kernel.  One that went out on the main stream: stream order and the new request's gate are the order.
+static int supersede_states(cf_ctx* ctx, const double* key) {
+    for (auto& p : ctx->prefetch)
+        if (p.valid && p.key == key) {
+            if (!p.on_main && p.done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p.done, 0));
+            p.valid = false;
+            ++ctx->prefetch_stats.superseded;
+        }
+    return CF_OK;
+}
 
 extern "C" {
 
@@ -85,14 +95,11 @@ static int request_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_in
     CHECK(ensure_aux_stream(ctx));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     CHECK(cf_flush_deferred_prefetch(ctx));  // at most one request waits for a solver launch
-    // An earlier request into the SAME exchange set that went out on the auxiliary stream and was never consumed (another
-    // clock, a switch of CF_OPT_MERGED_PREFETCH in between): this request supersedes it, and whichever stream writes the
-    // set next — the main stream in the merged forms — is ordered behind that kernel
-    for (auto& p : ctx->prefetch)
-        if (p.valid && !p.on_main && p.key == out->u) {
-            if (p.done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p.done, 0));
-            p.valid = false;
-        }
+    // two states of OTHER sets are pending: there is no record for this one.  Refused here, where nothing has been launched or
+    // booked for it — not behind the launch that would carry it, whose writes would then be on nobody's books
+    if (!ctx->prefetch_slot(out->u)) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
+    CHECK(supersede_states(ctx, out->u));
+    ++ctx->prefetch_stats.requests;
     // the set written was last read by kernels already queued on the main stream: everything queued so far gates it.
     // With CF_OPT_MERGED_PREFETCH the request leaves inside a main-stream launch (stream order is the gate) and an event
     // per step would only put a barrier packet into the queue; the rare flush to the auxiliary stream records it then.
@@ -265,12 +272,14 @@ int cf_fold_north_halo(cf_ctx* ctx, double* const* d_fields, const int* location
 int cf_discard_prefetched_atmosphere_state(cf_ctx* ctx) {
     if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->deferred.valid) ++ctx->prefetch_stats.discarded;
     ctx->deferred.valid = false;   // requested, not launched: never will be
     for (auto& p : ctx->prefetch)
         if (p.valid) {
             // launched on the auxiliary stream: whatever the caller does to that exchange set next is ordered behind it
             if (!p.on_main && p.done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p.done, 0));
             p.valid = false;
+            ++ctx->prefetch_stats.discarded;
         }
     return CF_OK;
 }
@@ -279,7 +288,7 @@ int cf_discard_prefetched_atmosphere_state(cf_ctx* ctx) {
 int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_schedule* S, const cf_atmos_source* src,
                   const cf_interp_weights* w, const cf_interface_fluxes* fluxes, const cf_sea_ice_fields* ice,
                   const cf_net_ocean_fluxes* net) {
-    if (!ctx || !S || !src) return fail(ctx, CF_ERR_INVALID, "cf_time_steps: NULL argument");
+    if (!ctx || !S || !src || !w) return fail(ctx, CF_ERR_INVALID, "cf_time_steps: NULL argument");
     if (S->struct_size != (int32_t)sizeof(cf_run_schedule))
         return fail(ctx, CF_ERR_INVALID, "cf_run_schedule.struct_size = %d, library expects %zu", S->struct_size, sizeof(cf_run_schedule));
     if (nsteps < 0 || first_step < 0 || S->n_ocean_states < 1 || !S->ocean_states || !S->atmos)
@@ -321,22 +330,25 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         const cf_atmos_source s0 = source_at(first_step);
         const cf_exchange_fields* a0 = &S->atmos[first_step % 2];
         bool pending = false;
-        for (auto& p : ctx->prefetch)
-            pending |= p.valid && p.key == a0->u && p.level1 == s0.level1 && p.level2 == s0.level2 && p.tf == s0.time_fraction;
+        for (auto& p : ctx->prefetch) pending |= p.valid && p.key == a0->u && same_interpolation(p.src, p.w, s0, *w);
         if (!pending && ctx->deferred.valid && ctx->deferred.out.u == a0->u) {
-            pending = ctx->deferred.src.level1 == s0.level1 && ctx->deferred.src.level2 == s0.level2 &&
-                      ctx->deferred.src.time_fraction == s0.time_fraction;
+            pending = same_interpolation(ctx->deferred.src, ctx->deferred.w, s0, *w);
             if (pending) CHECK(cf_flush_deferred_prefetch(ctx));
         }
         if (!pending) {
             if (ctx->merged_prefetch != 0) {
                 // the merged forms keep everything on the context's stream: so does the first step's interpolation
                 CHECK(cf_flush_deferred_prefetch(ctx));
+                if (!ctx->prefetch_slot(a0->u)) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
+                // a state of this set that is not the one this step asks for — and may have left on the auxiliary stream, under
+                // CF_OPT_MERGED_PREFETCH = 0 before a switch or by the flush above: the launch below is ordered behind it
+                CHECK(supersede_states(ctx, a0->u));
                 HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &s0, w, a0));
+                ++ctx->prefetch_stats.requests;
                 ctx->deferred.src = s0;
                 ctx->deferred.w = *w;
                 ctx->deferred.out = *a0;
-                CHECK(deferred_went_out_on_main(ctx));
+                CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_own));
             } else {
                 CHECK(request_prefetch(ctx, &s0, w, a0, false));
             }

@@ -86,11 +86,15 @@ int cf_window_commit(cf_window* w, int32_t slot, int64_t time_index) {
     // CF_PIPELINE_CONTINUING) was computed — or would be — from the snapshot this commit replaces: it is void.  The step it
     // was meant for then interpolates again, from the window's current contents.
     for (auto& p : ctx->prefetch)
-        if (p.valid && (p.level1 == slot || p.level2 == slot)) {
+        if (p.valid && (p.src.level1 == slot || p.src.level2 == slot)) {
             if (!p.on_main && p.done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p.done, 0));  // its writes must not race the redo
             p.valid = false;
+            ++ctx->prefetch_stats.voided;
         }
-    if (ctx->deferred.valid && (ctx->deferred.src.level1 == slot || ctx->deferred.src.level2 == slot)) ctx->deferred.valid = false;
+    if (ctx->deferred.valid && (ctx->deferred.src.level1 == slot || ctx->deferred.src.level2 == slot)) {
+        ctx->deferred.valid = false;
+        ++ctx->prefetch_stats.voided;
+    }
     // the device copy of this slot may only be overwritten once every interpolation already queued has read it
     HIP_TRY(ctx, hipEventRecord(w->ev_compute.get(), ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(w->copy_stream.get(), w->ev_compute.get(), 0));

@@ -341,6 +341,21 @@ function debug_land_zero_launches(b)
     return Int(n[])
 end
 
+# self-test hook: which way every atmosphere state requested ahead went since the context was made (cf_prefetch_stats);
+# requests == consumed + mismatched + voided + superseded + discarded + pending at every point
+mutable struct CfPrefetchStats
+    struct_size::Int32; pending::Int32
+    requests::UInt64
+    launched_aux::UInt64; launched_tail::UInt64; launched_merged::UInt64; launched_ice_tail::UInt64; launched_own::UInt64
+    consumed::UInt64; mismatched::UInt64; voided::UInt64; superseded::UInt64; discarded::UInt64
+    step_interpolations::UInt64
+end
+function debug_prefetch_stats(b)
+    st = CfPrefetchStats(Int32(sizeof(CfPrefetchStats)), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+    check(b.ctx, ccall((:cf_debug_prefetch_stats, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfPrefetchStats}), b.ctx, st))
+    return st
+end
+
 # ---- run!(simulation) of a prescribed-ocean model inside the library (bench / offline forcing runs) -------------------
 struct CfRunSchedule
     struct_size::Int32; n_ocean_states::Int32

@@ -45,7 +45,9 @@ extern "C" {
                           * entry point changed, a host finds them by symbol; likewise CF_OPT_INTERP_TILE_ROWS (an experiment option)
                           * and cf_debug_interp_grid, and the sparse surface operator (cf_regrid_*); likewise CF_OPT_LAND_ZEROS and
                           * cf_debug_land_zero_launches — with them cf_time_steps gained a contract on its outputs, stated there;
-                          * likewise the surface monitor (cf_monitor_*, cf_attach_monitor) */
+                          * likewise the surface monitor (cf_monitor_*, cf_attach_monitor); likewise cf_debug_prefetch_stats — with it
+                          * a state requested ahead is matched by its source and weights as well, and a third pending request is
+                          * refused when it is made: both stated at cf_prefetch_atmosphere_state */
 
 /* status codes */
 #define CF_OK 0
@@ -924,7 +926,9 @@ int cf_fold_north_halo(cf_ctx* ctx, double* const* d_fields, const int* location
  *     steps first_step … first_step + nsteps − 1 and nothing else, and leaves the other exchange set as the last-but-one
  *     step left it.
  *   CF_PIPELINE_CONTINUING (2): the last step also requests step first_step + nsteps, for a loop that goes on in the
- *     next call (which recognises the pending state by its output set, levels and time fraction).  The caller
+ *     next call (which recognises the pending state by its output set and by the whole interpolation it asks for — source
+ *     arrays and shape, levels, time fraction and weights, as cf_prefetch_atmosphere_state states; a call that finds anything
+ *     else pending for its first step, or nothing, starts that step's interpolation itself).  The caller
  *     guarantees that the source slots of that step are resident and FINAL when this call is made (a sliding window
  *     must not recommit them in between — cf_window_commit / an upload into a level a pending request reads voids it
  *     silently), and that exchange set (first_step + nsteps) mod 2 is not read after this call's last step: it is
@@ -1323,7 +1327,34 @@ int cf_solver_path(cf_ctx* ctx, int* lean_kernel, int* fused_net);
  * NEXT step's atmosphere state into `out` on the auxiliary stream now; the next cf_update_state whose (levels, time
  * fraction, exchange fields) match finds it done (it waits on an event instead of launching the interpolation).
  * `out` must not be the set the current step's kernels still read.  cf_update_state's signature — the reference
- * seam — is unchanged.                                                                                          */
+ * seam — is unchanged.
+ * The life of a request.  It is PENDING from this call on, and ends in exactly one of five ways:
+ *   consumed    the next cf_update_state / cf_update_state_sea_ice into `out` asks for the same interpolation — the same source
+ *               (its nine data pointers, ns_x, ns_y, n_levels), the same level1, level2 and time_fraction, and the same weights
+ *               (every pointer of cf_interp_weights and `separable`): the step does not interpolate.
+ *   mismatched  that step asks for anything else: it is ordered behind the request's kernel and interpolates itself.
+ *   voided      cf_window_commit rewrites a slot whose NUMBER is level1 or level2 of the request (of whichever source: a false
+ *               void only costs an interpolation).  The next step into `out` interpolates itself, from the new contents.
+ *   superseded  a later request into the same `out` arrives first.
+ *   discarded   cf_discard_prefetched_atmosphere_state.
+ * A step into another exchange set leaves the request pending.  At most one request per exchange set and two in all are
+ * pending: a request into a third set while two others are pending is refused with CF_ERR_INVALID before anything is launched
+ * or booked for it, and the two stay pending (one of them that has not left yet leaves on the auxiliary stream, as it does
+ * before any new request).  While a request is pending the host writes neither `out` nor the source levels it
+ * reads, other than by cf_window_commit.
+ * Where the kernel runs does not change a bit of any result, and depends on CF_OPT_MERGED_PREFETCH at the moment the request
+ * LEAVES, not when it was made.  It leaves with the next step into another set than `out`:
+ *   0  on the auxiliary stream, right behind that step's solver launch;
+ *   1  inside that step's face-stress launch, with or without sea ice (CF_OPT_FUSED_NET ≠ 0 and the default solver);
+ *   2  as tail workgroups of that step's solver launch (cf_update_state, CF_OPT_FUSED_NET ≠ 0 and the default solver), or in
+ *      the tail of the sea-ice interface launch (cf_update_state_sea_ice, whatever CF_OPT_FUSED_NET says);
+ *   1 or 2 where that form does not apply: a launch of its own on the context's stream behind the step.  That is with
+ *      CF_OPT_FUSED_NET = 0 (but for the sea-ice tail), and wherever the tiled interpolation's tile — 4 waves × 9 variables ×
+ *      CF_OPT_INTERP_TILE_CAP doubles of LDS (default 128 cells; an experiment option) — does not fit the launch that would carry
+ *      it: 64 KiB in the face-stress launch (every cap but 0, which turns the tiled interpolation off), 40 KiB in the tail
+ *      workgroups of either solver launch (a cap of 1 … 142 cells).  CF_OPT_INTERP_TILE_ROWS does not enter.
+ * Before such a step it leaves on the auxiliary stream when cf_sync is called, when another request is made, or when the next
+ * step is into `out` itself.  cf_debug_prefetch_stats counts every one of these.                                        */
 int cf_prefetch_atmosphere_state(cf_ctx* ctx, const cf_atmos_source* src_next, const cf_interp_weights* w,
                                  const cf_exchange_fields* out);
 /* Forget every atmosphere state that was requested ahead and not consumed (cf_prefetch_atmosphere_state, cf_time_steps with
@@ -1331,6 +1362,26 @@ int cf_prefetch_atmosphere_state(cf_ctx* ctx, const cf_atmos_source* src_next, c
  * changes the clock calls this so that no later cf_update_state mistakes the set's contents for the state it asks for.
  * An interpolation already running on the auxiliary stream is ordered ahead of whatever follows on the context's stream. */
 int cf_discard_prefetched_atmosphere_state(cf_ctx* ctx);
+
+/* Self-test hook (host bookkeeping only, launches nothing, changes no state): which way every atmosphere state requested ahead
+ * went since cf_create — requests of cf_prefetch_atmosphere_state and of a pipelined cf_time_steps alike (which makes one per
+ * step but the first of a call that finds its state pending, and under CF_PIPELINE_CONTINUING one more for the step behind its
+ * last).  Every accepted request leaves at most once (the launched_* counters) and ends exactly once, so at every point
+ *   requests = consumed + mismatched + voided + superseded + discarded + pending.
+ * Set struct_size = sizeof(cf_prefetch_stats) before the call.                                                          */
+typedef struct cf_prefetch_stats {
+    int32_t struct_size;
+    int32_t pending;               /* requests neither ended nor refused, launched or not (0, 1 or 2) */
+    uint64_t requests;             /* accepted */
+    uint64_t launched_aux;         /* left on the auxiliary stream */
+    uint64_t launched_tail;        /* … as tail workgroups of an ocean solver launch */
+    uint64_t launched_merged;      /* … inside a face-stress launch */
+    uint64_t launched_ice_tail;    /* … in the tail of a sea-ice interface launch */
+    uint64_t launched_own;         /* … as a launch of its own on the context's stream */
+    uint64_t consumed, mismatched, voided, superseded, discarded;   /* how they ended (cf_prefetch_atmosphere_state) */
+    uint64_t step_interpolations;  /* interpolations cf_update_state / _sea_ice launched for their own step */
+} cf_prefetch_stats;
+int cf_debug_prefetch_stats(cf_ctx* ctx, cf_prefetch_stats* out);
 
 #ifdef __cplusplus
 }

@@ -16,14 +16,14 @@ HEADER = open(os.path.join(ROOT, "include", "coflux.h")).read()
 NOT_BOUND = {"cf_version", "cf_set_flux_params", "cf_set_stream", "cf_debug_eval", "cf_debug_chunk_plan", "cf_device_free",
              "cf_time_stage", "cf_time_copy", "cf_profile_enable", "cf_profile_read", "cf_comm_destroy", "cf_window_upload", "cf_solver_path"}
 
-JL_SIZE = {"Int32": 4, "Cint": 4, "Int64": 8, "Float64": 8, "Float32": 4}
+JL_SIZE = {"Int32": 4, "Cint": 4, "Int64": 8, "UInt64": 8, "Float64": 8, "Float32": 4}
 TWINS = {"CfGrid": abi.Grid, "CfRoughness": abi.Roughness, "CfThermodynamics": abi.Thermodynamics, "CfSeawater": abi.Seawater,
          "CfFluxParams": abi.FluxParams, "CfOceanSurface": abi.OceanSurface, "CfExchangeFields": abi.ExchangeFields,
          "CfInterfaceFluxes": abi.InterfaceFluxes, "CfSeaIceFields": abi.SeaIceFields, "CfNetOceanFluxes": abi.NetOceanFluxes,
          "CfAtmosSource": abi.AtmosSource, "CfInterpWeights": abi.InterpWeights, "CfSeaIceParams": abi.SeaIceParams,
          "CfSeaIceState": abi.SeaIceState, "CfNetSeaIceFluxes": abi.NetSeaIceFluxes, "CfRunSchedule": abi.RunSchedule,
          "CfSeaIceAlbedoParams": abi.SeaIceAlbedoParams, "CfIceOceanParams": abi.IceOceanParams, "CfIceOceanFluxes": abi.IceOceanFluxes,
-         "CfLandSource": abi.LandSource}
+         "CfLandSource": abi.LandSource, "CfPrefetchStats": abi.PrefetchStats}
 
 
 def julia_structs():
@@ -76,5 +76,5 @@ def test_struct_mirrors_have_the_abi_sizes():
         assert len(structs[name]) >= 1
     # field NAMES of the flat pointer bundles line up with the ctypes mirrors (order is the ABI)
     for name in ("CfOceanSurface", "CfExchangeFields", "CfInterfaceFluxes", "CfSeaIceFields", "CfNetOceanFluxes", "CfSeaIceState",
-                 "CfIceOceanFluxes", "CfRunSchedule", "CfLandSource", "CfSeaIceAlbedoParams", "CfIceOceanParams", "CfSeaIceParams"):
+                 "CfIceOceanFluxes", "CfRunSchedule", "CfLandSource", "CfSeaIceAlbedoParams", "CfIceOceanParams", "CfSeaIceParams", "CfPrefetchStats"):
         assert [f for f, _t in structs[name]] == [f for f, *_ in TWINS[name]._fields_], name

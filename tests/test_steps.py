@@ -80,11 +80,16 @@ def test_prefetch_mismatch_is_ignored_not_used():
     ctx.update_state(src, w, states[0], a, fl, net, level1=1, level2=2, time_fraction=0.25)
     ctx.sync()
     want = {k: v.clone() for k, v in a.items()}
+    before = ctx.prefetch_stats()
     ctx.prefetch_atmosphere_state(src, w, a, level1=0, level2=1, time_fraction=0.5)      # wrong time for the next call
     ctx.update_state(src, w, states[0], a, fl, net, level1=1, level2=2, time_fraction=0.25)
     ctx.sync()
     for k in EXCHANGE_NAMES:
         assert torch.equal(a[k], want[k]), k
+    # … and it was there to be ignored: accepted, launched (a request into the step's own set leaves on the auxiliary stream),
+    # found by the step, told apart and interpolated again
+    moved = {k: v - before[k] for k, v in ctx.prefetch_stats().items() if v != before[k]}
+    assert moved == dict(requests=1, launched_aux=1, mismatched=1, step_interpolations=1), moved
     ctx.close()
 
 
@@ -106,14 +111,19 @@ def test_request_flushed_by_sync_is_ordered_behind_the_readers_of_its_set(mode):
     for _ in range(3):   # work queued on the main stream that READS set b (the net fluxes read Qs, Ql, Mp)
         ctx.update_state(src, w, states[0], b, fl, net, level1=0, level2=1, time_fraction=0.25)
     want_fl = {k: v.clone() for k, v in fl.items()}
+    before = ctx.prefetch_stats()
     ctx.prefetch_atmosphere_state(src, w, b, level1=1, level2=2, time_fraction=0.75)   # overwrites b; no solver launch follows
     ctx.sync()                                                                          # the flush
+    moved = {k: v - before[k] for k, v in ctx.prefetch_stats().items() if v != before[k]}
+    assert moved == dict(requests=1, launched_aux=1, pending=1), moved                  # whatever the mode
     for k in FLUX_NAMES:   # the three queued steps saw the OLD contents of b
         assert torch.equal(fl[k], want_fl[k]), k
     for k in EXCHANGE_NAMES:
         assert torch.equal(b[k], ref[k]), k
     ctx.update_state(src, w, states[1], b, fl, net, level1=1, level2=2, time_fraction=0.75)   # consumes the pending state
     ctx.sync()
+    moved = {k: v - before[k] for k, v in ctx.prefetch_stats().items() if v != before[k]}
+    assert moved == dict(requests=1, launched_aux=1, consumed=1), moved                 # (no interpolation by the step)
     for k in FLUX_NAMES:
         assert torch.equal(fl[k], rfl[k]), k
     for k in NET_NAMES:

@@ -508,7 +508,8 @@ def test_time_steps_on_the_atlas(merged, solver):
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_prefetch_atmosphere_state_on_the_atlas(mode):
     """cf_prefetch_atmosphere_state: a request that no solver launch follows is flushed by cf_sync and goes out on the auxiliary
-    stream, whatever CF_OPT_MERGED_PREFETCH says; followed by cf_update_state it rides as that mode decides.  Both ways the
+    stream, whatever CF_OPT_MERGED_PREFETCH says; followed by cf_update_state it rides as that mode decides — the counters of
+    cf_debug_prefetch_stats say that it did: one launch on the auxiliary stream, one by the mode's own route.  Both ways the
     requested set is within the bound of the exact reference and has the stand-alone launch's bits."""
     import torch
     from coflux.runtime import FLUX_NAMES, NET_NAMES
@@ -530,6 +531,7 @@ def test_prefetch_atmosphere_state_on_the_atlas(mode):
                     continue               # the merged forms need the tiled interpolation
                 _set(ctx, rows, cap)
                 out.clear()
+                before = ctx.prefetch_stats()
                 ctx.interpolate_atmosphere_state(src, dw, out.sets[0], *ahead)
                 ctx.prefetch_atmosphere_state(src, dw, out.sets[1], *ahead)
                 ctx.sync()
@@ -537,6 +539,9 @@ def test_prefetch_atmosphere_state_on_the_atlas(mode):
                 ctx.update_state(src, dw, states[0], out.sets[2], fl, net, level1=first[0], level2=first[1], time_fraction=first[2])
                 ctx.sync()
                 label = (name, grid, win, "mode", mode, "ROWS", rows, "cap", cap)
+                moved = {k: v - before[k] for k, v in ctx.prefetch_stats().items() if k.startswith("launched_") and v != before[k]}
+                route = ("launched_aux", "launched_merged", "launched_tail")[mode]
+                assert moved == ({"launched_aux": 2} if mode == 0 else {"launched_aux": 1, route: 1}), (label, moved)
                 _assert_within(out.host(1, win), exact, M, cs is not None, label)
                 bits = out.all.view(torch.int64)
                 assert torch.equal(bits[1], bits[0]) and torch.equal(bits[3], bits[0]), label
