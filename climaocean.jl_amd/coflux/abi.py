@@ -206,6 +206,30 @@ class InterpWeights(C.Structure):
                 ("cos_rot", C.c_void_p), ("sin_rot", C.c_void_p), ("latitude", C.c_void_p)]
 
 
+class CoupledPrepare(C.Structure):
+    """cf_coupled_prepare: the three jobs of cf_prepare_coupled_step (a job is absent when its output is NULL)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32),
+                ("ocean", OceanSurface), ("weights", InterpWeights),
+                ("land", LandSource), ("land_freshwater", C.c_void_p),
+                ("ice_ocean", IceOceanParams), ("concentration", C.c_void_p), ("x_stress", C.c_void_p), ("y_stress", C.c_void_p),
+                ("ice_ocean_fluxes", IceOceanFluxes),
+                ("piston_velocity", C.c_double), ("target_salinity", C.c_void_p), ("restoring_buffer", C.c_void_p)]
+
+
+class CoupledStep(C.Structure):
+    """cf_coupled_step: what cf_time_steps_coupled needs beyond cf_time_steps' arguments."""
+    _fields_ = [("struct_size", C.c_int32), ("n_ice_states", C.c_int32),
+                ("ice_states", C.POINTER(SeaIceState)), ("skin_temperature", C.c_void_p),
+                ("ai_fluxes", InterfaceFluxes), ("net_ice", NetSeaIceFluxes),
+                ("land", LandSource), ("land_first_level", C.c_int32), ("compute_ice_ocean", C.c_int32),
+                ("land_time_fraction", C.c_double), ("land_time_fraction_increment", C.c_double),
+                ("land_freshwater", C.c_void_p),
+                ("ice_ocean", IceOceanParams), ("ice_ocean_fluxes", IceOceanFluxes),
+                ("piston_velocity", C.c_double), ("target_salinity", C.c_void_p), ("restoring_buffer", C.c_void_p),
+                ("normalize_salinity", C.c_int32), ("reserved", C.c_int32),
+                ("area", C.c_void_p), ("mean_out", C.c_void_p)]
+
+
 class AverageTerm(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("a", C.c_void_p), ("b", C.c_void_p), ("scale", C.c_double),
                 ("mean", C.c_void_p)]
@@ -287,6 +311,7 @@ EXPORTED_SYMBOLS = (
     "cf_monitor_create", "cf_monitor_destroy", "cf_monitor_collect", "cf_monitor_count", "cf_monitor_read", "cf_monitor_status",
     "cf_monitor_reset", "cf_attach_monitor",
     "cf_regrid_create", "cf_regrid_destroy", "cf_regrid_apply",
+    "cf_prepare_coupled_step", "cf_time_steps_coupled",
 )
 
 PACKAGE_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -400,6 +425,10 @@ def load_library(path=None):
     lib.cf_time_steps.argtypes = [
         vp, C.c_int64, C.c_int, C.POINTER(RunSchedule), C.POINTER(AtmosSource), C.POINTER(InterpWeights),
         C.POINTER(InterfaceFluxes), C.POINTER(SeaIceFields), C.POINTER(NetOceanFluxes)]
+    lib.cf_prepare_coupled_step.argtypes = [vp, C.POINTER(CoupledPrepare)]
+    lib.cf_time_steps_coupled.argtypes = [
+        vp, C.c_int64, C.c_int, C.POINTER(RunSchedule), C.POINTER(AtmosSource), C.POINTER(InterpWeights),
+        C.POINTER(InterfaceFluxes), C.POINTER(SeaIceFields), C.POINTER(NetOceanFluxes), C.POINTER(CoupledStep)]
     lib.cf_prefetch_atmosphere_state.argtypes = [vp, C.POINTER(AtmosSource), C.POINTER(InterpWeights), C.POINTER(ExchangeFields)]
     lib.cf_ensure_chunk_table.argtypes = [vp, vp]
     lib.cf_debug_chunk_table.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -20,6 +20,7 @@ The atmosphere holds a window of snapshots in HBM filled from a provider: synthe
 Float32 plane files of coflux/jra55.py (`omip_forcing`; NetCDF decoding itself is not possible in this image).
 """
 import logging
+import math
 import time
 from dataclasses import dataclass, field
 from types import SimpleNamespace
@@ -657,6 +658,119 @@ def time_step(model, dt):
     model.clock.time += dt
     model.clock.iteration += 1
     update_state(model)
+
+
+def _device_clock(level1, fraction, n_levels, step, increment):
+    """(first_level, time_fraction) with which the device loop's clock — total = time_fraction + step · increment, level1 =
+    (first_level + ⌊total⌋) mod n_levels, ñ = total − ⌊total⌋ (cf_time_steps) — gives exactly (level1, fraction) at `step`,
+    or None.  The sum is simulated in the same double arithmetic, so a returned pair is verified, not estimated."""
+    base = float(step) * increment
+    shift = max(0, math.ceil(base - fraction))
+    guess = fraction + shift - base
+    for tf in (guess, np.nextafter(guess, np.inf), np.nextafter(guess, -np.inf)):
+        tf = float(tf)
+        total = tf + base
+        whole = math.floor(total)
+        if tf >= 0.0 and total - whole == fraction:
+            return (level1 - int(whole)) % n_levels, tf
+    return None
+
+
+def _clock_at(first_level, time_fraction, n_levels, step, increment):
+    total = time_fraction + float(step) * increment
+    whole = math.floor(total)
+    level1 = (first_level + int(whole)) % n_levels
+    return level1, (level1 + 1) % n_levels, total - whole
+
+
+def time_steps(model, dt, nsteps, normalize=None):
+    """`nsteps` × time_step!(coupled_model, Δt), each followed by `normalize(model)` (a NormalizeSalinity) when one is given,
+    inside libcoflux (cf_time_steps_coupled): no host work between the steps.  For a model whose ocean has no step_callback,
+    whose atmosphere and land are whole records in memory, and which has sea ice with a surface state; anything else raises
+    ValueError with the reason.  Both clocks advance by nsteps · Δt and every field of the model — the sea ice's
+    top_surface_temperature and interfaces.land_freshwater included — is left as the host loop leaves it, bit for bit: the
+    device loop's clock (fraction + step · increment) is held to time_step!'s own (t / Δt_snapshot) on the host first, and
+    where the two would part in the last bit — Δt / Δt_snapshot is not a binary fraction — the run continues in a further
+    call from a re-based clock.  One call when they agree throughout.  Steps are numbered by model.clock.iteration, which is
+    what the context's attached averager, integrator and monitor collect on."""
+    itf, atm, ocean, si, land = model.interfaces, model.atmosphere, model.ocean, model.sea_ice, getattr(model, "land", None)
+    if ocean.step_callback is not None:
+        raise ValueError("time_steps: the ocean has a step_callback (host work between the steps); use time_step")
+    if atm.provider is not None:
+        raise ValueError("time_steps: the atmosphere is a sliding window (provider); only a whole record in memory is supported")
+    if land is not None and land.provider is not None:
+        raise ValueError("time_steps: the land is a sliding window (provider); only a whole record in memory is supported")
+    if si is None or itf.atmosphere_sea_ice_interface is None:
+        raise ValueError("time_steps: the model has no sea ice with a surface state (thickness, top_surface_temperature); "
+                         "the ocean-only loop is FluxContext.time_steps")
+    if getattr(model, "_pipeline_dt", None) is not None or getattr(itf, "_next_state_in_other", False):
+        raise ValueError("time_steps: called inside run!(simulation)")
+    if normalize is not None and normalize.flux_field is not itf.net_fluxes.ocean.S:
+        raise ValueError("time_steps: normalize is not the NormalizeSalinity of this model's salinity flux")
+    ctx = itf.context
+    first = model.clock.iteration
+    t0 = model.clock.time
+    times = []
+    t = t0
+    for _ in range(nsteps):   # (the clock of time_step!: repeated addition)
+        t += dt
+        times.append(t)
+    clocks = [(atm, [atm.time_indices(t) for t in times], dt / atm.time_interval)]
+    if land is not None:
+        clocks.append((land, [land.levels(t) for t in times], dt / land.time_interval))
+    ai = itf.atmosphere_sea_ice_interface._fields
+    exchange = itf.sea_ice_ocean_heat_flux is not None
+    if exchange:
+        f = itf.sea_ice_ocean_fluxes
+        si.interface_heat, si.salt_flux, si.frazil_heat = f["interface_heat"], f["salt_flux"], f["frazil_heat"]
+        ice_ocean = dict(f)
+    else:
+        ice_ocean = {k: v for k, v in (("interface_heat", si.interface_heat), ("salt_flux", si.salt_flux), ("frazil_heat", si.frazil_heat))
+                     if v is not None}
+    if land is not None and not hasattr(itf, "land_freshwater"):
+        itf.land_freshwater = ctx.zeros()
+    restoring = normalize.additional_fluxes if normalize is not None else None
+    # the carried skin temperature is the interface's own `temperature`: time_step! writes the result there and copies the whole
+    # array to the sea ice — so the first guess goes in on the window the solve reads, and the array comes back whole
+    W = (slice(ocean.grid.halo[1] - 1, ocean.grid.halo[1] + ocean.grid.size[1] + 1), slice(ocean.grid.halo[0] - 1, ocean.grid.halo[0] + ocean.grid.size[0] + 1))
+    ai["temperature"][W].copy_(si.top_surface_temperature[W])
+    state = {k: v for k, v in si.surface_state().items() if k != "top_temperature"}
+    stresses = {k: v for k, v in (("x_stress", si.x_stress), ("y_stress", si.y_stress)) if v is not None}
+    a = 0
+    while a < nsteps:
+        g = first + a
+        based = []
+        for comp, want, inc in clocks:
+            n1, n2, frac = want[a]
+            c = _device_clock(n1, frac, comp.n_levels, g, inc)
+            if c is None or _clock_at(c[0], c[1], comp.n_levels, g, inc) != (n1, n2, frac):
+                raise ValueError(f"time_steps: the device loop's clock cannot take the snapshots ({n1}, {n2}) at fraction {frac!r} "
+                                 f"of step {g} (a clamped record at its end?); use time_step")
+            based.append(c)
+        b = a + 1
+        while b < nsteps and all(_clock_at(c[0], c[1], comp.n_levels, first + b, inc) == tuple(want[b])
+                                 for (comp, want, inc), c in zip(clocks, based)):
+            b += 1
+        sch = ctx.make_schedule([ocean.surface_state()], [itf._exchange_sets[itf._exchange_current]], first_level=based[0][0],
+                                time_fraction=based[0][1], time_fraction_increment=clocks[0][2], fold_north=itf.fold_north)
+        kw = {}
+        if land is not None:
+            kw.update(friver=land.data["friver"], licalvf=land.data.get("licalvf"), land_out=itf.land_freshwater,
+                      land_first_level=based[1][0], land_time_fraction=based[1][1], land_time_fraction_increment=clocks[1][2])
+        if restoring is not None:
+            kw.update(piston_velocity=restoring.velocity, target=restoring.target, restoring_out=normalize.additional_buffer)
+        if normalize is not None:
+            kw.update(normalize=True, area=normalize.area, mean_out=normalize.mean_total)
+        block = ctx.make_coupled_step([state], ai["temperature"], ai, itf.net_fluxes._sea_ice_fields,
+                                      ice_ocean_params=itf.ice_ocean_params if exchange else None, ice_ocean_fluxes=ice_ocean, **kw)
+        ctx.time_steps_coupled(g, b - a, sch, atm.data, itf.weights, itf.atmosphere_ocean_interface._fields, itf.net_fluxes._ocean_fields,
+                               stresses or None, block)
+        a = b
+    si.top_surface_temperature.copy_(ai["temperature"])
+    for _ in range(nsteps):
+        ocean.time_step(dt)
+        model.clock.time += dt
+        model.clock.iteration += 1
 
 
 @dataclass

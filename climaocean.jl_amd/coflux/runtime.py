@@ -419,6 +419,80 @@ class FluxContext:
                                            C.byref(f), C.byref(i) if i is not None else None, C.byref(n)),
                     "cf_time_steps")
 
+    # -- the coupled step: sea ice, land, restoring ------------------------------------------------
+    ICE_STATE_NAMES = ("concentration", "thickness", "top_temperature", "u", "v", "albedo", "snow_thickness")
+
+    def _land_struct(self, friver, licalvf, level1=0, level2=0, time_fraction=0.0):
+        s = abi.LandSource()
+        if friver is not None:
+            assert friver.dtype == torch.float32 and friver.is_cuda and friver.is_contiguous()
+            s.friver = friver.data_ptr()
+            s.licalvf = licalvf.data_ptr() if licalvf is not None else None
+            s.n_levels, s.ns_y, s.ns_x = friver.shape
+        s.level1, s.level2, s.time_fraction = level1, level2, float(time_fraction)
+        return s
+
+    def prepare_coupled_step(self, ocean, *, weights=None, friver=None, licalvf=None, land_out=None, level1=0, level2=1,
+                             time_fraction=0.0, ice_ocean_params=None, concentration=None, x_stress=None, y_stress=None,
+                             ice_ocean_out=None, piston_velocity=0.0, target=None, restoring_out=None):
+        """cf_prepare_coupled_step: interpolate_land_freshwater (→ land_out), compute_sea_ice_ocean_fluxes (→ the dict
+        ice_ocean_out) and materialize_salinity_restoring (→ restoring_out) as one launch, same bits; a job whose output is
+        None is left out."""
+        p = abi.CoupledPrepare()
+        p.struct_size = C.sizeof(abi.CoupledPrepare)
+        p.ocean = self.ocean_struct(ocean)
+        if land_out is not None:
+            p.weights = self.weights_struct(weights)
+            p.land = self._land_struct(friver, licalvf, level1, level2, time_fraction)
+            p.land_freshwater = land_out.data_ptr()
+        if ice_ocean_out is not None:
+            p.ice_ocean = ice_ocean_params
+            p.concentration, p.x_stress, p.y_stress = _ptr(concentration), _ptr(x_stress), _ptr(y_stress)
+            p.ice_ocean_fluxes = self._struct(abi.IceOceanFluxes, ice_ocean_out,
+                                              ("interface_heat", "salt_flux", "frazil_heat", "friction_velocity"))
+        if restoring_out is not None:
+            p.piston_velocity, p.target_salinity, p.restoring_buffer = float(piston_velocity), _ptr(target), restoring_out.data_ptr()
+        self._check(self.lib.cf_prepare_coupled_step(self._h, C.byref(p)), "cf_prepare_coupled_step")
+
+    def make_coupled_step(self, ice_states, skin_temperature, ai_fluxes, net_ice, *, friver=None, licalvf=None, land_out=None,
+                          land_first_level=0, land_time_fraction=0.0, land_time_fraction_increment=0.0, ice_ocean_params=None,
+                          ice_ocean_fluxes=None, piston_velocity=0.0, target=None, restoring_out=None, normalize=False, area=None,
+                          mean_out=None):
+        """cf_coupled_step for time_steps_coupled; keeps the ctypes array and the tensors alive on the returned object.
+        `ice_states`: dicts of ICE_STATE_NAMES (top_temperature is ignored: `skin_temperature` is carried); `ice_ocean_fluxes`:
+        dict interface_heat, salt_flux[, frazil_heat, friction_velocity] — computed each step when `ice_ocean_params` is
+        given, taken as given otherwise."""
+        k = abi.CoupledStep()
+        k.struct_size = C.sizeof(abi.CoupledStep)
+        st = (abi.SeaIceState * max(len(ice_states), 1))(*[self._struct(abi.SeaIceState, s, self.ICE_STATE_NAMES) for s in ice_states])
+        k.n_ice_states, k.ice_states = len(ice_states), st
+        k.skin_temperature = _ptr(skin_temperature)
+        k.ai_fluxes = self.fluxes_struct({n: t for n, t in (ai_fluxes or {}).items() if n != "temperature"})
+        k.net_ice = self._struct(abi.NetSeaIceFluxes, net_ice, ("top_heat", "bottom_heat"))
+        k.land = self._land_struct(friver, licalvf)
+        k.land_first_level, k.land_time_fraction = int(land_first_level), float(land_time_fraction)
+        k.land_time_fraction_increment = float(land_time_fraction_increment)
+        k.land_freshwater = _ptr(land_out)
+        if ice_ocean_params is not None:
+            k.compute_ice_ocean, k.ice_ocean = 1, ice_ocean_params
+        k.ice_ocean_fluxes = self._struct(abi.IceOceanFluxes, ice_ocean_fluxes, ("interface_heat", "salt_flux", "frazil_heat", "friction_velocity"))
+        k.piston_velocity, k.target_salinity, k.restoring_buffer = float(piston_velocity), _ptr(target), _ptr(restoring_out)
+        k.normalize_salinity, k.area, k.mean_out = int(bool(normalize)), _ptr(area), _ptr(mean_out)
+        k._keep = (st, ice_states, skin_temperature, ai_fluxes, net_ice, friver, licalvf, land_out, ice_ocean_fluxes, target, restoring_out,
+                   area, mean_out)
+        return k
+
+    def time_steps_coupled(self, first_step, nsteps, schedule, src, weights, fluxes, net, ice, coupled):
+        """run!(simulation) of the OMIP configuration inside libcoflux (cf_time_steps_coupled): per step the fold, the
+        preamble (land, ice–ocean exchange, restoring), update_state_sea_ice with the carried skin temperature, and
+        NormalizeSalinity.  `ice`: the partition's stresses (dict x_stress, y_stress) or None."""
+        s = self.source_struct(src, 0, 0, 0.0)
+        w = self.weights_struct(weights)
+        f, n, i = self.fluxes_struct(fluxes), self.net_struct(net), self.ice_struct(ice)
+        self._check(self.lib.cf_time_steps_coupled(self._h, first_step, nsteps, C.byref(schedule), C.byref(s), C.byref(w), C.byref(f),
+                                                   C.byref(i) if i is not None else None, C.byref(n),
+                                                   C.byref(coupled) if coupled is not None else None), "cf_time_steps_coupled")
+
     # -- time averages ----------------------------------------------------------------------------
     def average(self, sources, means):
         """A device-side running mean of `sources` into `means` (cf_average_create): lists of up to abi.AVERAGE_MAX_FIELDS

@@ -1454,6 +1454,95 @@ int cf_materialize_salinity_restoring(cf_ctx* ctx, double piston_velocity, const
     return CF_OK;
 }
 
+// The argument checks of cf_prepare_coupled_step — each present job's are its own entry point's — apart from the launch:
+// cf_time_steps_coupled makes them for every state of its schedule before its first launch
+int check_coupled_prepare(cf_ctx* ctx, const cf_coupled_prepare* p) {
+    if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
+    if (!p) return fail(ctx, CF_ERR_INVALID, "cf_prepare_coupled_step: prepare is NULL");
+    if (p->struct_size != (int32_t)sizeof(cf_coupled_prepare))
+        return fail(ctx, CF_ERR_INVALID, "cf_coupled_prepare.struct_size = %d, library expects %zu", p->struct_size, sizeof(cf_coupled_prepare));
+    const bool ice_job = p->ice_ocean_fluxes.interface_heat != nullptr;
+    if (p->land_freshwater) {
+        const cf_land_source* src = &p->land;
+        if (!src->friver) return fail(ctx, CF_ERR_INVALID, "cf_prepare_coupled_step: land.friver is NULL");
+        CHECK(check_weights(ctx, &p->weights));
+        if (src->ns_x <= 0 || src->ns_y <= 0 || src->n_levels <= 0 || src->level1 < 0 || src->level1 >= src->n_levels || src->level2 < 0 ||
+            src->level2 >= src->n_levels)
+            return fail(ctx, CF_ERR_INVALID, "land source: shape %dx%d, levels (%d,%d) of %d", src->ns_x, src->ns_y, src->level1, src->level2, src->n_levels);
+    }
+    if (ice_job) {
+        const cf_ice_ocean_params* params = &p->ice_ocean;
+        if (!p->ocean.T || !p->ocean.S || !p->ice_ocean_fluxes.salt_flux)
+            return fail(ctx, CF_ERR_INVALID, "cf_prepare_coupled_step: ocean.T, ocean.S or ice_ocean_fluxes.salt_flux is NULL");
+        if (params->struct_size != (int32_t)sizeof(cf_ice_ocean_params))
+            return fail(ctx, CF_ERR_INVALID, "cf_ice_ocean_params.struct_size = %d, library expects %zu", params->struct_size,
+                        sizeof(cf_ice_ocean_params));
+        if (!(params->heat_transfer_coefficient > 0) || !(params->salt_transfer_coefficient > 0) || !(params->liquidus_slope > 0) ||
+            !(params->latent_heat_of_fusion > 0))
+            return fail(ctx, CF_ERR_INVALID, "ice-ocean transfer coefficients, liquidus slope and latent heat must be > 0");
+    }
+    if (p->restoring_buffer && (!p->target_salinity || !p->ocean.S))
+        return fail(ctx, CF_ERR_INVALID, "cf_prepare_coupled_step: target_salinity or ocean.S is NULL");
+    if ((ice_job || p->restoring_buffer) && ctx->dev.mask_kind != CF_MASK_NONE && !p->ocean.mask)
+        return fail(ctx, CF_ERR_INVALID, "ocean mask is NULL");
+    return CF_OK;
+}
+
+int cf_prepare_coupled_step(cf_ctx* ctx, const cf_coupled_prepare* p) {
+    CHECK(check_coupled_prepare(ctx, p));
+    const bool ice_job = p->ice_ocean_fluxes.interface_heat != nullptr;
+    if (!p->land_freshwater && !ice_job && !p->restoring_buffer) return CF_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ice_job) CHECK(wait_for_halos(ctx));
+    PrepareArgs A{};
+    if (p->land_freshwater) {
+        A.friver = p->land.friver;
+        A.licalvf = p->land.licalvf;
+        A.ns_x = p->land.ns_x;
+        A.ns_y = p->land.ns_y;
+        A.level1 = p->land.level1;
+        A.level2 = p->land.level2;
+        A.tf = p->land.time_fraction;
+        A.land_out = p->land_freshwater;
+    }
+    if (ice_job) {
+        A.Q = p->ice_ocean;
+        A.T = p->ocean.T;
+        A.conc = p->concentration;
+        A.tx = p->x_stress;
+        A.ty = p->y_stress;
+        A.Qio = p->ice_ocean_fluxes.interface_heat;
+        A.Jsio = p->ice_ocean_fluxes.salt_flux;
+        A.Qfr = p->ice_ocean_fluxes.frazil_heat;
+        A.ustar = p->ice_ocean_fluxes.friction_velocity;
+    }
+    if (p->restoring_buffer) {
+        A.vp = p->piston_velocity;
+        A.target = p->target_salinity;
+        A.restoring = p->restoring_buffer;
+    }
+    A.S = p->ocean.S;
+    A.mask = p->ocean.mask;
+    HIP_TRY(ctx, launch_prepare_coupled_step(ctx->stream, ctx->dev, ctx->grid, p->land_freshwater ? &p->weights : nullptr, A));
+    return CF_OK;
+}
+
+// cf_time_steps_coupled (coflux_steps.cpp): the NULL checks cf_update_state_sea_ice would make at the first step, made before
+// the first launch of the loop
+int check_coupled_update(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w, const cf_run_schedule* S,
+                         const cf_interface_fluxes* fluxes, const cf_net_ocean_fluxes* net, const cf_interface_fluxes* ai_fluxes) {
+    cf_atmos_source s0 = *src;   // (the levels are the loop's own: the clock was checked)
+    s0.level1 = s0.level2 = 0;
+    CHECK(check_source(ctx, &s0));
+    CHECK(check_weights(ctx, w));
+    for (int n = 0; n < S->n_ocean_states; ++n) CHECK(check_ocean(ctx, &S->ocean_states[n]));
+    for (int n = 0; n < S->n_atmos_sets; ++n) CHECK(check_exchange(ctx, &S->atmos[n], true));
+    CHECK(check_fluxes(ctx, fluxes));
+    CHECK(check_net(ctx, net, w));
+    if (check_fluxes(ctx, ai_fluxes) != CF_OK) return fail(ctx, CF_ERR_INVALID, "cf_time_steps_coupled: ai_fluxes fields are NULL");
+    return CF_OK;
+}
+
 int cf_normalize_salinity_flux(cf_ctx* ctx, double* d_flux, const double* d_additional, const double* d_area,
                                const void* d_mask, double* d_mean_out) {
     if (!ctx || !d_flux) return fail(ctx, CF_ERR_INVALID, "cf_normalize_salinity_flux: bad arguments");

@@ -270,6 +270,12 @@ int average_collect(cf_average* a, double weight);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state); *route is the counter of
 // ctx->prefetch_stats that names the launch it left in
 extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx, uint64_t* route);
+// coflux_abi.cpp: the argument checks of cf_prepare_coupled_step and of the cf_update_state_sea_ice of a coupled step loop,
+// without their launches (cf_time_steps_coupled validates a whole call before its first launch)
+extern "C" __attribute__((visibility("hidden"))) int check_coupled_prepare(cf_ctx* ctx, const cf_coupled_prepare* p);
+extern "C" __attribute__((visibility("hidden"))) int check_coupled_update(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
+                                                                          const cf_run_schedule* S, const cf_interface_fluxes* fluxes,
+                                                                          const cf_net_ocean_fluxes* net, const cf_interface_fluxes* ai_fluxes);
 
 // Whether the atmosphere state requested ahead from (a, wa) is the one a step asks for with (b, wb): the same source arrays and
 // shape, levels and time fraction, through the same map.  Levels and fraction alone do not say so: two snapshot windows, a

@@ -14,6 +14,7 @@
 
 #include <algorithm>
 
+#include "coflux_coupled_cells.hpp"
 #include "coflux_interp_cell.hpp"
 #include "coflux_interp_tiles.hpp"
 #include "coflux_kernel_types.hpp"
@@ -141,22 +142,7 @@ __global__ __launch_bounds__(256) void interpolate_land_kernel(const float* __re
     const int jj = idx / wx;
     const int i = idx - jj * wx - G.ring, j = jj - G.ring;
     const size_t k = cell_index(G, i, j);
-    const double fi = Wt.separable ? Wt.fi[i + G.hx] : Wt.fi[k];
-    const double fj = Wt.separable ? Wt.fj[j + G.hy] : Wt.fj[k];
-    const double xi = fi - floor(fi), eta = fj - floor(fj);
-    const int i0 = (int)trunc(fi), ja = (int)trunc(fj);
-    const int is0 = wrap_index(i0, ns_x), is1 = wrap_index(i0 + (fi > 0.0 ? 1 : (fi < 0.0 ? -1 : 0)), ns_x);
-    const int j0 = min(max(ja, 0), ns_y - 1), j1 = min(max(ja + (fj > 0.0 ? 1 : (fj < 0.0 ? -1 : 0)), 0), ns_y - 1);
-    const size_t g00 = (size_t)j0 * ns_x + is0, g10 = (size_t)j0 * ns_x + is1, g01 = (size_t)j1 * ns_x + is0, g11 = (size_t)j1 * ns_x + is1;
-    const size_t plane = (size_t)ns_x * ns_y;
-    const double w00 = (1.0 - xi) * (1.0 - eta), w01 = (1.0 - xi) * eta, w10 = xi * (1.0 - eta), w11 = xi * eta;
-    auto value = [&](const float* d) {
-        const float* a = d + (size_t)level1 * plane;
-        const float* b = d + (size_t)level2 * plane;
-        return bilinear(w00, w01, w10, w11, blend_levels(a[g00], b[g00], tf), blend_levels(a[g01], b[g01], tf),
-                        blend_levels(a[g10], b[g10], tf), blend_levels(a[g11], b[g11], tf));
-    };
-    out[k] = value(friver) + (licalvf ? value(licalvf) : 0.0);
+    out[k] = land_freshwater_cell(friver, licalvf, ns_x, ns_y, level1, level2, tf, Wt, G, i, j, k);
 }
 
 hipError_t launch_interpolate_land(hipStream_t st, const GridDesc& G, const cf_land_source* s, const cf_interp_weights* w, double* out) {

@@ -138,6 +138,30 @@ hipError_t launch_sea_ice_albedo(hipStream_t st, const cf_sea_ice_albedo_params&
 hipError_t launch_sea_ice_ocean_fluxes(hipStream_t st, const DevParams& P, const cf_ice_ocean_params& Q, const GridDesc& G,
                                        const cf_ocean_surface* o, const double* conc, const double* tx, const double* ty,
                                        const cf_ice_ocean_fluxes* out);
+// cf_prepare_coupled_step (coflux_net.hip): the three jobs of the one launch; a job whose output is null is absent
+struct PrepareArgs {
+    const float* friver;      // land freshwater → land_out on W
+    const float* licalvf;
+    int32_t ns_x, ns_y, level1, level2;
+    double tf;
+    double* land_out;
+    cf_ice_ocean_params Q;    // ice–ocean exchange and frazil → Qio, Jsio[, Qfr, ustar] on I
+    const double* T;
+    const double* conc;
+    const double* tx;
+    const double* ty;
+    double* Qio;
+    double* Jsio;
+    double* Qfr;
+    double* ustar;
+    double vp;                // restoring buffer → restoring on I
+    const double* target;
+    double* restoring;
+    const double* S;          // read once for both interior jobs, like the mask
+    const void* mask;
+};
+hipError_t launch_prepare_coupled_step(hipStream_t st, const DevParams& P, const GridDesc& G, const cf_interp_weights* w,
+                                       const PrepareArgs& A);
 constexpr int SALINITY_PARTIAL_BLOCKS = 512;
 hipError_t launch_salinity_partial_sums(hipStream_t st, const DevParams& P, const GridDesc& G, const double* flux,
                                         const double* additional, const double* area, const void* mask, double* partial,

@@ -2,6 +2,7 @@
 // conversion), plus the device-copy kernel that calibrates the HBM denominator.
 #include <hip/hip_runtime.h>
 
+#include "coflux_coupled_cells.hpp"
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
 
@@ -82,7 +83,8 @@ __global__ __launch_bounds__(NET_BLOCK) void salinity_restoring_kernel(DevParams
     if (idx >= G.nx * G.ny) return;
     const int j = idx / G.nx;
     const size_t k = cell_index(G, idx - j * G.nx, j);
-    out[k] = cell_is_wet(P, mask, k) ? vp * (S[k] - target[k]) : 0.0;
+    const bool wet = cell_is_wet(P, mask, k);
+    out[k] = salinity_restoring_cell(wet, vp, wet ? S[k] : 0.0, target, k);
 }
 
 hipError_t launch_salinity_restoring(hipStream_t st, const DevParams& P, const GridDesc& G, const void* mask, double vp,
@@ -176,34 +178,12 @@ __global__ __launch_bounds__(NET_BLOCK) void sea_ice_ocean_flux_kernel(DevParams
     if (idx >= ncells) return;
     const int j = idx / G.nx;
     const size_t k = cell_index(G, idx - j * G.nx, j);
-    double q_io = 0.0, j_io = 0.0, q_fr = 0.0, us = 0.0;
-    if (cell_is_wet(P, O.mask, k)) {
-        const double rho_o = 1.0 / P.rho_o_inv, c_o = 1.0 / P.c_o_inv;
-        const double So = O.S[k];
-        double To = O.T[k];
-        const double Tf = -Q.liquidus_slope * So;
-        if (Q.time_step > 0.0 && To < Tf) {  // frazil: the deficit below freezing is handed to the ice model
-            q_fr = rho_o * c_o * Q.top_cell_thickness * (To - Tf) / Q.time_step;
-            To = Tf;
-        }
-        const double a = conc ? conc[k] : 0.0;
-        if (a > 0.0) {
-            const double txc = tx ? 0.5 * (tx[k] + tx[k + 1]) : 0.0, tyc = ty ? 0.5 * (ty[k] + ty[k + (size_t)G.sj]) : 0.0;
-            us = fmax(sqrt(sqrt(txc * txc + tyc * tyc)), Q.minimum_friction_velocity);
-            // α_s (S_o − S_b) = (c_o α_h / ℒ)(T_o + m S_b)(S_b − S_i): the positive root of A S_b² + B S_b − C = 0
-            const double ah = Q.heat_transfer_coefficient, as = Q.salt_transfer_coefficient, m = Q.liquidus_slope;
-            const double g = c_o * ah / Q.latent_heat_of_fusion;
-            const double A = g * m, B = g * To - g * m * Q.ice_salinity + as, C = g * To * Q.ice_salinity + as * So;
-            const double Sb = (-B + sqrt(B * B + 4.0 * A * C)) / (2.0 * A);
-            const double Tb = -m * Sb;
-            q_io = a * rho_o * c_o * ah * us * (To - Tb);
-            j_io = a * as * us * (So - Sb);
-        }
-    }
-    Qio[k] = q_io;
-    Jsio[k] = j_io;
-    if (Qfr) Qfr[k] = q_fr;
-    if (ustar_out) ustar_out[k] = us;
+    const bool wet = cell_is_wet(P, O.mask, k);
+    const IceOceanCell C = sea_ice_ocean_cell(P, Q, G, wet, wet ? O.S[k] : 0.0, O.T, conc, tx, ty, k);
+    Qio[k] = C.q_io;
+    Jsio[k] = C.j_io;
+    if (Qfr) Qfr[k] = C.q_fr;
+    if (ustar_out) ustar_out[k] = C.us;
 }
 
 hipError_t launch_sea_ice_ocean_fluxes(hipStream_t st, const DevParams& P, const cf_ice_ocean_params& Q, const GridDesc& G,
@@ -212,6 +192,41 @@ hipError_t launch_sea_ice_ocean_fluxes(hipStream_t st, const DevParams& P, const
     const int ncells = G.nx * G.ny;
     hipLaunchKernelGGL(sea_ice_ocean_flux_kernel, dim3((ncells + NET_BLOCK - 1) / NET_BLOCK), dim3(NET_BLOCK), 0, st, P, Q, G,
                        make_ocean(o), conc, tx, ty, out->interface_heat, out->salt_flux, out->frazil_heat, out->friction_velocity);
+    return hipGetLastError();
+}
+
+// =============================================================================================
+// cf_prepare_coupled_step: the three pointwise passes in front of a coupled step's solve as ONE launch — the land freshwater
+// on the ring window W (interpolate_land_kernel's cell), the ice–ocean exchange with frazil and the restoring buffer on the
+// interior I (sea_ice_ocean_flux_kernel's and salinity_restoring_kernel's cells).  One thread per cell of W; the two interior
+// jobs share one read of the mask and of S.  A job whose output pointer is null is absent.  Same functions, same bits.
+// =============================================================================================
+__global__ __launch_bounds__(NET_BLOCK) void prepare_coupled_step_kernel(DevParams P, GridDesc G, WeightDesc Wt, PrepareArgs A) {
+    const int wx = G.nx + 2 * G.ring, wy = G.ny + 2 * G.ring;
+    const int idx = (int)blockIdx.x * NET_BLOCK + (int)threadIdx.x;
+    if (idx >= wx * wy) return;
+    const int jj = idx / wx;
+    const int i = idx - jj * wx - G.ring, j = jj - G.ring;
+    const size_t k = cell_index(G, i, j);
+    if (A.land_out) A.land_out[k] = land_freshwater_cell(A.friver, A.licalvf, A.ns_x, A.ns_y, A.level1, A.level2, A.tf, Wt, G, i, j, k);
+    if (i < 0 || i >= G.nx || j < 0 || j >= G.ny) return;
+    if (!A.Qio && !A.restoring) return;
+    const bool wet = cell_is_wet(P, A.mask, k);
+    const double So = wet ? A.S[k] : 0.0;
+    if (A.Qio) {
+        const IceOceanCell C = sea_ice_ocean_cell(P, A.Q, G, wet, So, A.T, A.conc, A.tx, A.ty, k);
+        A.Qio[k] = C.q_io;
+        A.Jsio[k] = C.j_io;
+        if (A.Qfr) A.Qfr[k] = C.q_fr;
+        if (A.ustar) A.ustar[k] = C.us;
+    }
+    if (A.restoring) A.restoring[k] = salinity_restoring_cell(wet, A.vp, So, A.target, k);
+}
+
+hipError_t launch_prepare_coupled_step(hipStream_t st, const DevParams& P, const GridDesc& G, const cf_interp_weights* w,
+                                       const PrepareArgs& A) {
+    const int n = (G.nx + 2 * G.ring) * (G.ny + 2 * G.ring);
+    hipLaunchKernelGGL(prepare_coupled_step_kernel, dim3((n + NET_BLOCK - 1) / NET_BLOCK), dim3(NET_BLOCK), 0, st, P, G, make_weights(w), A);
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 //   * cf_fold_north_halo: the tripolar fold on the last slab,
 //   * cf_time_steps: run!(simulation) of a prescribed-ocean coupled model without returning to the host language.
 #include <map>
+#include <optional>
 
 #include "coflux_series.hpp"
 
@@ -285,22 +286,115 @@ int cf_discard_prefetched_atmosphere_state(cf_ctx* ctx) {
 }
 
 // ---- run!(simulation) -------------------------------------------------------------------------
-int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_schedule* S, const cf_atmos_source* src,
-                  const cf_interp_weights* w, const cf_interface_fluxes* fluxes, const cf_sea_ice_fields* ice,
-                  const cf_net_ocean_fluxes* net) {
-    if (!ctx || !S || !src || !w) return fail(ctx, CF_ERR_INVALID, "cf_time_steps: NULL argument");
+// cf_time_steps_coupled: what the block itself must satisfy (the schedule's scalars are checked already).  Every message names
+// the field.
+static int check_coupled_block(cf_ctx* ctx, const cf_run_schedule* S, const cf_atmos_source* src, const cf_interp_weights* w,
+                               const cf_interface_fluxes* fluxes, const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* net,
+                               const cf_coupled_step* K) {
+    const char* fn = "cf_time_steps_coupled";
+    if (K->struct_size != (int32_t)sizeof(cf_coupled_step))
+        return fail(ctx, CF_ERR_INVALID, "cf_coupled_step.struct_size = %d, library expects %zu", K->struct_size, sizeof(cf_coupled_step));
+    if (!ctx->ice_ready) return fail(ctx, CF_ERR_INVALID, "%s: cf_set_sea_ice_formulation has not been called", fn);
+    if (S->halo_backend != CF_HALO_NONE)
+        return fail(ctx, CF_ERR_INVALID, "%s: halo_backend = %d, but nothing moves the ice rows between ranks yet: only CF_HALO_NONE", fn,
+                    S->halo_backend);
+    if (K->n_ice_states < 1 || !K->ice_states) return fail(ctx, CF_ERR_INVALID, "%s: n_ice_states = %d (at least 1) or ice_states is NULL", fn, K->n_ice_states);
+    for (int n = 0; n < K->n_ice_states; ++n) {
+        if (!K->ice_states[n].concentration || !K->ice_states[n].thickness)
+            return fail(ctx, CF_ERR_INVALID, "%s: ice_states[%d].concentration or .thickness is NULL", fn, n);
+        // the partition reads ℵ of the step's ice state: a fixed pointer in `ice` can only be that of every state
+        if (ice && ice->concentration && ice->concentration != K->ice_states[n].concentration)
+            return fail(ctx, CF_ERR_INVALID, "%s: ice->concentration is not ice_states[%d].concentration: the partition and the interface "
+                        "solve would read different ice (pass NULL: every step takes its ice state's)", fn, n);
+    }
+    if (!K->skin_temperature) return fail(ctx, CF_ERR_INVALID, "%s: skin_temperature is NULL", fn);
+    if (K->ai_fluxes.temperature && K->ai_fluxes.temperature != K->skin_temperature)
+        return fail(ctx, CF_ERR_INVALID, "%s: ai_fluxes.temperature is neither NULL nor skin_temperature", fn);
+    if (!K->net_ice.top_heat || !K->net_ice.bottom_heat) return fail(ctx, CF_ERR_INVALID, "%s: net_ice.top_heat or .bottom_heat is NULL", fn);
+    if (K->land.friver) {
+        if (!K->land_freshwater) return fail(ctx, CF_ERR_INVALID, "%s: land_freshwater is NULL", fn);
+        if (K->land.ns_x <= 0 || K->land.ns_y <= 0 || K->land.n_levels <= 0 || K->land_first_level < 0 || K->land_first_level >= K->land.n_levels)
+            return fail(ctx, CF_ERR_INVALID, "%s: land shape %dx%d, land_first_level = %d of %d levels", fn, K->land.ns_x, K->land.ns_y,
+                        K->land_first_level, K->land.n_levels);
+        if (!(K->land_time_fraction >= 0.0) || !(K->land_time_fraction_increment >= 0.0) || !std::isfinite(K->land_time_fraction) ||
+            !std::isfinite(K->land_time_fraction_increment))
+            return fail(ctx, CF_ERR_INVALID, "%s: land_time_fraction = %g, land_time_fraction_increment = %g", fn, K->land_time_fraction,
+                        K->land_time_fraction_increment);
+    }
+    if (K->compute_ice_ocean && (!K->ice_ocean_fluxes.interface_heat || !K->ice_ocean_fluxes.salt_flux))
+        return fail(ctx, CF_ERR_INVALID, "%s: ice_ocean_fluxes.interface_heat or .salt_flux is NULL", fn);
+    cf_interface_fluxes ai = K->ai_fluxes;
+    ai.temperature = K->skin_temperature;
+    CHECK(check_coupled_update(ctx, src, w, S, fluxes, net, &ai));
+    if (K->mean_out) {   // one double: it may not lie inside any ocean-grid array of the call (the normalisation would race with it)
+        std::vector<const void*> arrays;
+        auto add = [&](const void* p) {
+            if (p) arrays.push_back(p);
+        };
+        auto add_fluxes = [&](const cf_interface_fluxes& f) {
+            for (const void* p : {(const void*)f.sensible_heat, (const void*)f.latent_heat, (const void*)f.water_vapor, (const void*)f.x_momentum,
+                                  (const void*)f.y_momentum, (const void*)f.temperature, (const void*)f.friction_velocity,
+                                  (const void*)f.temperature_scale, (const void*)f.humidity_scale})
+                add(p);
+        };
+        for (int n = 0; n < S->n_ocean_states; ++n) {
+            const cf_ocean_surface& o = S->ocean_states[n];
+            for (const void* p : {(const void*)o.T, (const void*)o.S, (const void*)o.u, (const void*)o.v}) add(p);
+        }
+        for (int n = 0; n < S->n_atmos_sets; ++n) {
+            const cf_exchange_fields& e = S->atmos[n];
+            for (const void* p : {(const void*)e.u, (const void*)e.v, (const void*)e.T, (const void*)e.p, (const void*)e.q, (const void*)e.Qs,
+                                  (const void*)e.Ql, (const void*)e.Mp})
+                add(p);
+        }
+        for (int n = 0; n < K->n_ice_states; ++n) {
+            const cf_sea_ice_state& st = K->ice_states[n];
+            for (const void* p : {(const void*)st.concentration, (const void*)st.thickness, (const void*)st.u, (const void*)st.v,
+                                  (const void*)st.albedo, (const void*)st.snow_thickness})
+                add(p);
+        }
+        add_fluxes(*fluxes);
+        add_fluxes(ai);
+        for (const void* p : {(const void*)net->u, (const void*)net->v, (const void*)net->T, (const void*)net->S,
+                              (const void*)net->shortwave_surface_flux, (const void*)net->upwelling_longwave,
+                              (const void*)net->downwelling_longwave, (const void*)net->downwelling_shortwave})
+            add(p);
+        if (ice) {
+            add(ice->x_stress);
+            add(ice->y_stress);
+        }
+        for (const void* p : {(const void*)K->net_ice.top_heat, (const void*)K->net_ice.bottom_heat, (const void*)K->land_freshwater,
+                              (const void*)K->ice_ocean_fluxes.interface_heat, (const void*)K->ice_ocean_fluxes.salt_flux,
+                              (const void*)K->ice_ocean_fluxes.frazil_heat, (const void*)K->ice_ocean_fluxes.friction_velocity,
+                              (const void*)K->target_salinity, (const void*)K->restoring_buffer, (const void*)K->area})
+            add(p);
+        const uintptr_t bytes = (uintptr_t)ctx->grid.sj * (uintptr_t)(ctx->grid.ny + 2 * ctx->grid.hy) * sizeof(double);
+        const uintptr_t m = (uintptr_t)K->mean_out;
+        for (const void* p : arrays)
+            if (m + sizeof(double) > (uintptr_t)p && m < (uintptr_t)p + bytes)
+                return fail(ctx, CF_ERR_INVALID, "%s: mean_out lies inside another array of the call", fn);
+    }
+    return CF_OK;
+}
+
+// The one step loop behind cf_time_steps (K = NULL: per step cf_update_state) and cf_time_steps_coupled (K: the coupled block —
+// per step the preamble, cf_update_state_sea_ice and the normalisation).  `name`: the entry point, for the messages.
+static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, int nsteps, const cf_run_schedule* S,
+                           const cf_atmos_source* src, const cf_interp_weights* w, const cf_interface_fluxes* fluxes,
+                           const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* net, const cf_coupled_step* K) {
+    if (!ctx || !S || !src || !w) return fail(ctx, CF_ERR_INVALID, "%s: NULL argument", name);
     if (S->struct_size != (int32_t)sizeof(cf_run_schedule))
         return fail(ctx, CF_ERR_INVALID, "cf_run_schedule.struct_size = %d, library expects %zu", S->struct_size, sizeof(cf_run_schedule));
     if (nsteps < 0 || first_step < 0 || S->n_ocean_states < 1 || !S->ocean_states || !S->atmos)
-        return fail(ctx, CF_ERR_INVALID, "cf_time_steps: bad schedule");
-    if (S->pipeline < 0 || S->pipeline > CF_PIPELINE_CONTINUING) return fail(ctx, CF_ERR_INVALID, "cf_time_steps: pipeline = %d", S->pipeline);
+        return fail(ctx, CF_ERR_INVALID, "%s: bad schedule", name);
+    if (S->pipeline < 0 || S->pipeline > CF_PIPELINE_CONTINUING) return fail(ctx, CF_ERR_INVALID, "%s: pipeline = %d", name, S->pipeline);
     if (S->n_atmos_sets < 1 || S->n_atmos_sets > 2 || (S->pipeline && S->n_atmos_sets != 2))
-        return fail(ctx, CF_ERR_INVALID, "cf_time_steps: %d exchange-field sets (pipelining needs 2)", S->n_atmos_sets);
+        return fail(ctx, CF_ERR_INVALID, "%s: %d exchange-field sets (pipelining needs 2)", name, S->n_atmos_sets);
     if (!(S->time_fraction >= 0.0) || !(S->time_fraction_increment >= 0.0) || S->first_level < 0 || S->first_level >= src->n_levels)
-        return fail(ctx, CF_ERR_INVALID, "cf_time_steps: bad clock (fraction %g, increment %g, level %d of %d)", S->time_fraction,
+        return fail(ctx, CF_ERR_INVALID, "%s: bad clock (fraction %g, increment %g, level %d of %d)", name, S->time_fraction,
                     S->time_fraction_increment, S->first_level, src->n_levels);
     if (S->halo_backend != CF_HALO_NONE && S->halo_rows != ctx->grid.ring + 1)
-        return fail(ctx, CF_ERR_INVALID, "cf_time_steps: halo_rows = %d, but the ring row reads v[j+1]: rows must be ring + 1 = %d",
+        return fail(ctx, CF_ERR_INVALID, "%s: halo_rows = %d, but the ring row reads v[j+1]: rows must be ring + 1 = %d", name,
                     S->halo_rows, ctx->grid.ring + 1);
     auto source_at = [&](int64_t step) {
         cf_atmos_source s = *src;
@@ -311,6 +405,42 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         s.time_fraction = total - whole;
         return s;
     };
+    // the coupled block's preamble for step `step`: the land clock runs by source_at's arithmetic on the block's own fields
+    auto prepare_at = [&](int64_t step, const cf_ocean_surface* o, const cf_sea_ice_state* is) {
+        cf_coupled_prepare P{};
+        P.struct_size = (int32_t)sizeof(cf_coupled_prepare);
+        P.ocean = *o;
+        if (K->land.friver) {
+            P.weights = *w;
+            P.land = K->land;
+            const double total = K->land_time_fraction + (double)step * K->land_time_fraction_increment;
+            const double whole = std::floor(total);
+            P.land.level1 = (int)((K->land_first_level + (int64_t)whole) % K->land.n_levels);
+            P.land.level2 = (P.land.level1 + 1) % K->land.n_levels;
+            P.land.time_fraction = total - whole;
+            P.land_freshwater = K->land_freshwater;
+        }
+        if (K->compute_ice_ocean) {
+            P.ice_ocean = K->ice_ocean;
+            P.concentration = is->concentration;
+            P.x_stress = ice ? ice->x_stress : nullptr;
+            P.y_stress = ice ? ice->y_stress : nullptr;
+            P.ice_ocean_fluxes = K->ice_ocean_fluxes;
+        }
+        if (K->restoring_buffer) {
+            P.piston_velocity = K->piston_velocity;
+            P.target_salinity = K->target_salinity;
+            P.restoring_buffer = K->restoring_buffer;
+        }
+        return P;
+    };
+    if (K) {   // everything the steps' own entry points would refuse, before the first launch: the outputs stay untouched
+        CHECK(check_coupled_block(ctx, S, src, w, fluxes, ice, net, K));
+        for (int n = 0; n < S->n_ocean_states; ++n) {
+            const cf_coupled_prepare P = prepare_at(first_step, &S->ocean_states[n], &K->ice_states[0]);
+            CHECK(check_coupled_prepare(ctx, &P));
+        }
+    }
     CHECK(series_room(ctx, ctx->integrals, first_step, nsteps, "integrator"));   // a series that would overflow: nothing is launched
     CHECK(series_room(ctx, ctx->monitor, first_step, nsteps, "monitor"));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -320,8 +450,8 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         // INSIDE the step loop (a stream synchronisation behind a queued peer-direct halo kernel that waits for its
         // neighbour, and a rebuild per step when states alternate: ADVICE r2)
         if (S->ocean_states[n].mask != S->ocean_states[0].mask)
-            return fail(ctx, CF_ERR_INVALID, "cf_time_steps: ocean state %d carries a different mask pointer than state 0; the states of a "
-                        "schedule share one wet mask", n);
+            return fail(ctx, CF_ERR_INVALID, "%s: ocean state %d carries a different mask pointer than state 0; the states of a "
+                        "schedule share one wet mask", name, n);
         if (n == 0) CHECK(cf_ensure_chunk_table(ctx, S->ocean_states[n].mask));
     }
     static const int fold_loc[4] = {CF_FOLD_CENTER, CF_FOLD_CENTER, CF_FOLD_X_FACE, CF_FOLD_Y_FACE};
@@ -356,7 +486,9 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
     }
     // CF_OPT_LAND_ZEROS: the steps below are one loop over fixed outputs, one mask pointer and one chunk table (checked above) —
     // cf_update_state may leave the land cells to the first of them.  Closed on every way out of this function.
-    const LandZeroScope land_zero_scope(ctx);
+    // (the coupled form does not open one: it writes the land at every step, as the host loop of its entry points does)
+    std::optional<LandZeroScope> land_zero_scope;
+    if (!K) land_zero_scope.emplace(ctx);
     for (int64_t step = first_step; step < first_step + nsteps; ++step) {
         const cf_ocean_surface* o = &S->ocean_states[step % S->n_ocean_states];
         double* rows[4] = {const_cast<double*>(o->T), const_cast<double*>(o->S), const_cast<double*>(o->u),
@@ -378,6 +510,12 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
             }
         }
         if (S->fold_north) CHECK(cf_fold_north_halo(ctx, rows, fold_loc, fold_sign, 4, ctx->grid.ring + 1));
+        const cf_sea_ice_state* is = K ? &K->ice_states[step % K->n_ice_states] : nullptr;
+        if (K) {
+            const cf_coupled_prepare P = prepare_at(step, o, is);
+            CHECK(cf_prepare_coupled_step(ctx, &P));
+            if (K->land.friver) ctx->d_land_freshwater = K->land_freshwater;   // cf_set_land_freshwater
+        }
         const cf_atmos_source s = source_at(step);
         const cf_exchange_fields* a = &S->atmos[S->n_atmos_sets == 2 ? step % 2 : 0];
         // CF_PIPELINE_WITHIN_CALL: nothing beyond this call's steps is read or written.  CF_PIPELINE_CONTINUING: the last
@@ -389,7 +527,23 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
             const cf_atmos_source sn = source_at(step + 1);
             CHECK(cf_prefetch_atmosphere_state(ctx, &sn, w, &S->atmos[(step + 1) % 2]));
         }
-        CHECK(cf_update_state(ctx, &s, w, o, a, fluxes, ice, net));
+        if (K) {
+            cf_sea_ice_fields partition{};   // ℵ of this step's ice state, the caller's stresses, the block's ice–ocean fluxes
+            if (ice) partition = *ice;
+            partition.concentration = is->concentration;
+            partition.interface_heat = K->ice_ocean_fluxes.interface_heat;
+            partition.salt_flux = K->ice_ocean_fluxes.salt_flux;
+            cf_sea_ice_state state = *is;    // the skin temperature is carried: first guess and result in one buffer
+            state.top_temperature = K->skin_temperature;
+            cf_interface_fluxes ai = K->ai_fluxes;
+            ai.temperature = K->skin_temperature;
+            CHECK(cf_update_state_sea_ice(ctx, &s, w, o, a, fluxes, &partition, net, &state, &ai, K->ice_ocean_fluxes.frazil_heat,
+                                          K->ice_ocean_fluxes.interface_heat, &K->net_ice));
+            if (K->normalize_salinity)
+                CHECK(cf_normalize_salinity_flux(ctx, net->S, K->restoring_buffer, K->area, o->mask, K->mean_out));
+        } else {
+            CHECK(cf_update_state(ctx, &s, w, o, a, fluxes, ice, net));
+        }
         // an attached averager (cf_attach_average) collects on the GLOBAL step index: a run split into several calls collects
         // the same steps.  Queued behind every launch of the step — the face stresses of the merged and tail forms included
         if (ctx->average && (step + 1) % ctx->average_stride == 0)
@@ -399,6 +553,19 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
         if (ctx->monitor.collects(step)) CHECK(cf_monitor_collect(ctx->monitor.handle, ctx->monitor.stamp(step)));
     }
     return CF_OK;
+}
+
+int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_schedule* S, const cf_atmos_source* src,
+                  const cf_interp_weights* w, const cf_interface_fluxes* fluxes, const cf_sea_ice_fields* ice,
+                  const cf_net_ocean_fluxes* net) {
+    return time_steps_loop(ctx, "cf_time_steps", first_step, nsteps, S, src, w, fluxes, ice, net, nullptr);
+}
+
+int cf_time_steps_coupled(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_schedule* S, const cf_atmos_source* src,
+                          const cf_interp_weights* w, const cf_interface_fluxes* fluxes, const cf_sea_ice_fields* ice,
+                          const cf_net_ocean_fluxes* net, const cf_coupled_step* coupled) {
+    if (ctx && !coupled) return fail(ctx, CF_ERR_INVALID, "cf_time_steps_coupled: the coupled block is NULL");
+    return time_steps_loop(ctx, "cf_time_steps_coupled", first_step, nsteps, S, src, w, fluxes, ice, net, coupled);
 }
 
 }  // extern "C"

@@ -627,4 +627,53 @@ materialize_salinity_restoring!(b, piston_velocity, target, ocean::CfOceanSurfac
     check(b.ctx, ccall((:cf_materialize_salinity_restoring, libcoflux), Cint,
                        (Ptr{Cvoid}, Float64, Ptr{Float64}, Ref{CfOceanSurface}, Ptr{Float64}), b.ctx, piston_velocity, target, ocean, buffer))
 
+# ---- the coupled step: OceanSeaIceModel(ocean, sea_ice; atmosphere, land, interfaces) + restoring + NormalizeSalinity ---------
+# prepare_coupled_step! is the three calls above (land freshwater, ice–ocean exchange, restoring buffer) as ONE launch, same
+# bits; a job is absent when its output pointer is C_NULL.  A host that steps its own ocean calls it, then update_state_sea_ice!.
+struct CfIceOceanParamsData   # the isbits twin of CfIceOceanParams: a mutable struct is a reference when it is a field
+    struct_size::Int32; reserved::Int32
+    heat_transfer_coefficient::Float64; salt_transfer_coefficient::Float64; minimum_friction_velocity::Float64
+    ice_density::Float64; latent_heat_of_fusion::Float64; ice_salinity::Float64; liquidus_slope::Float64
+    top_cell_thickness::Float64; time_step::Float64
+end
+CfIceOceanParamsData(p::CfIceOceanParams) = CfIceOceanParamsData(ntuple(i -> getfield(p, i), fieldcount(CfIceOceanParams))...)
+struct CfCoupledPrepare
+    struct_size::Int32; reserved::Int32
+    ocean::CfOceanSurface
+    weights::CfInterpWeights
+    land::CfLandSource
+    land_freshwater::Ptr{Float64}
+    ice_ocean::CfIceOceanParamsData
+    concentration::Ptr{Float64}; x_stress::Ptr{Float64}; y_stress::Ptr{Float64}
+    ice_ocean_fluxes::CfIceOceanFluxes
+    piston_velocity::Float64
+    target_salinity::Ptr{Float64}; restoring_buffer::Ptr{Float64}
+end
+prepare_coupled_step!(b, p::CfCoupledPrepare) =
+    check(b.ctx, ccall((:cf_prepare_coupled_step, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfCoupledPrepare}), b.ctx, p))
+# time_steps_coupled!: time_steps! of that configuration — per step the preamble, update_state_sea_ice! on ice state
+# s mod n_ice_states with the CARRIED skin temperature, and NormalizeSalinity — without returning to Julia.
+struct CfCoupledStep
+    struct_size::Int32; n_ice_states::Int32
+    ice_states::Ptr{CfSeaIceState}
+    skin_temperature::Ptr{Float64}
+    ai_fluxes::CfInterfaceFluxes
+    net_ice::CfNetSeaIceFluxes
+    land::CfLandSource
+    land_first_level::Int32; compute_ice_ocean::Int32
+    land_time_fraction::Float64; land_time_fraction_increment::Float64
+    land_freshwater::Ptr{Float64}
+    ice_ocean::CfIceOceanParamsData
+    ice_ocean_fluxes::CfIceOceanFluxes
+    piston_velocity::Float64
+    target_salinity::Ptr{Float64}; restoring_buffer::Ptr{Float64}
+    normalize_salinity::Int32; reserved::Int32
+    area::Ptr{Float64}; mean_out::Ptr{Float64}
+end
+time_steps_coupled!(b, first_step, nsteps, sched::CfRunSchedule, src, w, fluxes, ice, net, coupled::CfCoupledStep) =
+    check(b.ctx, ccall((:cf_time_steps_coupled, libcoflux), Cint,
+                       (Ptr{Cvoid}, Int64, Cint, Ref{CfRunSchedule}, Ref{CfAtmosSource}, Ref{CfInterpWeights}, Ref{CfInterfaceFluxes},
+                        Ptr{CfSeaIceFields}, Ref{CfNetOceanFluxes}, Ref{CfCoupledStep}),
+                       b.ctx, first_step, nsteps, sched, src, w, fluxes, ice, net, coupled))
+
 end # module

@@ -822,6 +822,36 @@ int cf_materialize_salinity_restoring(cf_ctx* ctx, double piston_velocity /* m/s
 int cf_normalize_salinity_flux(cf_ctx* ctx, double* d_flux, const double* d_additional, const double* d_area,
                                const void* d_mask, double* d_mean_out);
 
+/* The preamble of a coupled step (omip_simulation.jl:123-163, :507-523): what cf_interpolate_land_freshwater,
+ * cf_compute_sea_ice_ocean_fluxes and cf_materialize_salinity_restoring do in front of cf_update_state_sea_ice, as ONE
+ * launch (one thread per cell of W; the two interior jobs share one read of S and of the mask).  Every array the call
+ * writes holds, on every cell of its parent array, the bits those three entry points leave when called in that order: the
+ * per-cell arithmetic is theirs.  A job is absent when its output is NULL:
+ *   land_freshwater                    NULL ⇒ no land job (`land` and `weights` are not read),
+ *   ice_ocean_fluxes.interface_heat    NULL ⇒ no ice–ocean job (`ice_ocean`, `concentration`, the stresses, ocean.T are not read),
+ *   restoring_buffer                   NULL ⇒ no restoring job (`piston_velocity`, `target_salinity` are not read);
+ * with every job absent nothing is launched.  The arguments of a present job are checked as its own entry point checks them. */
+typedef struct cf_coupled_prepare {
+    int32_t struct_size;                  /* sizeof(cf_coupled_prepare) */
+    int32_t reserved;
+    cf_ocean_surface ocean;               /* S and mask: both interior jobs; T: the ice–ocean job; u, v are not read */
+    cf_interp_weights weights;            /* the land job's map (separable or 2-D), as cf_interpolate_land_freshwater takes it */
+    cf_land_source land;                  /* friver [+ licalvf], the two levels and the fraction */
+    double* land_freshwater;              /* M_land on W */
+    cf_ice_ocean_params ice_ocean;
+    const double* concentration;          /* ℵ (NULL ⇒ 0) */
+    const double* x_stress;               /* kinematic ice–ocean stress at u-faces / v-faces (NULL ⇒ 0): read at i + 1 / j + 1 too */
+    const double* y_stress;
+    cf_ice_ocean_fluxes ice_ocean_fluxes; /* Q_io, Jˢ_io on I; frazil_heat, friction_velocity may be NULL */
+    double piston_velocity;               /* v_p, m/s */
+    const double* target_salinity;        /* S★ */
+    double* restoring_buffer;             /* J_add = v_p (Sₒ − S★) on I (0 on land) */
+} cf_coupled_prepare;
+/* Footprint: the union of the three entry points' — reads both land sources in full and fi / fj as the atmosphere does, writes
+ * land_freshwater on W; reads T, S, mask, ℵ, S★ on I, x_stress also at i + 1, y_stress also at j + 1; writes the ice–ocean
+ * outputs and restoring_buffer on I only (0 on land).  Nothing else is read or written.                                     */
+int cf_prepare_coupled_step(cf_ctx* ctx, const cf_coupled_prepare* prepare);
+
 /* ------------------------------------------------------------------------------------------
  * Measurement helper: run `launches` back-to-back launches of one stage on the context's stream
  * bracketed by HIP events ON THAT STREAM and return the average milliseconds per launch.
@@ -963,6 +993,64 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
                   const cf_atmos_source* src /* levels / fraction are overridden per step */,
                   const cf_interp_weights* w, const cf_interface_fluxes* fluxes, const cf_sea_ice_fields* ice,
                   const cf_net_ocean_fluxes* net);
+
+/* run!(simulation) of the OMIP configuration — OceanSeaIceModel(ocean, sea_ice; atmosphere, land, interfaces) with the
+ * salinity restoring on the top boundary condition and NormalizeSalinity at IterationInterval(1) (omip_simulation.jl:123-163,
+ * :385-388, :507-523) — without returning to the host language.  cf_time_steps' arguments and clock, plus this block.  Per step
+ * s (global index), on the context's stream, no host synchronisation:
+ *   1. fold_north: cf_fold_north_halo on the four ocean rows, as cf_time_steps does;
+ *   2. the preamble (cf_prepare_coupled_step; each job optional): the land freshwater at the block's own clock — levels and
+ *      fraction from land_first_level, land_time_fraction, land_time_fraction_increment by cf_time_steps' arithmetic — into
+ *      land_freshwater, which the net ocean fluxes then read as if handed to cf_set_land_freshwater (it stays set after the
+ *      call); with compute_ice_ocean the three-equation exchange and frazil from ocean state s, ℵ of ice state s and the
+ *      stresses of `ice` into ice_ocean_fluxes; the restoring buffer from ocean state s;
+ *   3. with a pipelined schedule the request for step s + 1's atmosphere state, exactly as cf_time_steps makes it;
+ *   4. cf_update_state_sea_ice with ocean_states[s mod n_ocean_states] and ice_states[s mod n_ice_states] (ℵ, hᵢ, hₛ, velocities,
+ *      albedo; its top_temperature is ignored).  The partition reads ℵ of that ice state, the stresses of `ice`, and
+ *      ice_ocean_fluxes.interface_heat / salt_flux (computed in 2 or, without compute_ice_ocean, taken as given; NULL ⇒ 0;
+ *      `ice`'s own interface_heat / salt_flux are not read); the net sea-ice fluxes read ice_ocean_fluxes.frazil_heat /
+ *      interface_heat.  skin_temperature is CARRIED: the first guess of the interface solve and the buffer its result is
+ *      written to — the in-place update cf_sea_ice_state documents; ai_fluxes.temperature is NULL or that very buffer;
+ *   5. normalize_salinity: cf_normalize_salinity_flux on net->S with restoring_buffer (or NULL), `area` and `mean_out`;
+ *   6. the attached averager, integrator and monitor, by cf_time_steps' rule.
+ * Land cells are written at every step (CF_OPT_LAND_ZEROS does not apply to this loop).
+ * CF_ERR_INVALID, with the field named, before anything is launched — the outputs are untouched — for: a NULL block or a
+ * wrong struct_size; cf_set_sea_ice_formulation not called; n_ice_states < 1 or ice_states NULL; an ice state without
+ * concentration or thickness; `ice`->concentration that is neither NULL nor the concentration of every ice state (the
+ * partition and the interface solve would disagree); land_first_level outside the land source's levels, a negative or
+ * non-finite land_time_fraction / _increment, a bad land shape; NULL among skin_temperature, ai_fluxes, net_ice, the
+ * land_freshwater of a land job, the ice_ocean_fluxes of compute_ice_ocean, `fluxes`, `net`, the exchange sets or the
+ * ocean states; an ai_fluxes.temperature that is another buffer; mean_out inside any array of the call; and
+ * halo_backend != CF_HALO_NONE: nothing moves ice rows between ranks yet (the ice–ocean exchange reads the stresses' east
+ * column and north row, the partition reads ℵ across faces — those halos are the caller's, also under fold_north).        */
+typedef struct cf_coupled_step {
+    int32_t struct_size;                  /* sizeof(cf_coupled_step) */
+    int32_t n_ice_states;                 /* ≥ 1 */
+    const cf_sea_ice_state* ice_states;   /* step s reads ice_states[s mod n_ice_states] */
+    double* skin_temperature;             /* carried top surface temperature [°C] */
+    cf_interface_fluxes ai_fluxes;        /* atmosphere–sea-ice interface fluxes (temperature: NULL or skin_temperature) */
+    cf_net_sea_ice_fluxes net_ice;
+    cf_land_source land;                  /* friver NULL ⇒ no land job; level1, level2, time_fraction are overridden per step */
+    int32_t land_first_level;             /* memory level of the land snapshot n₁ at step 0; levels advance cyclically */
+    int32_t compute_ice_ocean;            /* 1: the preamble computes ice_ocean_fluxes from `ice_ocean`; 0: they are inputs */
+    double land_time_fraction;            /* ñ of the land record at step 0 */
+    double land_time_fraction_increment;
+    double* land_freshwater;              /* M_land on W */
+    cf_ice_ocean_params ice_ocean;
+    cf_ice_ocean_fluxes ice_ocean_fluxes; /* Q_io, Jˢ_io, Q_frazil[, u★] */
+    double piston_velocity;               /* restoring: v_p [m/s], S★, J_add; restoring_buffer NULL ⇒ no restoring job */
+    const double* target_salinity;
+    double* restoring_buffer;
+    int32_t normalize_salinity;           /* 1: NormalizeSalinity after every step */
+    int32_t reserved;
+    const double* area;                   /* cell areas for the normalisation (NULL ⇒ uniform) */
+    double* mean_out;                     /* device double: the mean the last step subtracted (may be NULL) */
+} cf_coupled_step;
+/* Footprint: per step cf_fold_north_halo's (fold_north), cf_prepare_coupled_step's, cf_update_state_sea_ice's,
+ * cf_normalize_salinity_flux's (every cell of net->S, and *mean_out) and those of the attached collections.              */
+int cf_time_steps_coupled(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_schedule* schedule,
+                          const cf_atmos_source* src, const cf_interp_weights* w, const cf_interface_fluxes* fluxes,
+                          const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* net, const cf_coupled_step* coupled);
 
 /* ------------------------------------------------------------------------------------------
  * Time averages of surface fields on the device: the output that every reference configuration writes, e.g. the OMIP
