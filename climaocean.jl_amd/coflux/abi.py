@@ -39,6 +39,12 @@ DERIVED_MAX_SOURCES = 16                           # distinct source arrays of o
 (TERM_FIELD, TERM_PRODUCT, TERM_CENTER_X, TERM_CENTER_Y, TERM_CENTER_X_SQUARE, TERM_CENTER_Y_SQUARE, TERM_KINETIC_ENERGY,
  TERM_EAST, TERM_NORTH) = range(9)                 # cf_average_term.kind
 TERM_AT_CENTERS = 1                                # cf_average_term.flags (EAST / NORTH)
+(BUDGET_HEAT_SHORTWAVE, BUDGET_HEAT_LONGWAVE_UP, BUDGET_HEAT_LONGWAVE_DOWN, BUDGET_HEAT_SENSIBLE, BUDGET_HEAT_LATENT,
+ BUDGET_HEAT_ATMOSPHERE_OCEAN, BUDGET_HEAT_ICE_OCEAN, BUDGET_HEAT_FRAZIL, BUDGET_HEAT_NET, BUDGET_SALT_EVAPORATION,
+ BUDGET_SALT_PRECIPITATION, BUDGET_SALT_ATMOSPHERE_OCEAN, BUDGET_SALT_ICE_OCEAN, BUDGET_SALT_LAND,
+ BUDGET_SALT_NET) = range(15)                      # cf_budget_term.kind (cf_average_create_budget)
+BUDGET_KINDS = 15
+ATTACHED_AVERAGES_MAX = 4                          # slots of cf_attach_average_slot (slot 0 is cf_attach_average's)
 INTEGRALS_MAX_ENTRIES, INTEGRALS_MAX_FIELDS = 32, 32   # entries / distinct arrays of one surface integrator (cf_integrals_create)
 INTEGRAND_ONE, INTEGRAND_FIELD, INTEGRAND_PRODUCT, INTEGRAND_ABOVE = 0, 1, 2, 3
 MONITOR_MAX_ENTRIES = 16                             # entries of one surface monitor (cf_monitor_create)
@@ -240,6 +246,17 @@ class AverageDesc(C.Structure):
                 ("cos_rotation", C.c_void_p), ("sin_rotation", C.c_void_p), ("max_workgroups", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BudgetTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_double), ("mean", C.c_void_p)]
+
+
+class BudgetDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_terms", C.c_int32), ("terms", C.POINTER(BudgetTerm)),
+                ("ocean", C.POINTER(OceanSurface)), ("exchange", C.POINTER(ExchangeFields)), ("fluxes", C.POINTER(InterfaceFluxes)),
+                ("ice", C.POINTER(SeaIceFields)), ("frazil_heat", C.c_void_p), ("land_freshwater", C.c_void_p),
+                ("weights", C.POINTER(InterpWeights)), ("max_workgroups", C.c_int32), ("reserved", C.c_int32)]
+
+
 class IntegralEntry(C.Structure):
     _fields_ = [("kind", C.c_int32), ("region_bit", C.c_int32), ("a", C.c_void_p), ("b", C.c_void_p),
                 ("threshold", C.c_double)]
@@ -305,7 +322,7 @@ EXPORTED_SYMBOLS = (
     "cf_ensure_chunk_table", "cf_debug_chunk_table", "cf_debug_interp_grid", "cf_debug_land_zero_launches", "cf_solver_path", "cf_solver_iteration_path", "cf_solver_latency_layout", "cf_comm_count", "cf_build_stamp", "cf_discard_prefetched_atmosphere_state",
     "cf_debug_prefetch_stats",
     "cf_average_create", "cf_average_destroy", "cf_average_reset", "cf_average_collect", "cf_average_weight", "cf_attach_average",
-    "cf_average_create_derived",
+    "cf_average_create_derived", "cf_average_create_budget", "cf_attach_average_slot",
     "cf_integrals_create", "cf_integrals_destroy", "cf_integrals_collect", "cf_integrals_count", "cf_integrals_read",
     "cf_integrals_reset", "cf_attach_integrals",
     "cf_monitor_create", "cf_monitor_destroy", "cf_monitor_collect", "cf_monitor_count", "cf_monitor_read", "cf_monitor_status",
@@ -460,6 +477,8 @@ def load_library(path=None):
     lib.cf_average_weight.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.cf_attach_average.argtypes = [vp, vp, C.c_int32, C.c_double]
     lib.cf_average_create_derived.argtypes = [vp, C.POINTER(AverageDesc), C.POINTER(vp)]
+    lib.cf_average_create_budget.argtypes = [vp, C.POINTER(BudgetDesc), C.POINTER(vp)]
+    lib.cf_attach_average_slot.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_double]
     # the two series recorders: the same entry points but for the descriptor (and the records' type, passed as an address)
     for family, desc in (("integrals", IntegralsDesc), ("monitor", MonitorDesc)):
         for name, args in (("create", [vp, C.POINTER(desc), C.c_int32, C.POINTER(vp)]), ("destroy", [vp]), ("collect", [vp, C.c_double]),

@@ -31,7 +31,7 @@ import torch
 
 from . import abi, synthetic
 from . import interface_computations as ic
-from .runtime import EXCHANGE_NAMES, FLUX_NAMES, FLUX_OPTIONAL, NET_NAMES, FluxContext
+from .runtime import BUDGET_KINDS, EXCHANGE_NAMES, FLUX_NAMES, FLUX_OPTIONAL, NET_NAMES, FluxContext
 
 minutes, hours, days = 60.0, 3600.0, 86400.0
 EARTH_RADIUS = 6.371e6   # m (Oceananigans' R_Earth)
@@ -683,7 +683,7 @@ def _clock_at(first_level, time_fraction, n_levels, step, increment):
     return level1, (level1 + 1) % n_levels, total - whole
 
 
-def time_steps(model, dt, nsteps, normalize=None):
+def time_steps(model, dt, nsteps, normalize=None, averages=None):
     """`nsteps` × time_step!(coupled_model, Δt), each followed by `normalize(model)` (a NormalizeSalinity) when one is given,
     inside libcoflux (cf_time_steps_coupled): no host work between the steps.  For a model whose ocean has no step_callback,
     whose atmosphere and land are whole records in memory, and which has sea ice with a surface state; anything else raises
@@ -692,7 +692,10 @@ def time_steps(model, dt, nsteps, normalize=None):
     device loop's clock (fraction + step · increment) is held to time_step!'s own (t / Δt_snapshot) on the host first, and
     where the two would part in the last bit — Δt / Δt_snapshot is not a binary fraction — the run continues in a further
     call from a re-based clock.  One call when they agree throughout.  Steps are numbered by model.clock.iteration, which is
-    what the context's attached averager, integrator and monitor collect on."""
+    what the context's attached averagers, integrator and monitor collect on.  `averages`: a SurfaceFluxAverages writer — ALL
+    of its averagers are attached for the length of the call, one per slot from slot 0 (at most abi.ATTACHED_AVERAGES_MAX), and
+    collect every step with weight Δt; the slots are emptied again on the way out.  Its window is the caller's: read
+    `averages.means` and reset the averagers."""
     itf, atm, ocean, si, land = model.interfaces, model.atmosphere, model.ocean, model.sea_ice, getattr(model, "land", None)
     if ocean.step_callback is not None:
         raise ValueError("time_steps: the ocean has a step_callback (host work between the steps); use time_step")
@@ -708,6 +711,11 @@ def time_steps(model, dt, nsteps, normalize=None):
     if normalize is not None and normalize.flux_field is not itf.net_fluxes.ocean.S:
         raise ValueError("time_steps: normalize is not the NormalizeSalinity of this model's salinity flux")
     ctx = itf.context
+    attached = list(averages.averagers) if averages is not None else []
+    if len(attached) > abi.ATTACHED_AVERAGES_MAX:
+        raise ValueError(f"time_steps: the writer has {len(attached)} averagers, the step loop collects {abi.ATTACHED_AVERAGES_MAX}")
+    if averages is not None and (averages._east or averages._north):
+        raise ValueError("time_steps: the writer reads [i+1] / [j+1] of fields the library writes (halos filled between steps); use run")
     first = model.clock.iteration
     t0 = model.clock.time
     times = []
@@ -736,6 +744,30 @@ def time_steps(model, dt, nsteps, normalize=None):
     ai["temperature"][W].copy_(si.top_surface_temperature[W])
     state = {k: v for k, v in si.surface_state().items() if k != "top_temperature"}
     stresses = {k: v for k, v in (("x_stress", si.x_stress), ("y_stress", si.y_stress)) if v is not None}
+    # a writer with budget outputs lends the loop its Qs, Ql, Mp (SurfaceFluxAverages: the fields its averagers are bound to)
+    current = itf._exchange_sets[itf._exchange_current]
+    lent = dict(current, **averages._budget_atmos) if averages is not None and averages._budget_atmos else current
+    for slot, averager in enumerate(attached):
+        ctx.attach_average(averager, 1, dt, slot=slot)
+    try:
+        _device_steps(model, dt, nsteps, normalize, clocks, first, lent, ai, state, stresses, exchange, ice_ocean, restoring)
+    finally:
+        for slot in range(len(attached)):
+            ctx.attach_average(None, slot=slot)
+        if lent is not current:
+            for name, t in averages._budget_atmos.items():
+                current[name].copy_(t)
+    si.top_surface_temperature.copy_(ai["temperature"])
+    for _ in range(nsteps):
+        ocean.time_step(dt)
+        model.clock.time += dt
+        model.clock.iteration += 1
+
+
+def _device_steps(model, dt, nsteps, normalize, clocks, first, exchange_set, ai, state, stresses, exchange, ice_ocean, restoring):
+    """time_steps' calls of cf_time_steps_coupled: one per stretch of steps on which the device loop's clocks agree with the host's"""
+    itf, atm, ocean, land = model.interfaces, model.atmosphere, model.ocean, getattr(model, "land", None)
+    ctx = itf.context
     a = 0
     while a < nsteps:
         g = first + a
@@ -751,7 +783,7 @@ def time_steps(model, dt, nsteps, normalize=None):
         while b < nsteps and all(_clock_at(c[0], c[1], comp.n_levels, first + b, inc) == tuple(want[b])
                                  for (comp, want, inc), c in zip(clocks, based)):
             b += 1
-        sch = ctx.make_schedule([ocean.surface_state()], [itf._exchange_sets[itf._exchange_current]], first_level=based[0][0],
+        sch = ctx.make_schedule([ocean.surface_state()], [exchange_set], first_level=based[0][0],
                                 time_fraction=based[0][1], time_fraction_increment=clocks[0][2], fold_north=itf.fold_north)
         kw = {}
         if land is not None:
@@ -766,11 +798,6 @@ def time_steps(model, dt, nsteps, normalize=None):
         ctx.time_steps_coupled(g, b - a, sch, atm.data, itf.weights, itf.atmosphere_ocean_interface._fields, itf.net_fluxes._ocean_fields,
                                stresses or None, block)
         a = b
-    si.top_surface_temperature.copy_(ai["temperature"])
-    for _ in range(nsteps):
-        ocean.time_step(dt)
-        model.clock.time += dt
-        model.clock.iteration += 1
 
 
 @dataclass
@@ -1036,6 +1063,51 @@ def omip_surface_outputs(model):
 RHO_OCEAN, CP_OCEAN = 1026.0, 3991.86795711963   # visualize/common.jl:17-18
 
 
+class BudgetTerm:
+    """BudgetTerm(kind, scale=1.0): one part of the net heat or salt flux as an averaged output (cf_average_create_budget) —
+    `kind` a name of runtime.BUDGET_KINDS ("heat_atmosphere_ocean", "salt_net", …) or abi.BUDGET_*; the sample is part · scale.
+    The part is evaluated per cell inside the collection launch from the arrays the net fluxes were computed from; it is
+    never written to memory."""
+
+    def __init__(self, kind, scale=1.0):
+        self.kind = BUDGET_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if not 0 <= self.kind < abi.BUDGET_KINDS:
+            raise ValueError(f"BudgetTerm: kind = {kind!r}")
+        self.scale = float(scale)
+
+
+# the reference's budget fields (omip_diagnostics.jl:84-89,135-140) by its names, then the finer parts
+BUDGET_OUTPUTS = (("JTao", "heat_atmosphere_ocean"), ("JTio", "heat_ice_ocean"), ("JTf", "heat_frazil"), ("JTn", "heat_net"),
+                  ("JSn", "salt_net"), ("JSio", "salt_ice_ocean"),
+                  ("heat_shortwave", "heat_shortwave"), ("heat_longwave_up", "heat_longwave_up"),
+                  ("heat_longwave_down", "heat_longwave_down"), ("heat_sensible", "heat_sensible"), ("heat_latent", "heat_latent"),
+                  ("salt_evaporation", "salt_evaporation"), ("salt_precipitation", "salt_precipitation"),
+                  ("salt_atmosphere_ocean", "salt_atmosphere_ocean"), ("salt_land", "salt_land"))
+
+
+def omip_budget_outputs(model):
+    """The budget fields of the reference's `:surface` writer — JTao, JTio, JTf, JTn, JSn, JSio (omip_diagnostics.jl:84-89,
+    135-140) — and the finer parts of the atmosphere–ocean terms under descriptive names: heat_shortwave, heat_longwave_up,
+    heat_longwave_down, heat_sensible, heat_latent (they sum to JTao; the shortwave is left out of it under
+    penetrating_shortwave), salt_evaporation, salt_precipitation (they sum to salt_atmosphere_ocean) and salt_land.  Fifteen
+    BudgetTerm outputs: one more averager of a SurfaceFluxAverages writer."""
+    return {name: BudgetTerm(kind) for name, kind in BUDGET_OUTPUTS}
+
+
+def budget_inputs(model):
+    """The arrays compute_net_ocean_fluxes! reads in this model, as the keywords of FluxContext.budget_average.  The exchange
+    fields are interfaces' set 0: the state at the model's clock everywhere outside run!(simulation)."""
+    itf, ice = model.interfaces, model.sea_ice
+    kw = dict(ocean=model.ocean.surface_state(), atmos=itf._exchange_sets[0], fluxes=itf.atmosphere_ocean_interface._fields,
+              weights=itf.weights)
+    if ice is not None:
+        kw["ice"] = {k: v for k, v in ice.fields().items() if k in ("concentration", "interface_heat", "salt_flux")}
+        kw["frazil_heat"] = ice.frazil_heat
+    if getattr(itf, "land_freshwater", None) is not None:
+        kw["land_freshwater"] = itf.land_freshwater
+    return kw
+
+
 def geographic_surface_outputs(model):
     """What the reference's figures make of the time means before regridding (linear, so averaged directly): the wind stress
     in N m⁻² as geographic east / north components, −ρ · (ℑx tauuo, ℑy tauvo) rotated (cache.jl:372-386); the surface
@@ -1058,7 +1130,10 @@ class SurfaceFluxAverages:
     Scaled (omip_surface_outputs and geographic_surface_outputs are presets): the outputs then go through
     cf_average_create_derived, abi.AVERAGE_MAX_FIELDS terms per launch, with `rotation` = (cos θ, sin θ) device arrays
     (default: grid_rotation(model)) for East / North.  More outputs than that make several averagers (`averagers`);
-    `averager` is only the first of them, so attaching it to time_steps() collects the first sixteen outputs alone.
+    `averager` is only the first of them, so attaching it to time_steps() collects the first sixteen outputs alone —
+    models.time_steps(…, averages=writer) attaches them all.  BudgetTerm outputs (omip_budget_outputs is the preset) are parts
+    of the net heat and salt flux evaluated inside the collection launch (cf_average_create_budget); they are grouped into
+    averagers of their own after the others.
     Halos: a term that reads [i+1] / [j+1] of a field the LIBRARY writes (the net fluxes, the interface fluxes: written on the
     interior only) gets that field's first east halo column / north halo row filled here before every collection —
     periodic wrap in x (zero on a grid that does not close in longitude: the face is a wall), the tripolar fold
@@ -1075,26 +1150,56 @@ class SurfaceFluxAverages:
         self.on_window = on_window
         ctx = itf.context
         self.means = {name: ctx.zeros() for name in self.outputs}
-        if not any(isinstance(o, SurfaceExpression) for o in self.outputs.values()):
-            self.averagers = [ctx.average(list(self.outputs.values()), list(self.means.values()))]
+        others = {name: o for name, o in self.outputs.items() if not isinstance(o, BudgetTerm)}
+        if not others:
+            self.averagers = []
+        elif not any(isinstance(o, SurfaceExpression) for o in others.values()):
+            self.averagers = [ctx.average(list(others.values()), [self.means[name] for name in others])]
         else:
-            if rotation is None and any(getattr(o, "rotates", False) for o in self.outputs.values()):
+            if rotation is None and any(getattr(o, "rotates", False) for o in others.values()):
                 rotation = grid_rotation(model)
             self.averagers = [ctx.derived_average(terms, *(rotation or (None, None))) for terms in self.descriptor()]
             self._plan_halo_fills()
+        # budget outputs: their own averagers, after the others.  They read the shortwave, longwave and precipitation of the
+        # exchange state at the model's clock — inside run!(simulation) that state alternates between two field sets, so the
+        # averagers are bound to three fields of the writer's, which write() fills from the current set before it collects
+        # and models.time_steps lends to the device loop as that loop's Qs, Ql, Mp
+        budget = self.budget_descriptor()
+        if budget:
+            self._budget_atmos = {name: ctx.zeros() for name in ("Qs", "Ql", "Mp")}
+            inputs = dict(budget_inputs(model), atmos=self._budget_atmos)
+            self.averagers += [ctx.budget_average(terms, **inputs) for terms in budget]
         self.averager = self.averagers[0]
         self.windows = []
         g = model.ocean.grid
         (self._nx, self._ny, _), (self._hx, self._hy, _) = g.size, g.halo
 
     def descriptor(self):
-        """The term tables (kind, a, b, scale, flags, mean) of the outputs, abi.AVERAGE_MAX_FIELDS terms per averager."""
+        """The term tables (kind, a, b, scale, flags, mean) of the outputs that are no BudgetTerm, abi.AVERAGE_MAX_FIELDS terms
+        per averager."""
         terms = []
         for name, o in self.outputs.items():
+            if isinstance(o, BudgetTerm):
+                continue
             kind, flags, a, b, scale = o.term() if isinstance(o, SurfaceExpression) else (abi.TERM_FIELD, 0, o, None, 1.0)
             terms.append((kind, a, b, scale, flags, self.means[name]))
         n = abi.AVERAGE_MAX_FIELDS
         return [terms[k:k + n] for k in range(0, len(terms), n)]
+
+    def budget_descriptor(self):
+        """The term tables (kind, scale, mean) of the BudgetTerm outputs, abi.AVERAGE_MAX_FIELDS terms per averager."""
+        terms = [(o.kind, o.scale, self.means[name]) for name, o in self.outputs.items() if isinstance(o, BudgetTerm)]
+        n = abi.AVERAGE_MAX_FIELDS
+        return [terms[k:k + n] for k in range(0, len(terms), n)]
+
+    _budget_atmos = None
+
+    def stage_exchange(self, exchange):
+        """The Qs, Ql, Mp that the budget averagers read ← those of the exchange set `exchange` (three device copies)."""
+        if self._budget_atmos is not None:
+            for name, t in self._budget_atmos.items():
+                if t.data_ptr() != exchange[name].data_ptr():
+                    t.copy_(exchange[name])
 
     _east, _north = (), ()
 
@@ -1139,6 +1244,8 @@ class SurfaceFluxAverages:
         weight, t_k = self.schedule.sample(clock.time, clock.iteration)
         if weight is not None:
             self.fill_halos()
+            if self._budget_atmos is not None:
+                self.stage_exchange(self.model.interfaces.exchange_atmosphere_state)
             for averager in self.averagers:
                 averager.collect(weight)
         if t_k is not None:

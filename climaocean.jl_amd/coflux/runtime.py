@@ -508,12 +508,31 @@ class FluxContext:
         launch (0: the library's; scheduling only)."""
         return TimeAverager.derived(self, terms, cos_rotation, sin_rotation, max_workgroups)
 
-    def attach_average(self, averager, stride=1, step_weight=1.0):
-        """time_steps() collects `averager` after every step s with (s + 1) % stride == 0, weight stride · step_weight
-        (cf_attach_average); None detaches."""
+    def budget_average(self, terms, *, ocean=None, atmos=None, fluxes=None, ice=None, frazil_heat=None, land_freshwater=None,
+                       weights=None, max_workgroups=0):
+        """A device-side running mean of parts of the net heat and salt flux (cf_average_create_budget), a TimeAverager like
+        average()'s.  `terms`: up to abi.AVERAGE_MAX_FIELDS tuples (kind, scale, mean) — kind a name of BUDGET_KINDS or
+        abi.BUDGET_*, the sample is x · scale, `mean` an ocean-grid float64 field.  The inputs are those the net fluxes were
+        computed from: the dicts `ocean` (S, mask), `atmos` (Qs, Ql, Mp), `fluxes` (sensible_heat, latent_heat, water_vapor,
+        temperature), `ice` (concentration, interface_heat, salt_flux), the fields `frazil_heat` and `land_freshwater`, and
+        `weights` (latitude, separable: the latitude-dependent albedo only).  Whatever no requested kind reads may be left
+        out.  The parameters are the context's at each collection."""
+        return TimeAverager.budget(self, terms, ocean, atmos, fluxes, ice, frazil_heat, land_freshwater, weights, max_workgroups)
+
+    def attach_average(self, averager, stride=1, step_weight=1.0, slot=0):
+        """time_steps() and time_steps_coupled() collect `averager` after every step s with (s + 1) % stride == 0, weight
+        stride · step_weight; None empties the slot.  `slot`: 0 … abi.ATTACHED_AVERAGES_MAX − 1, collected in slot order, each
+        with its own stride and weight (cf_attach_average_slot; slot 0 is cf_attach_average's)."""
         h = averager._h if averager is not None else None
-        self._attached_average = averager
-        self._check(self.lib.cf_attach_average(self._h, h, int(stride), float(step_weight)), "cf_attach_average")
+        slot = int(slot)
+        if slot == 0:
+            rc, what = self.lib.cf_attach_average(self._h, h, int(stride), float(step_weight)), "cf_attach_average"
+        else:
+            rc, what = self.lib.cf_attach_average_slot(self._h, slot, h, int(stride), float(step_weight)), "cf_attach_average_slot"
+        self._check(rc, what)
+        if not hasattr(self, "_attached_averages"):
+            self._attached_averages = {}
+        self._attached_averages[slot] = averager   # kept alive while attached
 
     # -- surface integrals ------------------------------------------------------------------------
     def integrals(self, entries, area=None, mask=None, region=None, capacity=1024, max_workgroups=0):
@@ -603,6 +622,15 @@ TERM_KINDS = dict(field=abi.TERM_FIELD, product=abi.TERM_PRODUCT, center_x=abi.T
                   kinetic_energy=abi.TERM_KINETIC_ENERGY, east=abi.TERM_EAST, north=abi.TERM_NORTH)
 
 
+BUDGET_KINDS = dict(heat_shortwave=abi.BUDGET_HEAT_SHORTWAVE, heat_longwave_up=abi.BUDGET_HEAT_LONGWAVE_UP,
+                    heat_longwave_down=abi.BUDGET_HEAT_LONGWAVE_DOWN, heat_sensible=abi.BUDGET_HEAT_SENSIBLE,
+                    heat_latent=abi.BUDGET_HEAT_LATENT, heat_atmosphere_ocean=abi.BUDGET_HEAT_ATMOSPHERE_OCEAN,
+                    heat_ice_ocean=abi.BUDGET_HEAT_ICE_OCEAN, heat_frazil=abi.BUDGET_HEAT_FRAZIL, heat_net=abi.BUDGET_HEAT_NET,
+                    salt_evaporation=abi.BUDGET_SALT_EVAPORATION, salt_precipitation=abi.BUDGET_SALT_PRECIPITATION,
+                    salt_atmosphere_ocean=abi.BUDGET_SALT_ATMOSPHERE_OCEAN, salt_ice_ocean=abi.BUDGET_SALT_ICE_OCEAN,
+                    salt_land=abi.BUDGET_SALT_LAND, salt_net=abi.BUDGET_SALT_NET)
+
+
 class _ChildHandle:
     """What TimeAverager, SurfaceIntegrator, SurfaceMonitor, SurfaceRegridder and SnapshotWindow share: a handle `_h` made on the context
     `ctx` that may outlive it (the library then fails every call but the `_destroy` one with "… has been destroyed")."""
@@ -675,6 +703,35 @@ class TimeAverager(_ChildHandle):
         desc = abi.AverageDesc(C.sizeof(abi.AverageDesc), len(self.terms), table, pointer(cos_rotation, "cos_rotation"),
                                pointer(sin_rotation, "sin_rotation"), int(max_workgroups), 0)
         ctx._check(self.lib.cf_average_create_derived(ctx._h, C.byref(desc), C.byref(self._h)), "cf_average_create_derived")
+        return self
+
+    @classmethod
+    def budget(cls, ctx, terms, ocean=None, atmos=None, fluxes=None, ice=None, frazil_heat=None, land_freshwater=None, weights=None,
+               max_workgroups=0):
+        """cf_average_create_budget (FluxContext.budget_average): `sources` are the input fields given, `terms` the table."""
+        self = cls.__new__(cls)
+        self._adopt(ctx)
+        self.terms = [tuple(t) for t in terms]
+        if len(self.terms) > abi.AVERAGE_MAX_FIELDS:
+            raise ValueError(f"{len(self.terms)} terms (at most {abi.AVERAGE_MAX_FIELDS})")
+        table = (abi.BudgetTerm * max(len(self.terms), 1))()
+        self.means = []
+        for k, (kind, scale, mean) in enumerate(self.terms):
+            if not _is_field(mean, ctx):
+                raise ValueError(f"term {k}: the mean is a contiguous float64 device array of shape {ctx.shape}")
+            table[k] = abi.BudgetTerm(BUDGET_KINDS[kind] if isinstance(kind, str) else int(kind), 0, float(scale), mean.data_ptr())
+            self.means.append(mean)
+        o = ctx.ocean_struct(ocean) if ocean is not None else None
+        e = ctx.exchange_struct(atmos) if atmos is not None else None
+        f = ctx.fluxes_struct(fluxes) if fluxes is not None else None
+        i = ctx.ice_struct(ice)
+        w = ctx.weights_struct(weights) if weights is not None else None
+        self.sources = [t for d in (ocean, atmos, fluxes, ice, weights) if d is not None for t in d.values() if isinstance(t, torch.Tensor)]
+        self.sources += [t for t in (frazil_heat, land_freshwater) if t is not None]
+        ref = lambda x: C.pointer(x) if x is not None else None  # noqa: E731
+        desc = abi.BudgetDesc(C.sizeof(abi.BudgetDesc), len(self.terms), table, ref(o), ref(e), ref(f), ref(i), _ptr(frazil_heat),
+                              _ptr(land_freshwater), ref(w), int(max_workgroups), 0)
+        ctx._check(self.lib.cf_average_create_budget(ctx._h, C.byref(desc), C.byref(self._h)), "cf_average_create_budget")
         return self
 
     def collect(self, weight):

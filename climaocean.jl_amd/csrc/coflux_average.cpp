@@ -1,5 +1,5 @@
 // coflux_average.cpp — time averages of surface fields accumulated on the device (include/coflux.h: cf_average_*,
-// cf_attach_average; the kernel is coflux_average.hip).  The host keeps each window's total weight and turns a collection
+// cf_attach_average, cf_attach_average_slot; the kernel is coflux_average.hip).  The host keeps each window's total weight and turns a collection
 // of weight w into the two coefficients of the running mean; the device does one launch per collection.
 #include "coflux_ctx.hpp"
 
@@ -10,7 +10,12 @@ int average_collect(cf_average* a, double weight) {
     const double c_prev = store ? 0.0 : a->total / total;
     const double c_new = store ? 1.0 : weight / total;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (a->derived)
+    if (a->budget) {
+        // the parameters are read at each collection: a latitude-dependent albedo set after the averager was made needs the latitude
+        if (a->budget_terms.reads_albedo && ctx->dev.albedo_kind == CF_ALBEDO_LATITUDE_DEPENDENT && !a->budget_terms.latitude)
+            return fail(ctx, CF_ERR_INVALID, "cf_average_collect: the latitude-dependent albedo needs the budget averager's weights->latitude");
+        HIP_TRY(ctx, launch_budget_average(ctx->stream, ctx->dev, a->budget_terms, ctx->grid, store, c_prev, c_new));
+    } else if (a->derived)
         HIP_TRY(ctx, launch_derived_average(ctx->stream, a->terms, ctx->grid, store, c_prev, c_new));
     else
         HIP_TRY(ctx, launch_average(ctx->stream, a->fields, a->nfields, ctx->grid, store, c_prev, c_new));
@@ -51,7 +56,9 @@ int cf_average_create(cf_ctx* ctx, int nfields, const double* const* d_sources, 
 
 int cf_average_destroy(cf_average* a) {
     if (!a) return CF_OK;
-    if (a->ctx && a->ctx->average == a) a->ctx->average = nullptr;
+    if (a->ctx)
+        for (auto& slot : a->ctx->averages)
+            if (slot.handle == a) slot.handle = nullptr;
     child_leave(a);
     delete a;
     return CF_OK;
@@ -78,19 +85,32 @@ int cf_average_weight(cf_average* a, double* total, int64_t* samples) {
     return CF_OK;
 }
 
-int cf_attach_average(cf_ctx* ctx, cf_average* a, int32_t stride, double step_weight) {
-    if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
+// one slot of ctx->averages; `fn` names the entry point in the error text
+static int attach_average_slot(cf_ctx* ctx, const char* fn, int32_t slot, cf_average* a, int32_t stride, double step_weight) {
     if (!a) {
-        ctx->average = nullptr;
+        ctx->averages[slot].handle = nullptr;
         return CF_OK;
     }
-    if (a->ctx != ctx) return fail(ctx, CF_ERR_INVALID, "cf_attach_average: the averager belongs to another context");
+    if (a->ctx != ctx) return fail(ctx, CF_ERR_INVALID, "%s: the averager belongs to another context", fn);
     if (stride < 1 || !(step_weight > 0.0) || !std::isfinite(step_weight * stride))
-        return fail(ctx, CF_ERR_INVALID, "cf_attach_average: stride %d (≥ 1), step weight %g (> 0 and finite)", stride, step_weight);
-    ctx->average = a;
-    ctx->average_stride = stride;
-    ctx->average_step_weight = step_weight;
+        return fail(ctx, CF_ERR_INVALID, "%s: stride %d (≥ 1), step weight %g (> 0 and finite)", fn, stride, step_weight);
+    for (int32_t s = 0; s < CF_ATTACHED_AVERAGES_MAX; ++s)
+        if (s != slot && ctx->averages[s].handle == a)
+            return fail(ctx, CF_ERR_INVALID, "%s: the averager is already attached to slot %d", fn, s);
+    ctx->averages[slot] = cf_ctx::AverageSlot{a, stride, step_weight};
     return CF_OK;
+}
+
+int cf_attach_average(cf_ctx* ctx, cf_average* a, int32_t stride, double step_weight) {
+    if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
+    return attach_average_slot(ctx, "cf_attach_average", 0, a, stride, step_weight);
+}
+
+int cf_attach_average_slot(cf_ctx* ctx, int32_t slot, cf_average* a, int32_t stride, double step_weight) {
+    if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
+    if (slot < 0 || slot >= CF_ATTACHED_AVERAGES_MAX)
+        return fail(ctx, CF_ERR_INVALID, "cf_attach_average_slot: slot %d (0…%d)", slot, CF_ATTACHED_AVERAGES_MAX - 1);
+    return attach_average_slot(ctx, "cf_attach_average_slot", slot, a, stride, step_weight);
 }
 
 }  // extern "C"

@@ -206,10 +206,14 @@ struct cf_ctx {
     int prof_capacity = 0, prof_count = 0;
     // every averager, integrator, monitor, regridder and window made on this context (cf_destroy orphans them)
     std::vector<cf_child*> children;
-    // time averages (coflux_average.cpp): the one cf_time_steps collects (cf_attach_average)
-    cf_average* average = nullptr;
-    int32_t average_stride = 1;
-    double average_step_weight = 0.0;
+    // time averages (coflux_average.cpp): the ones the step loops collect, in slot order (cf_attach_average_slot; slot 0 is
+    // cf_attach_average's)
+    struct AverageSlot {
+        cf_average* handle = nullptr;
+        int32_t stride = 1;
+        double step_weight = 0.0;
+        bool collects(int64_t step) const { return handle && (step + 1) % stride == 0; }
+    } averages[CF_ATTACHED_AVERAGES_MAX];
     // the series recorders cf_time_steps collects after it: surface integrals (cf_attach_integrals), then the monitor (cf_attach_monitor)
     SeriesAttachment<cf_integrals> integrals;
     SeriesAttachment<cf_monitor> monitor;
@@ -237,6 +241,8 @@ struct cf_average : cf_child {
     int64_t samples = 0;
     bool derived = false;    // made by cf_average_create_derived (coflux_derived.cpp): `terms` replaces `fields`
     DerivedArgs terms{};
+    bool budget = false;     // made by cf_average_create_budget (coflux_budget.cpp): `budget_terms` replaces `fields`
+    BudgetArgs budget_terms{};
 };
 
 struct cf_regrid : cf_child {
@@ -306,7 +312,7 @@ inline void child_leave(cf_child* child) {
 inline void orphan_children(cf_ctx* ctx) {
     for (cf_child* child : ctx->children) child->ctx = nullptr;
     ctx->children.clear();
-    ctx->average = nullptr;
+    for (auto& slot : ctx->averages) slot.handle = nullptr;
     ctx->integrals.detach();
     ctx->monitor.detach();
 }

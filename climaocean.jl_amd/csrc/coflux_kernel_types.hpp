@@ -248,6 +248,20 @@ struct NetCell {
     double JT, JS, sw, lw_up, lw_down, sw_down;
 };
 
+// The ocean albedo of interior cell (row j, element k): the constant, or Large & Yeager's a_diffuse − a_direct·cos(2φ) at the
+// cell's latitude.  Shared by net_flux_kernel (coflux_net.hip) and budget_average_kernel (coflux_budget.hip), which must
+// agree on its bits: the expression is one, unsplit, under the translation unit's own contraction setting.  The latitude's
+// load is a function of its own so that a kernel can issue it with its other loads (0.0, and no load, for the constant).
+__device__ __forceinline__ double ocean_latitude_cell(const DevParams& P, const WeightDesc& Wt, const GridDesc& G, int j, size_t k) {
+    if (P.albedo_kind != CF_ALBEDO_LATITUDE_DEPENDENT) return 0.0;
+    return Wt.separable ? Wt.latitude[j + G.hy] : Wt.latitude[k];
+}
+__device__ __forceinline__ double ocean_albedo_cell(const DevParams& P, double phi) {
+    double alb = P.albedo;
+    if (P.albedo_kind == CF_ALBEDO_LATITUDE_DEPENDENT) alb = P.albedo_diffuse - P.albedo_direct * cos(2.0 * phi * (CF_PI / 180.0));
+    return alb;
+}
+
 __device__ __forceinline__ NetCell net_cell_local(const DevParams& P, double alb, double aice, double So, double Ts_kelvin,
                                                   double Mp, double Qs, double Ql, double Qc, double Qv, double Mv,
                                                   double Qio, double Jsio, double Mland = 0.0) {

@@ -196,6 +196,26 @@ struct DerivedArgs {
     int32_t max_blocks, pad;   // cf_average_desc.max_workgroups (0: the kernel's own cap); the launcher reads it, the kernel does not
 };
 hipError_t launch_derived_average(hipStream_t st, const DerivedArgs& A, const GridDesc& G, bool store, double c_prev, double c_new);
+// cf_average_collect of a budget averager (coflux_budget.hip): the inputs of compute_net_ocean_fluxes!'s cell in a fixed
+// numbering; in[s] is NULL where no requested kind reads input s or the caller has none (the cell then sees 0.0), so the
+// pointer table is the load mask.  term t averages kind[t] (CF_BUDGET_*) times scale[t] into mean[t].
+enum BudgetInput {
+    BUDGET_IN_S, BUDGET_IN_TS, BUDGET_IN_MP, BUDGET_IN_QS, BUDGET_IN_QL, BUDGET_IN_QC, BUDGET_IN_QV, BUDGET_IN_MV,
+    BUDGET_IN_ICE, BUDGET_IN_QIO, BUDGET_IN_JSIO, BUDGET_IN_LAND, BUDGET_IN_FRAZIL, BUDGET_INPUTS
+};
+struct BudgetArgs {
+    const double* in[BUDGET_INPUTS];
+    const void* mask;
+    const double* latitude;    // read only with reads_albedo and CF_ALBEDO_LATITUDE_DEPENDENT
+    double* mean[CF_AVERAGE_MAX_FIELDS];
+    double scale[CF_AVERAGE_MAX_FIELDS];
+    uint8_t kind[CF_AVERAGE_MAX_FIELDS];
+    int32_t n_terms, separable;
+    int32_t reads_albedo;      // some requested kind reads Qts
+    int32_t max_blocks;        // cf_budget_desc.max_workgroups (0: the kernel's own cap); the launcher reads it, the kernel does not
+};
+hipError_t launch_budget_average(hipStream_t st, const DevParams& P, const BudgetArgs& A, const GridDesc& G, bool store, double c_prev,
+                                 double c_new);
 // cf_integrals_collect (coflux_integrals.hip): one record of area-weighted, masked, regional integrals; the distinct `a` / `b`
 // arrays of the entries are numbered (field slots) by the host
 // interior cells per tile of the summation order (a constant of the record's bits; A/B builds may set it: 512 · 1 / 2 / 4)

@@ -28,11 +28,7 @@ __global__ __launch_bounds__(NET_BLOCK) void net_flux_kernel(DevParams P, GridDe
     const double aice_w = I.conc ? I.conc[kw] : 0.0;
     const double aice_s = I.conc ? I.conc[ks] : 0.0;
 
-    double alb = P.albedo;
-    if (P.albedo_kind == CF_ALBEDO_LATITUDE_DEPENDENT) {
-        double phi = Wt.separable ? Wt.latitude[j + G.hy] : Wt.latitude[k];
-        alb = P.albedo_diffuse - P.albedo_direct * cos(2.0 * phi * (CF_PI / 180.0));
-    }
+    const double alb = ocean_albedo_cell(P, ocean_latitude_cell(P, Wt, G, j, k));
     const NetCell C = net_cell_local(P, alb, aice, O.S[k], F.Ts[k] + P.T_offset, E.Mp[k], E.Qs[k], E.Ql[k], F.Qc[k], F.Qv[k],
                                      F.Fv[k], I.Qio ? I.Qio[k] : 0.0, I.Jsio ? I.Jsio[k] : 0.0, I.land ? I.land[k] : 0.0);
     const double tx = net_face_stress(P, F.tx[kw], F.tx[k], aice_w, aice, I.txio ? I.txio[k] : 0.0);

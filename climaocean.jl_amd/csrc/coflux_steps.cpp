@@ -544,10 +544,11 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
         } else {
             CHECK(cf_update_state(ctx, &s, w, o, a, fluxes, ice, net));
         }
-        // an attached averager (cf_attach_average) collects on the GLOBAL step index: a run split into several calls collects
-        // the same steps.  Queued behind every launch of the step — the face stresses of the merged and tail forms included
-        if (ctx->average && (step + 1) % ctx->average_stride == 0)
-            CHECK(average_collect(ctx->average, ctx->average_stride * ctx->average_step_weight));
+        // the attached averagers (cf_attach_average, cf_attach_average_slot), in slot order, collect on the GLOBAL step index: a run
+        // split into several calls collects the same steps.  Queued behind every launch of the step — the face stresses of the
+        // merged and tail forms included
+        for (const auto& slot : ctx->averages)
+            if (slot.collects(step)) CHECK(average_collect(slot.handle, slot.stride * slot.step_weight));
         // an attached integrator, then an attached monitor (SeriesAttachment): the same rule, one record per collected step
         if (ctx->integrals.collects(step)) CHECK(cf_integrals_collect(ctx->integrals.handle, ctx->integrals.stamp(step)));
         if (ctx->monitor.collects(step)) CHECK(cf_monitor_collect(ctx->monitor.handle, ctx->monitor.stamp(step)));

@@ -428,6 +428,49 @@ function CoFluxAverage(b::CoFluxBackend, terms::Vector{CfAverageTerm}; cos_rotat
     return a
 end
 
+# ---- the net heat and salt flux budget averaged in the collection launch (omip_diagnostics.jl:84-89,135-140) ---------------
+# JTao, JTio, JTf, JTn, JSn, JSio and the finer parts of compute_net_ocean_fluxes!'s two sums, evaluated per cell inside the
+# averager's launch from the arrays the net fluxes were computed from (include/coflux.h: cf_average_create_budget has the
+# table).  The result is an ordinary CoFluxAverage.  attach_average_slot! attaches up to CF_ATTACHED_AVERAGES_MAX averagers
+# to the step loops; slot 0 is attach_average!'s.
+const CF_BUDGET_HEAT_SHORTWAVE, CF_BUDGET_HEAT_LONGWAVE_UP, CF_BUDGET_HEAT_LONGWAVE_DOWN = Int32(0), Int32(1), Int32(2)
+const CF_BUDGET_HEAT_SENSIBLE, CF_BUDGET_HEAT_LATENT, CF_BUDGET_HEAT_ATMOSPHERE_OCEAN = Int32(3), Int32(4), Int32(5)
+const CF_BUDGET_HEAT_ICE_OCEAN, CF_BUDGET_HEAT_FRAZIL, CF_BUDGET_HEAT_NET = Int32(6), Int32(7), Int32(8)
+const CF_BUDGET_SALT_EVAPORATION, CF_BUDGET_SALT_PRECIPITATION, CF_BUDGET_SALT_ATMOSPHERE_OCEAN = Int32(9), Int32(10), Int32(11)
+const CF_BUDGET_SALT_ICE_OCEAN, CF_BUDGET_SALT_LAND, CF_BUDGET_SALT_NET = Int32(12), Int32(13), Int32(14)
+const CF_ATTACHED_AVERAGES_MAX = 4
+struct CfBudgetTerm
+    kind::Int32; reserved::Int32
+    scale::Float64
+    mean::Ptr{Float64}
+end
+struct CfBudgetDesc
+    struct_size::Int32; n_terms::Int32
+    terms::Ptr{CfBudgetTerm}
+    ocean::Ptr{CfOceanSurface}; exchange::Ptr{CfExchangeFields}; fluxes::Ptr{CfInterfaceFluxes}; ice::Ptr{CfSeaIceFields}
+    frazil_heat::Ptr{Float64}; land_freshwater::Ptr{Float64}
+    weights::Ptr{CfInterpWeights}
+    max_workgroups::Int32; reserved::Int32
+end
+function CoFluxAverage(b::CoFluxBackend, terms::Vector{CfBudgetTerm}; ocean = nothing, exchange = nothing, fluxes = nothing, ice = nothing,
+                       frazil_heat = C_NULL, land_freshwater = C_NULL, weights = nothing, max_workgroups = 0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    bundles = [isnothing(x) ? nothing : Ref(x) for x in (ocean, exchange, fluxes, ice, weights)]
+    GC.@preserve terms bundles begin
+        ptr(k, T) = isnothing(bundles[k]) ? Ptr{T}(C_NULL) : Base.unsafe_convert(Ptr{T}, bundles[k])
+        desc = CfBudgetDesc(sizeof(CfBudgetDesc), length(terms), pointer(terms), ptr(1, CfOceanSurface), ptr(2, CfExchangeFields),
+                            ptr(3, CfInterfaceFluxes), ptr(4, CfSeaIceFields), frazil_heat, land_freshwater, ptr(5, CfInterpWeights),
+                            max_workgroups, 0)
+        check(b.ctx, ccall((:cf_average_create_budget, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfBudgetDesc}, Ref{Ptr{Cvoid}}), b.ctx, desc, out))
+    end
+    a = CoFluxAverage(out[], b, Ptr{Float64}[], [t.mean for t in terms])
+    finalizer(x -> ccall((:cf_average_destroy, libcoflux), Cint, (Ptr{Cvoid},), x.ptr), a)
+    return a
+end
+attach_average_slot!(b, slot, a::Union{Nothing, CoFluxAverage}, stride = 1, step_weight = 1.0) =
+    check(b.ctx, ccall((:cf_attach_average_slot, libcoflux), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Float64),
+                       b.ctx, slot, isnothing(a) ? C_NULL : a.ptr, stride, step_weight))
+
 # ---- surface integrals on the device: scalar time series (omip_diagnostics.jl:194-218, visualize/common.jl:715-787) -----
 # An integrator turns surface fields into records of area-weighted, masked, regional integrals (one pass per collection)
 # and keeps the series on the device; read_integrals is the only host synchronisation.  attach_integrals! makes

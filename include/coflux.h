@@ -1160,6 +1160,123 @@ typedef struct cf_average_desc {
 int cf_average_create_derived(cf_ctx* ctx, const cf_average_desc* desc, cf_average** out);
 
 /* ------------------------------------------------------------------------------------------
+ * The net heat and salt flux budget averaged in the collection launch: the parts of hfds and wfo that the reference's
+ * `:surface` writer averages beside them — JTao, JTio, JTf, JTn, JSn, JSio (omip_diagnostics.jl:84-89,135-140) — and the
+ * finer split of the atmosphere–ocean part (shortwave, longwave up / down, sensible, latent; evaporation, precipitation,
+ * land).  compute_net_ocean_fluxes! forms every one of them per cell and stores only the two sums; here each is evaluated
+ * again per cell inside the averager's launch from the arrays that compute_net_ocean_fluxes! itself read, and no part is
+ * ever written to memory.
+ *
+ * cf_average_create_budget returns an ordinary cf_average: cf_average_collect / _reset / _weight / _destroy,
+ * cf_attach_average and cf_attach_average_slot work on it unchanged.  Each of its n_terms (1 … CF_AVERAGE_MAX_FIELDS) names
+ * one KIND of the table below and gives one SAMPLE per interior cell, which enters the recurrence of cf_average_collect in
+ * place of f (the first collection of a window stores and never reads the mean):
+ *     sample = x · scale        (always multiplied: scale = 1.0 is exact and keeps −0.0 and NaN)
+ * The inputs are compute_net_ocean_fluxes!'s: Sₒ = ocean->S, Qs / Ql / Mp of `exchange`, Qc = fluxes->sensible_heat,
+ * Qv = fluxes->latent_heat, Mv = fluxes->water_vapor, Ts = fluxes->temperature + the context's temperature offset,
+ * ℵ = ice->concentration, Qio = ice->interface_heat, Jsio = ice->salt_flux, q_fr = frazil_heat, Mland = land_freshwater;
+ * ℵ, Qio, Jsio, q_fr and Mland are 0.0 where their pointer (or `ice`) is NULL.  The parameters (emissivity ε, σ, albedo,
+ * penetrating_shortwave, ρ_f⁻¹, ρₒ⁻¹, cₒ⁻¹, the salinity floor S_min, the wet mask's kind) are the context's
+ * (cf_set_flux_params), read at each collection.  Order of operations, every product and sum rounded on its own in the
+ * order written (no FMA), the intermediates exactly compute_net_ocean_fluxes!'s:
+ *     om  = 1.0 − ℵ                    roc = ρₒ⁻¹ · cₒ⁻¹                 T2 = Ts · Ts
+ *     Qu  = ((ε · σ) · T2) · T2        Qal = (−ε) · Ql                   Qts = ((−(1.0 − α)) · Qs) · om
+ *     Qss = penetrating_shortwave ? 0.0 : Qts                            SQao = (((Qu + Qc) + Qv) + Qal) · om + Qss
+ *     Fp  = (−Mp) · ρ_f⁻¹              Fe  = Mv · ρ_f⁻¹                  SFao = Fp + Fe
+ *     floor = Sₒ < S_min and SFao < 0.0 (net freshening of water already at the floor: the SUM decides, not a part)
+ *     SFs = floor ? 0.0 : SFao         SFl = (−Mland) · ρ_f⁻¹            SFls = (Sₒ < S_min and SFl < 0.0) ? 0.0 : SFl
+ * α is the constant albedo or, with CF_ALBEDO_LATITUDE_DEPENDENT, compute_net_ocean_fluxes!'s own expression at the cell's
+ * latitude (weights->latitude: per row with weights->separable, per cell otherwise) — the one device function both share.
+ *
+ *   kind                              x                                          reads
+ *   CF_BUDGET_HEAT_SHORTWAVE          Qts · roc   (= net shortwave_surface_flux) Qs, ℵ (+ latitude)
+ *   CF_BUDGET_HEAT_LONGWAVE_UP        (Qu · om) · roc                            Ts, ℵ
+ *   CF_BUDGET_HEAT_LONGWAVE_DOWN      (Qal · om) · roc                           Ql, ℵ
+ *   CF_BUDGET_HEAT_SENSIBLE           (Qc · om) · roc                            Qc, ℵ
+ *   CF_BUDGET_HEAT_LATENT             (Qv · om) · roc                            Qv, ℵ
+ *   CF_BUDGET_HEAT_ATMOSPHERE_OCEAN   SQao · roc                        JTao     Qs, Ts, Ql, Qc, Qv, ℵ (+ latitude)
+ *   CF_BUDGET_HEAT_ICE_OCEAN          Qio · roc                         JTio     Qio
+ *   CF_BUDGET_HEAT_FRAZIL             q_fr · roc                        JTf      q_fr
+ *   CF_BUDGET_HEAT_NET                SQao · roc + Qio · roc  (= net T) JTn      those of JTao and JTio
+ *   CF_BUDGET_SALT_EVAPORATION        om · ((−Sₒ) · (floor ? 0.0 : Fe))          Sₒ, Mv, Mp, ℵ
+ *   CF_BUDGET_SALT_PRECIPITATION      om · ((−Sₒ) · (floor ? 0.0 : Fp))          Sₒ, Mv, Mp, ℵ
+ *   CF_BUDGET_SALT_ATMOSPHERE_OCEAN   om · ((−Sₒ) · SFs)                         Sₒ, Mv, Mp, ℵ
+ *   CF_BUDGET_SALT_ICE_OCEAN          Jsio                              JSio     Jsio
+ *   CF_BUDGET_SALT_LAND               (−Sₒ) · SFls                               Sₒ, Mland
+ *   CF_BUDGET_SALT_NET                (om · ((−Sₒ) · SFs) + Jsio) + (−Sₒ) · SFls  (= net S)   JSn    those of the three above
+ * The five heat parts sum to JTao (without the shortwave under penetrating_shortwave, which leaves it out of SQao) and
+ * evaporation + precipitation to SALT_ATMOSPHERE_OCEAN, each up to the roundings of the formulas; HEAT_NET and SALT_NET
+ * are bit for bit what cf_compute_net_ocean_fluxes and cf_update_state store in net T and S from the same inputs, and
+ * HEAT_SHORTWAVE what they store in shortwave_surface_flux.  A cell that is land by the context's mask (ocean->mask, both
+ * mask kinds; no mask: none) gives the sample 0.0 · scale whatever its inputs hold.  The restoring buffer and
+ * NormalizeSalinity's mean are an array and a scalar of their own and so are no kinds.
+ *
+ * CF_ERR_INVALID, with nothing allocated or launched: wrong struct_size; max_workgroups < 0 or reserved != 0; n_terms
+ * outside 1 … CF_AVERAGE_MAX_FIELDS or terms NULL; an unknown kind or a term whose reserved is not 0; a NULL mean; a NULL
+ * required input of a requested kind — Sₒ, Qs, Ql, Mp, Qc, Qv, Mv, Ts where the table's "reads" column names them (ℵ, Qio,
+ * Jsio, q_fr and Mland are optional: 0.0); a non-finite scale; a mean whose parent array ((nx + 2hx)(ny + 2hy) doubles
+ * from its pointer) overlaps an input that some requested kind reads, the wet mask or another mean; a kind that reads the albedo on a
+ * context with CF_ALBEDO_LATITUDE_DEPENDENT and no weights->latitude (cf_average_collect also returns it, launching
+ * nothing, when the parameters were changed to that later).  The descriptor, its term table and the bundles are host
+ * memory, read during the call only; the device arrays they name are borrowed.
+ *
+ * Footprint of a collection (ONE launch for all terms; each distinct input is loaded once per cell however many terms
+ * read it, and an input that no requested kind reads is never touched and may be NULL): reads on I the arrays of the
+ * "reads" column of the requested kinds, the wet mask on I when the context has one, and the latitude (row j of the
+ * interior with weights->separable, the cell otherwise) when a requested kind reads the albedo and it depends on
+ * latitude; reads and writes the means on I (the first collection of a window only writes them).  Nothing else is read or
+ * written.  The bits of every mean depend on those values, the parameters and the weights alone — not on halo widths, the
+ * launched grid or on which other terms ride along.  Algorithmic bytes per cell: 8 · (distinct inputs read) + the mask's
+ * 1 or 8 + 16 · n_terms accumulating, 8 · n_terms storing.
+ * ---------------------------------------------------------------------------------------- */
+#define CF_BUDGET_HEAT_SHORTWAVE          0
+#define CF_BUDGET_HEAT_LONGWAVE_UP        1
+#define CF_BUDGET_HEAT_LONGWAVE_DOWN      2
+#define CF_BUDGET_HEAT_SENSIBLE           3
+#define CF_BUDGET_HEAT_LATENT             4
+#define CF_BUDGET_HEAT_ATMOSPHERE_OCEAN   5   /* JTao */
+#define CF_BUDGET_HEAT_ICE_OCEAN          6   /* JTio */
+#define CF_BUDGET_HEAT_FRAZIL             7   /* JTf  */
+#define CF_BUDGET_HEAT_NET                8   /* JTn  */
+#define CF_BUDGET_SALT_EVAPORATION        9
+#define CF_BUDGET_SALT_PRECIPITATION      10
+#define CF_BUDGET_SALT_ATMOSPHERE_OCEAN   11
+#define CF_BUDGET_SALT_ICE_OCEAN          12  /* JSio */
+#define CF_BUDGET_SALT_LAND               13
+#define CF_BUDGET_SALT_NET                14  /* JSn  */
+#define CF_BUDGET_KINDS                   15
+typedef struct cf_budget_term {
+    int32_t kind, reserved;         /* CF_BUDGET_*; 0 */
+    double scale;
+    double* mean;
+} cf_budget_term;
+typedef struct cf_budget_desc {
+    int32_t struct_size, n_terms;
+    const cf_budget_term* terms;    /* HOST array */
+    const cf_ocean_surface* ocean;          /* S, mask (T, u, v are not read); any bundle may be NULL */
+    const cf_exchange_fields* exchange;     /* Qs, Ql, Mp */
+    const cf_interface_fluxes* fluxes;      /* sensible_heat, latent_heat, water_vapor, temperature */
+    const cf_sea_ice_fields* ice;           /* concentration, interface_heat, salt_flux */
+    const double* frazil_heat;
+    const double* land_freshwater;
+    const cf_interp_weights* weights;       /* latitude, separable: read only for the latitude-dependent albedo */
+    int32_t max_workgroups;         /* cap of a collection's launch, 0 = the library's (scheduling only, never results) */
+    int32_t reserved;               /* 0 */
+} cf_budget_desc;
+int cf_average_create_budget(cf_ctx* ctx, const cf_budget_desc* desc, cf_average** out);
+
+/* Several attached averagers: the OMIP surface set is two averagers and its budget a third.  A context has
+ * CF_ATTACHED_AVERAGES_MAX slots, each with its own stride and step weight; cf_time_steps and cf_time_steps_coupled collect
+ * the occupied slots in slot order at the point where cf_attach_average's averager is collected, slot s at every step with
+ * (step + 1) % stride_s == 0 and weight stride_s · step_weight_s.  Slot 0 IS cf_attach_average's slot: that call replaces
+ * slot 0 and leaves the others alone.  a = NULL empties the slot; cf_average_destroy empties whichever slot holds the
+ * averager.  CF_ERR_INVALID: a slot outside 0 … CF_ATTACHED_AVERAGES_MAX − 1, an averager of another context, one that
+ * another slot already holds, stride < 1, a step weight that is not > 0 and finite.
+ * Footprint: cf_time_steps' own, and cf_average_collect's of each occupied slot at every step it collects.              */
+#define CF_ATTACHED_AVERAGES_MAX 4
+int cf_attach_average_slot(cf_ctx* ctx, int32_t slot, cf_average* a, int32_t stride, double step_weight);
+
+/* ------------------------------------------------------------------------------------------
  * Area-weighted surface integrals and their time series on the device: the scalars every reference run derives from the
  * surface — the global means of the `:averages` writer (OMIPConfigurations/omip_diagnostics.jl:194-218) and the Arctic /
  * Antarctic sea-ice volume ∫ hᵢ ℵ dA, area ∫ ℵ dA and extent ∫ [ℵ > 0.15] dA of compute_ice_diagnostics
