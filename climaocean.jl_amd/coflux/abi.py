@@ -49,6 +49,7 @@ INTEGRALS_MAX_ENTRIES, INTEGRALS_MAX_FIELDS = 32, 32   # entries / distinct arra
 INTEGRAND_ONE, INTEGRAND_FIELD, INTEGRAND_PRODUCT, INTEGRAND_ABOVE = 0, 1, 2, 3
 MONITOR_MAX_ENTRIES = 16                             # entries of one surface monitor (cf_monitor_create)
 MONITOR_VALUE, MONITOR_ABS = 0, 1                    # cf_monitor_entry.kind: y = x | y = |x|
+CLIMATOLOGY_MAX_FIELDS, CLIMATOLOGY_MAX_BINS = 16, 32   # fields / calendar bins of one climatology (cf_climatology_create)
 REGRID_MAX_FIELDS = 16                               # fields of one apply of a surface regridder (cf_regrid_apply)
 REGRID_MEAN, REGRID_SUM = 0, 1
 SOLVER_PATH_EXACT, SOLVER_PATH_CERTIFIED = 0, 1      # how the Monin–Obukhov fixed point is reached (include/coflux.h)
@@ -289,6 +290,12 @@ MONITOR_VALUE_DTYPE = np.dtype([("minimum", "<f8"), ("maximum", "<f8"), ("argmin
 assert MONITOR_VALUE_DTYPE.itemsize == C.sizeof(MonitorValue) == 64
 
 
+class ClimatologyDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_fields", C.c_int32), ("n_bins", C.c_int32), ("max_workgroups", C.c_int32),
+                ("sources", C.c_void_p * CLIMATOLOGY_MAX_FIELDS), ("totals", C.c_void_p * CLIMATOLOGY_MAX_FIELDS),
+                ("bins", C.c_void_p * CLIMATOLOGY_MAX_FIELDS), ("reserved", C.c_int32 * 2)]
+
+
 class RegridDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("mode", C.c_int32), ("n_rows", C.c_int64), ("nnz", C.c_int64),
                 ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("weight", C.c_void_p), ("mask", C.c_void_p),
@@ -327,6 +334,8 @@ EXPORTED_SYMBOLS = (
     "cf_integrals_reset", "cf_attach_integrals",
     "cf_monitor_create", "cf_monitor_destroy", "cf_monitor_collect", "cf_monitor_count", "cf_monitor_read", "cf_monitor_status",
     "cf_monitor_reset", "cf_attach_monitor",
+    "cf_climatology_create", "cf_climatology_destroy", "cf_climatology_reset", "cf_climatology_collect", "cf_climatology_weights",
+    "cf_climatology_extremes", "cf_calendar_bin", "cf_attach_climatology",
     "cf_regrid_create", "cf_regrid_destroy", "cf_regrid_apply",
     "cf_prepare_coupled_step", "cf_time_steps_coupled",
 )
@@ -486,6 +495,14 @@ def load_library(path=None):
             getattr(lib, f"cf_{family}_{name}").argtypes = args
         getattr(lib, f"cf_attach_{family}").argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double]
     lib.cf_monitor_status.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]
+    lib.cf_climatology_create.argtypes = [vp, C.POINTER(ClimatologyDesc), C.POINTER(vp)]
+    lib.cf_climatology_destroy.argtypes = [vp]
+    lib.cf_climatology_reset.argtypes = [vp]
+    lib.cf_climatology_collect.argtypes = [vp, C.c_int32, C.c_double]
+    lib.cf_climatology_weights.argtypes = [vp, c_double_p, C.POINTER(C.c_int64), c_double_p, C.POINTER(C.c_int64)]
+    lib.cf_climatology_extremes.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+    lib.cf_calendar_bin.argtypes = [c_double_p, c_int32_p, C.c_int32, C.c_double, c_int32_p]
+    lib.cf_attach_climatology.argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double, C.c_double, c_double_p, c_int32_p, C.c_int32]
     lib.cf_regrid_create.argtypes = [vp, C.POINTER(RegridDesc), C.POINTER(vp)]
     lib.cf_regrid_destroy.argtypes = [vp]
     lib.cf_regrid_apply.argtypes = [vp, C.c_int32, C.POINTER(vp), C.POINTER(vp), vp]

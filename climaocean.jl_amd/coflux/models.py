@@ -19,6 +19,7 @@ them (model.interfaces.net_fluxes.ocean.{u,v,T,S}, omip_diagnostics.jl:77-80).
 The atmosphere holds a window of snapshots in HBM filled from a provider: synthetic in tests/bench, or the raw
 Float32 plane files of coflux/jra55.py (`omip_forcing`; NetCDF decoding itself is not possible in this image).
 """
+import datetime as _dt
 import logging
 import math
 import time
@@ -31,7 +32,7 @@ import torch
 
 from . import abi, synthetic
 from . import interface_computations as ic
-from .runtime import BUDGET_KINDS, EXCHANGE_NAMES, FLUX_NAMES, FLUX_OPTIONAL, NET_NAMES, FluxContext
+from .runtime import BUDGET_KINDS, EXCHANGE_NAMES, FLUX_NAMES, FLUX_OPTIONAL, NET_NAMES, FluxContext, calendar_bin
 
 minutes, hours, days = 60.0, 3600.0, 86400.0
 EARTH_RADIUS = 6.371e6   # m (Oceananigans' R_Earth)
@@ -683,7 +684,7 @@ def _clock_at(first_level, time_fraction, n_levels, step, increment):
     return level1, (level1 + 1) % n_levels, total - whole
 
 
-def time_steps(model, dt, nsteps, normalize=None, averages=None):
+def time_steps(model, dt, nsteps, normalize=None, averages=None, climatology=None):
     """`nsteps` × time_step!(coupled_model, Δt), each followed by `normalize(model)` (a NormalizeSalinity) when one is given,
     inside libcoflux (cf_time_steps_coupled): no host work between the steps.  For a model whose ocean has no step_callback,
     whose atmosphere and land are whole records in memory, and which has sea ice with a surface state; anything else raises
@@ -695,7 +696,13 @@ def time_steps(model, dt, nsteps, normalize=None, averages=None):
     what the context's attached averagers, integrator and monitor collect on.  `averages`: a SurfaceFluxAverages writer — ALL
     of its averagers are attached for the length of the call, one per slot from slot 0 (at most abi.ATTACHED_AVERAGES_MAX), and
     collect every step with weight Δt; the slots are emptied again on the way out.  Its window is the caller's: read
-    `averages.means` and reset the averagers."""
+    `averages.means` and reset the averagers.  `climatology`: a MonthlyClimatology writer — attached for the length of the call
+    (cf_attach_climatology): every step its schedule takes is binned by the calendar month of origin + (s + 1) · Δt, rounded to
+    the second, and collected behind the averagers; detached again on the way out.  The stamp is a product where the model's
+    clock is a repeated sum: after the rounding the two name the same second unless a step lies within their rounding error of
+    an x.5-second tie.  Every sample has the writer's `sample_weight`, stride · (1 / stride) as the library forms it from the
+    stride and a per-step weight — 1 but for rounding (exactly 1 for stride 1), and the same number that run!(simulation)
+    collects with, so the two paths weigh alike."""
     itf, atm, ocean, si, land = model.interfaces, model.atmosphere, model.ocean, model.sea_ice, getattr(model, "land", None)
     if ocean.step_callback is not None:
         raise ValueError("time_steps: the ocean has a step_callback (host work between the steps); use time_step")
@@ -749,11 +756,19 @@ def time_steps(model, dt, nsteps, normalize=None, averages=None):
     lent = dict(current, **averages._budget_atmos) if averages is not None and averages._budget_atmos else current
     for slot, averager in enumerate(attached):
         ctx.attach_average(averager, 1, dt, slot=slot)
+    if climatology is not None:
+        if not isinstance(climatology.schedule, IterationInterval):
+            raise ValueError("time_steps: the climatology's schedule is not an IterationInterval")
+        stride = climatology.schedule.interval
+        ctx.attach_climatology(climatology.climatology, climatology.table(t0, t0 + (nsteps + 1) * dt), stride, 1.0 / stride,
+                               t0 - first * dt, dt)
     try:
         _device_steps(model, dt, nsteps, normalize, clocks, first, lent, ai, state, stresses, exchange, ice_ocean, restoring)
     finally:
         for slot in range(len(attached)):
             ctx.attach_average(None, slot=slot)
+        if climatology is not None:
+            ctx.attach_climatology(None)
         if lent is not current:
             for name, t in averages._budget_atmos.items():
                 current[name].copy_(t)
@@ -1392,6 +1407,125 @@ def surface_global_means(model, **kw):
     net, ao = itf.net_fluxes._ocean_fields, itf.atmosphere_ocean_interface._fields
     fields = dict(hfds=net["T"], wfo=net["S"], hfss=ao["sensible_heat"], hfls=ao["latent_heat"], tos=st["T"], sos=st["S"])
     return SurfaceIntegrals(model, {name: ("mean", f, None, 0.0, REGION_GLOBAL) for name, f in fields.items()}, **kw)
+
+
+# ---------------------------------------------------------------------------------------------
+# calendar-binned means on the device (cf_climatology_*): the monthly climatologies under the reference's monthly figures
+# ---------------------------------------------------------------------------------------------
+def _month_start_seconds(reference_date, year, month):
+    d = _dt.datetime(year, month, 1) - reference_date
+    return d.days * 86400 + d.seconds
+
+
+def calendar_bins(reference_date, first_time, last_time, kind="month", start_time=0, stop_time=math.inf):
+    """The calendar table (edges, bin_of_interval) of cf_attach_climatology / cf_calendar_bin for times first_time … last_time
+    [s since reference_date]: month(reference_date + Second(round(Int, t))) of compute_monthly_means (visualize/common.jl:184)
+    as intervals of whole seconds in the proleptic Gregorian calendar (`datetime`, like Julia's Dates).  kind "month": bin
+    m − 1 for calendar month m; "season": 0 DJF, 1 MAM, 2 JJA, 3 SON.  The edges are the month starts from the month of
+    first_time to the end of the month of last_time; a rounded time outside [start_time, stop_time] (in_window, common.jl:161,
+    applied to the rounded time) lies in an interval of bin −1: not collected."""
+    if kind not in ("month", "season"):
+        raise ValueError(f"calendar_bins: kind = {kind!r} (\"month\" or \"season\")")
+    if not (math.isfinite(first_time) and math.isfinite(last_time) and first_time <= last_time):
+        raise ValueError(f"calendar_bins: times {first_time} … {last_time}")
+    first = reference_date + _dt.timedelta(seconds=round(first_time))
+    last = reference_date + _dt.timedelta(seconds=round(last_time))
+    months = []   # (start second, bin) from the month of `first` to the month after `last`
+    y, m = first.year, first.month
+    while True:
+        months.append((_month_start_seconds(reference_date, y, m), m - 1 if kind == "month" else (m % 12) // 3))
+        if (y, m) > (last.year, last.month):
+            break
+        y, m = (y, m + 1) if m < 12 else (y + 1, 1)
+    lo = math.ceil(start_time) if math.isfinite(start_time) else (-math.inf if start_time < 0 else math.inf)
+    hi = math.floor(stop_time) + 1 if math.isfinite(stop_time) else (math.inf if stop_time > 0 else -math.inf)
+    cuts = sorted({s for s, _ in months} | {c for c in (lo, hi) if months[0][0] < c < months[-1][0]})
+    edges, bins = np.array(cuts, dtype=np.float64), np.zeros(len(cuts) - 1, dtype=np.int32)
+    starts = [s for s, _ in months]
+    for k, a in enumerate(cuts[:-1]):
+        owner = months[int(np.searchsorted(starts, a, side="right")) - 1][1]
+        bins[k] = owner if lo <= a < hi else -1
+    return edges, bins
+
+
+class MonthlyClimatology:
+    """An output writer of calendar-binned means: MonthlyClimatology(model, outputs; schedule = IterationInterval(1),
+    reference_date = DateTime(1958, 1, 1), start_time = 0, stop_time = Inf) — compute_mean_and_monthly (visualize/common.jl:
+    191-208) taken while the model runs instead of from stored snapshots.  `outputs`: name → ocean-grid device field (at most
+    abi.CLIMATOLOGY_MAX_FIELDS).  Every scheduled iteration is one sample of equal weight (`sample_weight`: 1 but for the
+    rounding of stride · (1 / stride)) — the reference counts snapshots —
+    binned by month(reference_date + Second(round(Int, clock.time))) and collected in ONE launch (cf_climatology_collect) into
+    the field's mean over all samples and into its month; samples outside [start_time, stop_time] are not collected.
+    mean(name) / month(name, m) / extremes(name) read the device."""
+
+    def __init__(self, model, outputs, schedule=None, reference_date=_dt.datetime(1958, 1, 1), start_time=0, stop_time=math.inf):
+        ctx = self.ctx = model.interfaces.context
+        self.model, self.outputs = model, dict(outputs)
+        self.schedule = IterationInterval(schedule) if isinstance(schedule, int) else (schedule or IterationInterval(1))
+        self.reference_date, self.start_time, self.stop_time = reference_date, start_time, stop_time
+        self.n_bins = 12
+        self.names = list(self.outputs)
+        self.totals = {name: ctx.zeros() for name in self.names}
+        self.bins = {name: torch.zeros((self.n_bins,) + tuple(ctx.shape), dtype=torch.float64, device=ctx.device) for name in self.names}
+        self.climatology = ctx.climatology([self.outputs[n] for n in self.names], [self.totals[n] for n in self.names],
+                                           [self.bins[n] for n in self.names], self.n_bins)
+        self._table = None
+        # every sample weighs the same: the product the step loop forms from a stride and a per-step weight (1 but for rounding)
+        stride = getattr(self.schedule, "interval", 1)
+        self.sample_weight = stride * (1.0 / stride)
+        g = model.ocean.grid
+        (self._nx, self._ny, _), (self._hx, self._hy, _) = g.size, g.halo
+
+    def table(self, first_time, last_time):
+        """The calendar table that covers first_time … last_time (kept and reused while it does)."""
+        t = self._table
+        if t is None or not (t[0][0] <= round(first_time) and round(last_time) < t[0][-1]):
+            self._table = calendar_bins(self.reference_date, first_time, max(last_time, first_time + 400 * days), "month",
+                                        self.start_time, self.stop_time)
+        return self._table
+
+    def initialize(self, simulation):
+        pass
+
+    def write(self, clock):
+        if self.schedule.actuate(clock.iteration):
+            self.climatology.collect(calendar_bin(self.table(clock.time, clock.time), clock.time), self.sample_weight)
+
+    def _interior(self, t):
+        hx, hy = self._hx, self._hy
+        return t[hy:hy + self._ny, hx:hx + self._nx].to("cpu", copy=True).numpy()
+
+    def mean(self, name):
+        """The mean over every collected sample (interior, host array); None before the first."""
+        return self._interior(self.totals[name]) if self.climatology.weights()[1] else None
+
+    def month(self, name, m):
+        """The mean over the samples of calendar month m = 1 … 12; None for a bin that received nothing — the
+        reference's `nothing`."""
+        if not 1 <= m <= self.n_bins:
+            raise ValueError(f"month: m = {m} (1 … {self.n_bins})")
+        return self._interior(self.bins[name][m - 1]) if self.climatology.weights()[3][m - 1] else None
+
+    def extremes(self, name):
+        """(min, max, argmin_month, argmax_month) over the available months per interior cell — reduce_monthly(c, sym, min | max)
+        (visualize/cache.jl:696-712) with the month (1-based) that attains each; host arrays.  ValueError when no month is
+        available, as the reference raises."""
+        if not self.climatology.weights()[1]:
+            raise ValueError(f"{name} has no available monthly bins")
+        lo, hi, alo, ahi = self.climatology.extremes(self.names.index(name))
+        return self._interior(lo), self._interior(hi), self._interior(alo) + 1, self._interior(ahi) + 1
+
+    def close(self):
+        self.climatology.close()
+
+
+def sea_ice_concentration_climatology(model, **kw):
+    """What sic_mean, sic_march and sic_september read (visualize/cache.jl:634-648): the writer of the sea-ice concentration's
+    mean and monthly means — w.mean("sic"), w.month("sic", 3), w.month("sic", 9)."""
+    si = model.sea_ice
+    if si is None or si.concentration is None:
+        raise ValueError("sea_ice_concentration_climatology: the model has no sea ice")
+    return MonthlyClimatology(model, {"sic": si.concentration}, **kw)
 
 
 # ---------------------------------------------------------------------------------------------

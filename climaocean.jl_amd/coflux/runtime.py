@@ -565,6 +565,31 @@ class FluxContext:
         time_origin + (s + 1) · step_seconds (cf_attach_monitor), after the attached averager and integrator; None detaches."""
         self._attach_series("monitor", monitor, stride, time_origin, step_seconds)
 
+    # -- calendar-binned means --------------------------------------------------------------------
+    def climatology(self, sources, totals, bins, n_bins, max_workgroups=0):
+        """Device-side calendar-binned running means (cf_climatology_create): per field of `sources` (up to
+        abi.CLIMATOLOGY_MAX_FIELDS ocean-grid float64 fields) a total mean `totals[k]` (an ocean-grid field, or None: that
+        field keeps no total) and a block `bins[k]` of shape (n_bins,) + ctx.shape; collect(bin, weight) after each sample."""
+        return Climatology(self, sources, totals, bins, n_bins, max_workgroups)
+
+    def attach_climatology(self, clim, table=None, stride=1, step_weight=1.0, time_origin=0.0, step_seconds=1.0):
+        """time_steps() and time_steps_coupled() collect `clim` after every step s with (s + 1) % stride == 0, after the
+        attached averagers and before the integrator and the monitor: the step is stamped time_origin + (s + 1) · step_seconds,
+        `table` = (edges, bin_of_interval) — as coflux.models.calendar_bins builds it; the library copies it — gives the bin
+        (−1: not collected), the weight is stride · step_weight (cf_attach_climatology).  None detaches."""
+        if clim is None:
+            self._check(self.lib.cf_attach_climatology(self._h, None, 1, 1.0, 0.0, 0.0, None, None, 0), "cf_attach_climatology")
+            self._attached_climatology = None
+            return
+        edges = np.ascontiguousarray(table[0], dtype=np.float64)
+        bin_of_interval = np.ascontiguousarray(table[1], dtype=np.int32)
+        if edges.ndim != 1 or bin_of_interval.shape != (max(edges.size - 1, 0),):
+            raise ValueError(f"attach_climatology: {edges.size} edges bound {edges.size - 1} intervals, got {bin_of_interval.shape}")
+        self._check(self.lib.cf_attach_climatology(self._h, clim._h, int(stride), float(step_weight), float(time_origin), float(step_seconds),
+                                                   edges.ctypes.data_as(abi.c_double_p), bin_of_interval.ctypes.data_as(abi.c_int32_p),
+                                                   int(edges.size)), "cf_attach_climatology")
+        self._attached_climatology = clim   # kept alive while attached
+
     # -- sparse surface operators -----------------------------------------------------------------
     def regridder(self, row_ptr, col, weight, mask=None, mode="mean", max_workgroups=0):
         """A fixed sparse surface operator on the device (cf_regrid_create): CSR over destination rows — row_ptr (n_rows + 1),
@@ -632,7 +657,7 @@ BUDGET_KINDS = dict(heat_shortwave=abi.BUDGET_HEAT_SHORTWAVE, heat_longwave_up=a
 
 
 class _ChildHandle:
-    """What TimeAverager, SurfaceIntegrator, SurfaceMonitor, SurfaceRegridder and SnapshotWindow share: a handle `_h` made on the context
+    """What TimeAverager, Climatology, SurfaceIntegrator, SurfaceMonitor, SurfaceRegridder and SnapshotWindow share: a handle `_h` made on the context
     `ctx` that may outlive it (the library then fails every call but the `_destroy` one with "… has been destroyed")."""
     _destroy = None   # name of the cf_*_destroy entry point
 
@@ -855,6 +880,86 @@ class SurfaceMonitor(_SeriesHandle):
         first, entries = C.c_int64(), C.c_uint32()
         self._check(self.lib.cf_monitor_status(self._h, C.byref(first), C.byref(entries)), "cf_monitor_status")
         return first.value, entries.value
+
+
+def calendar_bin(table, time):
+    """The bin of `time` [s] in the calendar table (edges, bin_of_interval): cf_calendar_bin, a pure host function — the time
+    is rounded to the nearest second first, ties to even.  −1: not collected; ValueError outside the table or for a bad table."""
+    lib = abi.load_library()
+    edges = np.ascontiguousarray(table[0], dtype=np.float64)
+    bin_of_interval = np.ascontiguousarray(table[1], dtype=np.int32)
+    if edges.ndim != 1 or bin_of_interval.shape != (max(edges.size - 1, 0),):
+        raise ValueError(f"calendar_bin: {edges.size} edges bound {edges.size - 1} intervals, got {bin_of_interval.shape}")
+    out = C.c_int32(-2)
+    rc = lib.cf_calendar_bin(edges.ctypes.data_as(abi.c_double_p), bin_of_interval.ctypes.data_as(abi.c_int32_p), int(edges.size),
+                             float(time), C.byref(out))
+    if rc != 0:
+        raise ValueError(lib.cf_last_error(None).decode())
+    return out.value
+
+
+class Climatology(_ChildHandle):
+    """cf_climatology_*: after collections (bin, weight) every `totals[k]` holds Σ w f / Σ w of `sources[k]` over all of them
+    and bin b of `bins[k]` the same over the collections into b, on the interior (halos and every other bin untouched) — bit
+    for bit what TimeAveragers fed those subsequences hold, in one launch per collection.  The library borrows the pointers:
+    the tensors are kept alive here."""
+    _destroy = "cf_climatology_destroy"
+
+    def __init__(self, ctx, sources, totals, bins, n_bins, max_workgroups=0):
+        self._adopt(ctx)
+        self.sources, self.bins, self.n_bins = list(sources), list(bins), int(n_bins)
+        self.totals = list(totals) if totals is not None else [None] * len(self.sources)
+        n = self.n_fields = len(self.sources)
+        if len(self.totals) != n or len(self.bins) != n:
+            raise ValueError(f"{n} sources, {len(self.totals)} totals, {len(self.bins)} bin blocks")
+        if n > abi.CLIMATOLOGY_MAX_FIELDS:
+            raise ValueError(f"{n} fields (at most {abi.CLIMATOLOGY_MAX_FIELDS})")
+        for t in self.sources + [t for t in self.totals if t is not None]:
+            if not _is_field(t, ctx):
+                raise ValueError(f"sources and totals are contiguous float64 device arrays of shape {ctx.shape}")
+        for t in self.bins:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                    and tuple(t.shape) == (self.n_bins,) + tuple(ctx.shape)):
+                raise ValueError(f"a bin block is a contiguous float64 device array of shape {(self.n_bins,) + tuple(ctx.shape)}")
+        desc = abi.ClimatologyDesc()
+        desc.struct_size, desc.n_fields, desc.n_bins, desc.max_workgroups = C.sizeof(abi.ClimatologyDesc), n, self.n_bins, int(max_workgroups)
+        for k in range(n):
+            desc.sources[k], desc.bins[k] = self.sources[k].data_ptr(), self.bins[k].data_ptr()
+            desc.totals[k] = self.totals[k].data_ptr() if self.totals[k] is not None else None
+        ctx._check(self.lib.cf_climatology_create(ctx._h, C.byref(desc), C.byref(self._h)), "cf_climatology_create")
+
+    def collect(self, bin, weight):
+        """One launch: the sources enter the totals and bin `bin` with `weight`; bin −1: nothing is collected."""
+        self._check(self.lib.cf_climatology_collect(self._h, int(bin), float(weight)), "cf_climatology_collect")
+
+    def reset(self):
+        self._check(self.lib.cf_climatology_reset(self._h), "cf_climatology_reset")
+
+    def weights(self):
+        """(total weight, collections, per-bin weights [n_bins], per-bin collections [n_bins]) since the last reset."""
+        total, samples = C.c_double(), C.c_int64()
+        bin_totals, bin_samples = np.zeros(self.n_bins), np.zeros(self.n_bins, dtype=np.int64)
+        self._check(self.lib.cf_climatology_weights(self._h, C.byref(total), C.byref(samples), bin_totals.ctypes.data_as(abi.c_double_p),
+                                                    bin_samples.ctypes.data_as(C.POINTER(C.c_int64))), "cf_climatology_weights")
+        return total.value, samples.value, bin_totals, bin_samples
+
+    def extremes(self, field=0, minimum=True, maximum=True, argmin=True, argmax=True, out=None):
+        """(min, max, argmin, argmax) over the non-empty bins of field `field`, per interior cell, with Julia's min / max (a NaN
+        in any non-empty bin gives NaN, −0.0 < +0.0); the arg arrays (int32) hold the smallest bin that attains the result.
+        Ocean-grid device arrays whose halos are left as they were — zero in a fresh one; `out`: four arrays (or None) to
+        write instead.  An output whose flag is False is not computed and returned as None.  One launch."""
+        ctx = self.ctx
+        given = list(out) if out is not None else [None] * 4
+        made = []
+        for k, (want, dtype) in enumerate(((minimum, torch.float64), (maximum, torch.float64), (argmin, torch.int32), (argmax, torch.int32))):
+            t = given[k] if want else None
+            if want and t is None:
+                t = torch.zeros(ctx.shape, dtype=dtype, device=self.sources[0].device)
+            if t is not None and not _is_field(t, ctx, dtype):
+                raise ValueError(f"extremes: output {k} is a contiguous {dtype} device array of shape {ctx.shape}")
+            made.append(t)
+        self._check(self.lib.cf_climatology_extremes(self._h, int(field), *[_ptr(t) for t in made]), "cf_climatology_extremes")
+        return tuple(made)
 
 
 REGRID_MODES = dict(mean=abi.REGRID_MEAN, sum=abi.REGRID_SUM)

@@ -101,7 +101,9 @@ extern "C" int cf_average_create_budget(cf_ctx* ctx, const cf_budget_desc* desc,
         for (int s = 0; s < BUDGET_INPUTS; ++s)
             if (A.in[s] && fields_overlap(G, A.mean[t], A.in[s]))
                 return fail(ctx, CF_ERR_INVALID, "cf_average_create_budget: mean %d overlaps the input %s", t, INPUT_NAME[s]);
-        if (A.mask && fields_overlap(G, A.mean[t], A.mask))
+        // the mask's own bytes: a uint8 mask is an eighth of a parent array of doubles, and a mean right behind it is legal
+        const uintptr_t parent_bytes = (uintptr_t)G.sj * (uintptr_t)(G.ny + 2 * G.hy) * sizeof(double);
+        if (A.mask && ranges_overlap(A.mean[t], parent_bytes, A.mask, ctx->dev.mask_kind == CF_MASK_U8 ? parent_bytes / sizeof(double) : parent_bytes))
             return fail(ctx, CF_ERR_INVALID, "cf_average_create_budget: mean %d overlaps the mask", t);
         for (int u = 0; u < t; ++u)
             if (fields_overlap(G, A.mean[t], A.mean[u]))

@@ -68,6 +68,24 @@ struct SeriesAttachment {
     int64_t collections(int64_t first_step, int nsteps) const { return (first_step + nsteps) / stride - first_step / stride; }
 };
 
+// What the step loops know of an attached climatology (coflux_climatology.cpp; cf_attach_climatology): the integrals' clock and a
+// copy of the caller's calendar table
+struct cf_climatology;
+struct ClimatologyAttachment {
+    cf_climatology* handle = nullptr;
+    int32_t stride = 1;
+    double step_weight = 0.0, time_origin = 0.0, step_seconds = 0.0;
+    std::vector<double> edges;
+    std::vector<int32_t> bin_of_interval;
+    void detach() {
+        handle = nullptr;
+        edges.clear();
+        bin_of_interval.clear();
+    }
+    bool collects(int64_t step) const { return handle && (step + 1) % stride == 0; }
+    double stamp(int64_t step) const { return time_origin + (double)(step + 1) * step_seconds; }
+};
+
 // Ownership: every stream, event, device buffer and IPC mapping below is a cf:: owner (coflux_owned.hpp) and releases itself
 // with the context; LaunchCfg, PeerMailbox and the kernels' arguments carry raw pointers filled from get().  Resources that
 // only make sense together sit in one struct, built aside and moved in only when all of it was created.
@@ -217,6 +235,8 @@ struct cf_ctx {
     // the series recorders cf_time_steps collects after it: surface integrals (cf_attach_integrals), then the monitor (cf_attach_monitor)
     SeriesAttachment<cf_integrals> integrals;
     SeriesAttachment<cf_monitor> monitor;
+    // the calendar-binned means the step loops collect between the averager slots and the integrator (cf_attach_climatology)
+    ClimatologyAttachment climatology;
 };
 
 // One cf_time_steps call's step loop, as CF_OPT_LAND_ZEROS sees it: open for exactly the scope's lifetime
@@ -243,6 +263,19 @@ struct cf_average : cf_child {
     DerivedArgs terms{};
     bool budget = false;     // made by cf_average_create_budget (coflux_budget.cpp): `budget_terms` replaces `fields`
     BudgetArgs budget_terms{};
+};
+
+// calendar-binned means (coflux_climatology.cpp): the pointers are the caller's, the weights are host bookkeeping — the handle
+// owns no device resource
+struct cf_climatology : cf_child {
+    int n_fields = 0, n_bins = 0, max_blocks = 0;
+    const double* src[CF_CLIMATOLOGY_MAX_FIELDS] = {};
+    double* total[CF_CLIMATOLOGY_MAX_FIELDS] = {};
+    double* bins[CF_CLIMATOLOGY_MAX_FIELDS] = {};
+    double weight = 0.0;       // of every collection since the reset
+    int64_t samples = 0;
+    double bin_weight[CF_CLIMATOLOGY_MAX_BINS] = {};
+    int64_t bin_samples[CF_CLIMATOLOGY_MAX_BINS] = {};
 };
 
 struct cf_regrid : cf_child {
@@ -273,6 +306,10 @@ int cf_fail(cf_ctx* ctx, int code, const char* fmt, ...);
 extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows);
 // coflux_average.cpp: one collection of `a` (cf_average_collect without the argument checks of the ABI entry)
 int average_collect(cf_average* a, double weight);
+// coflux_climatology.cpp: one collection of `c` into bin ≥ 0 (cf_climatology_collect without the argument checks of the ABI
+// entry); the bin of `time` in a calendar table that cf_attach_climatology has validated (false: outside the table)
+int climatology_collect(cf_climatology* c, int32_t bin, double weight);
+bool calendar_lookup(const std::vector<double>& edges, const std::vector<int32_t>& bin_of_interval, double time, int32_t* bin);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state); *route is the counter of
 // ctx->prefetch_stats that names the launch it left in
 extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx, uint64_t* route);
@@ -300,6 +337,12 @@ inline bool fields_overlap(const GridDesc& G, const void* p, const void* q) {
     return x < y + bytes && y < x + bytes;
 }
 
+// the same for two byte ranges of their own lengths (a block of several parent arrays, a uint8 mask)
+inline bool ranges_overlap(const void* p, uintptr_t bytes_p, const void* q, uintptr_t bytes_q) {
+    const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
+    return x < y + bytes_q && y < x + bytes_p;
+}
+
 // The child handles: `child` joins ctx's list / leaves it (a no-op once orphaned) / cf_destroy orphans them all
 inline void child_adopt(cf_ctx* ctx, cf_child* child) {
     child->ctx = ctx;
@@ -315,6 +358,7 @@ inline void orphan_children(cf_ctx* ctx) {
     for (auto& slot : ctx->averages) slot.handle = nullptr;
     ctx->integrals.detach();
     ctx->monitor.detach();
+    ctx->climatology.detach();
 }
 // CF_ERR_INVALID unless `child` is a handle whose context is alive: live(a, "cf_average_reset", "averager")
 inline int live(const cf_child* child, const char* fn, const char* kind) {

@@ -182,6 +182,27 @@ struct AverageFields {
 };
 hipError_t launch_average(hipStream_t st, const AverageFields& F, int nfields, const GridDesc& G, bool store, double c_prev,
                           double c_new);
+// cf_climatology_collect (coflux_climatology.hip): per field the source enters the total's running mean (total[f] NULL: this
+// field keeps none) and ONE bin's (bin[f] already points at that bin's parent array), each stored or blended with its own
+// coefficients, one launch; max_blocks: cf_climatology_desc.max_workgroups (0: the kernel's own cap)
+struct ClimatologyFields {
+    const double* src[CF_CLIMATOLOGY_MAX_FIELDS];
+    double* total[CF_CLIMATOLOGY_MAX_FIELDS];
+    double* bin[CF_CLIMATOLOGY_MAX_FIELDS];
+};
+struct ClimatologyBlend {
+    double total_prev, total_new, bin_prev, bin_new;
+};
+hipError_t launch_climatology(hipStream_t st, const ClimatologyFields& F, int nfields, const GridDesc& G, bool store_total,
+                              bool store_bin, const ClimatologyBlend& C, int max_blocks);
+// cf_climatology_extremes (coflux_climatology.hip): per interior cell Julia's min / max over the n listed bins of one field's
+// block, in list order (the host lists the non-empty bins ascending); any output may be NULL
+struct ClimatologyBinList {
+    int32_t n;
+    uint8_t bin[CF_CLIMATOLOGY_MAX_BINS];
+};
+hipError_t launch_climatology_extremes(hipStream_t st, const double* bins, size_t parent, const ClimatologyBinList& L, const GridDesc& G,
+                                       double* d_min, double* d_max, int32_t* d_argmin, int32_t* d_argmax, int max_blocks);
 // cf_average_collect of a derived averager (coflux_derived.hip): the distinct source arrays of the terms (rotation arrays
 // included) are numbered by the host; term t reads slots a[t] / b[t]; bit s of need_x / need_y: some term reads slot s at
 // [i+1] / [j+1]; cos_slot / sin_slot: −1 without an EAST / NORTH term

@@ -443,6 +443,16 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
     }
     CHECK(series_room(ctx, ctx->integrals, first_step, nsteps, "integrator"));   // a series that would overflow: nothing is launched
     CHECK(series_room(ctx, ctx->monitor, first_step, nsteps, "monitor"));
+    // an attached climatology whose calendar table does not cover a step it would collect: nothing is launched either
+    if (ctx->climatology.handle)
+        for (int64_t step = first_step; step < first_step + nsteps; ++step) {
+            int32_t bin;
+            if (ctx->climatology.collects(step) &&
+                !calendar_lookup(ctx->climatology.edges, ctx->climatology.bin_of_interval, ctx->climatology.stamp(step), &bin))
+                return fail(ctx, CF_ERR_INVALID, "%s: step %lld at time %.17g lies outside the attached climatology's calendar table "
+                            "[%.17g, %.17g)", name, (long long)step, ctx->climatology.stamp(step), ctx->climatology.edges.front(),
+                            ctx->climatology.edges.back());
+        }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (int n = 0; n < S->n_ocean_states; ++n) {
         if (ctx->dev.mask_kind != CF_MASK_NONE && !S->ocean_states[n].mask) return fail(ctx, CF_ERR_INVALID, "ocean state %d has no mask", n);
@@ -549,6 +559,14 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
         // merged and tail forms included
         for (const auto& slot : ctx->averages)
             if (slot.collects(step)) CHECK(average_collect(slot.handle, slot.stride * slot.step_weight));
+        // the attached climatology (cf_attach_climatology): the same rule, into the bin its calendar gives the step's time (−1:
+        // outside the analysis window, nothing is collected; the table covers the step: checked before the first launch)
+        if (ctx->climatology.collects(step)) {
+            const ClimatologyAttachment& at = ctx->climatology;
+            int32_t bin = -1;
+            calendar_lookup(at.edges, at.bin_of_interval, at.stamp(step), &bin);
+            if (bin >= 0) CHECK(climatology_collect(at.handle, bin, at.stride * at.step_weight));
+        }
         // an attached integrator, then an attached monitor (SeriesAttachment): the same rule, one record per collected step
         if (ctx->integrals.collects(step)) CHECK(cf_integrals_collect(ctx->integrals.handle, ctx->integrals.stamp(step)));
         if (ctx->monitor.collects(step)) CHECK(cf_monitor_collect(ctx->monitor.handle, ctx->monitor.stamp(step)));

@@ -21,6 +21,8 @@
 # by libcoflux (cf_device_alloc) and wrapped in `unsafe_wrap`-free handle structs.
 module CoFluxMI355X
 
+using Dates: Dates, DateTime, Second, month   # the calendar table of the climatologies (monthly_table)
+
 const libcoflux = get(ENV, "LIBCOFLUX", "libcoflux.so")
 
 # ---- mirrors of the POD structs in include/coflux.h (field order is the ABI) -----------------
@@ -589,6 +591,73 @@ end
 attach_monitor!(b, m::Union{Nothing, CoFluxMonitor}, stride = 1, time_origin = 0.0, step_seconds = 1.0) =
     check(b.ctx, ccall((:cf_attach_monitor, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Float64),
                        b.ctx, isnothing(m) ? C_NULL : m.ptr, stride, time_origin, step_seconds))
+
+# ---- calendar-binned means on the device (visualize/common.jl:176-208, cache.jl:634-712) -----------------------------------
+# A climatology bins up to 16 surface fields by calendar month (or any table of time intervals) while the model runs: one
+# launch per sample adds the source to the field's mean over all samples and to its bin's, each the running mean a
+# CoFluxAverager keeps.  `bins[f]` is a device block of n_bins ocean-grid arrays back to back; `totals[f]` may be C_NULL.
+# The calendar table is (edges, bin_of_interval): strictly increasing seconds and one bin (0-based, -1: not collected) per
+# interval; month(reference_date + Second(round(Int, t))) becomes the month starts as edges (monthly_table below).
+const CF_CLIMATOLOGY_MAX_FIELDS, CF_CLIMATOLOGY_MAX_BINS = 16, 32
+struct CfClimatologyDesc
+    struct_size::Int32; n_fields::Int32; n_bins::Int32; max_workgroups::Int32
+    sources::NTuple{16, Ptr{Float64}}
+    totals::NTuple{16, Ptr{Float64}}
+    bins::NTuple{16, Ptr{Float64}}
+    reserved::NTuple{2, Int32}
+end
+function CfClimatologyDesc(sources, totals, bins, n_bins; max_workgroups = 0)
+    n = length(sources)
+    (n <= 16 && length(totals) == n && length(bins) == n) || error("CoFluxMI355X: at most 16 climatology fields, one total and one bin block each")
+    pad(v) = ntuple(k -> k <= n ? Ptr{Float64}(v[k]) : Ptr{Float64}(C_NULL), 16)
+    return CfClimatologyDesc(sizeof(CfClimatologyDesc), n, n_bins, max_workgroups, pad(sources), pad(totals), pad(bins), (Int32(0), Int32(0)))
+end
+mutable struct CoFluxClimatology
+    ptr::Ptr{Cvoid}
+    backend::CoFluxBackend
+    n_fields::Int
+    n_bins::Int
+end
+function CoFluxClimatology(b::CoFluxBackend, desc::CfClimatologyDesc)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(b.ctx, ccall((:cf_climatology_create, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfClimatologyDesc}, Ref{Ptr{Cvoid}}), b.ctx, desc, out))
+    c = CoFluxClimatology(out[], b, desc.n_fields, desc.n_bins)
+    finalizer(x -> ccall((:cf_climatology_destroy, libcoflux), Cint, (Ptr{Cvoid},), x.ptr), c)
+    return c
+end
+# bin: 0-based, -1 collects nothing
+collect!(c::CoFluxClimatology, bin, weight) =
+    check(C_NULL, ccall((:cf_climatology_collect, libcoflux), Cint, (Ptr{Cvoid}, Int32, Float64), c.ptr, bin, weight))
+reset!(c::CoFluxClimatology) = check(C_NULL, ccall((:cf_climatology_reset, libcoflux), Cint, (Ptr{Cvoid},), c.ptr))
+function climatology_weights(c::CoFluxClimatology)
+    total = Ref{Float64}(0); samples = Ref{Int64}(0); bin_totals = zeros(Float64, c.n_bins); bin_samples = zeros(Int64, c.n_bins)
+    check(C_NULL, ccall((:cf_climatology_weights, libcoflux), Cint, (Ptr{Cvoid}, Ref{Float64}, Ref{Int64}, Ptr{Float64}, Ptr{Int64}),
+                        c.ptr, total, samples, bin_totals, bin_samples))
+    return (total = total[], samples = samples[], bin_totals = bin_totals, bin_samples = bin_samples)
+end
+# per interior cell min / max over the non-empty bins (Base.min / max semantics) and the 0-based bin of each; any output C_NULL
+climatology_extremes!(c::CoFluxClimatology, field, d_min, d_max, d_argmin = C_NULL, d_argmax = C_NULL) =
+    check(C_NULL, ccall((:cf_climatology_extremes, libcoflux), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                        c.ptr, field, d_min, d_max, d_argmin, d_argmax))
+function calendar_bin(edges::Vector{Float64}, bin_of_interval::Vector{Int32}, time)
+    bin = Ref{Int32}(-1)
+    check(C_NULL, ccall((:cf_calendar_bin, libcoflux), Cint, (Ptr{Float64}, Ptr{Int32}, Int32, Float64, Ref{Int32}),
+                        edges, bin_of_interval, length(edges), time, bin))
+    return bin[]
+end
+# the month table of compute_monthly_means for the years `years` (bins 0 … 11): monthly_table(DateTime(1958, 1, 1), 1958:1961)
+function monthly_table(reference_date, years)
+    starts = [DateTime(y, m, 1) for y in years for m in 1:12]
+    push!(starts, DateTime(last(years) + 1, 1, 1))
+    edges = Float64[Dates.value(Second(d - reference_date)) for d in starts]
+    return edges, Int32[month(d) - 1 for d in starts[1:end-1]]
+end
+function attach_climatology!(b, c::Union{Nothing, CoFluxClimatology}, edges::Vector{Float64} = Float64[], bin_of_interval::Vector{Int32} = Int32[];
+                             stride = 1, step_weight = 1.0, time_origin = 0.0, step_seconds = 1.0)
+    check(b.ctx, ccall((:cf_attach_climatology, libcoflux), Cint,
+                       (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Float64, Float64, Ptr{Float64}, Ptr{Int32}, Int32),
+                       b.ctx, isnothing(c) ? C_NULL : c.ptr, stride, step_weight, time_origin, step_seconds, edges, bin_of_interval, length(edges)))
+end
 
 # ---- a fixed sparse surface operator on the device (visualize/cache.jl:918-937, 983-1011) ---------------------------------
 # CSR over destination rows: `row_ptr` (0-based, n_rows + 1 entries), `col` (0-based interior cell numbers j·nx + i) and

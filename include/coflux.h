@@ -47,7 +47,8 @@ extern "C" {
                           * cf_debug_land_zero_launches — with them cf_time_steps gained a contract on its outputs, stated there;
                           * likewise the surface monitor (cf_monitor_*, cf_attach_monitor); likewise cf_debug_prefetch_stats — with it
                           * a state requested ahead is matched by its source and weights as well, and a third pending request is
-                          * refused when it is made: both stated at cf_prefetch_atmosphere_state */
+                          * refused when it is made: both stated at cf_prefetch_atmosphere_state; likewise the calendar-binned
+                          * means (cf_climatology_*, cf_calendar_bin, cf_attach_climatology) */
 
 /* status codes */
 #define CF_OK 0
@@ -1453,6 +1454,86 @@ int cf_monitor_status(cf_monitor* m, int64_t* first_bad_record, uint32_t* bad_en
 int cf_monitor_reset(cf_monitor* m);
 /* Footprint: cf_time_steps' own, and cf_monitor_collect's at every collected step.                                     */
 int cf_attach_monitor(cf_ctx* ctx, cf_monitor* m, int32_t stride, double time_origin, double step_seconds);
+
+/* ------------------------------------------------------------------------------------------
+ * Calendar-binned means of surface fields on the device: the monthly climatologies under every monthly figure of a
+ * reference analysis — compute_monthly_means / compute_mean_and_monthly (experiments/OMIPSimulations/scripts/visualize/
+ * common.jl:176-208) add each saved sample into one of twelve calendar-month bins and into a total, the month being
+ * month(reference_date + Second(round(Int, t))); the March / September sea-ice maps (visualize/cache.jl:634-686) and the
+ * per-cell minimum / maximum over the available months, reduce_monthly (cache.jl:696-712), sit on top.  A climatology
+ * holds up to CF_CLIMATOLOGY_MAX_FIELDS fields; per field a source, an optional TOTAL mean and a block of n_bins
+ * (1 … CF_CLIMATOLOGY_MAX_BINS) BIN means, every one an ocean-grid f64 array in the usual halo layout; bin b of field f
+ * starts (nx + 2hx)(ny + 2hy) · b doubles into bins[f].  Still ABI 5: additive.
+ *   Collection.  cf_climatology_collect of (bin, weight) is ONE launch over the interior I of every field: the source is
+ *     loaded once per cell and enters two running means by the recurrence of cf_average_collect, each with its OWN
+ *     coefficients computed on the host in double — the total's from the weight of every collection since the reset,
+ *     bin `bin`'s from the weight that bin has received.  The total stores without reading on the first collection since
+ *     the reset, the bin stores without reading on ITS first collection (a fresh buffer may hold NaNs); no other bin is
+ *     touched.  bin = −1: nothing is collected — no launch, no weight changes (a sample outside the analysis window).
+ *   Contract.  After any sequence of collections the total holds, bit for bit, what a cf_average collecting the same
+ *     samples and weights holds, and bin b what a cf_average collecting only bin b's subsequence holds.  The bits do not
+ *     depend on the halo widths, where the arrays start in memory, the launched grid (`max_workgroups`), or which other
+ *     fields ride along.
+ *   Footprint of a collection: reads the sources on I; reads and writes — or, where it stores, only writes — the totals
+ *     and the one bin on I.  Nothing else is accessed: the halos of every mean, the gaps between the bins of a block and
+ *     all other bins included.  40 algorithmic bytes per cell and field when both accumulate, 24 when both store.
+ *   Extremes.  cf_climatology_extremes is one launch for one field: per interior cell the minimum and maximum over the bins
+ *     that have at least one sample, taken in ascending bin order with Julia's min / max (what reduce_monthly applies): a NaN
+ *     in any non-empty bin gives NaN (its payload is not part of the contract), −0.0 < +0.0.  d_argmin / d_argmax (int32
+ *     arrays indexed like the halo layout) receive the smallest bin index that attains the result, or the first NaN bin.
+ *     Any of the four outputs may be NULL; only I of an output is written.  Empty bins are never read: they may be poison.
+ *     CF_ERR_INVALID when every bin is empty (the reference raises "has no available monthly bins").
+ *   Calendar.  A table is n_edges strictly increasing times `edges` [s]; interval k = [edges[k], edges[k+1]) carries
+ *     bin_of_interval[k] in −1 … n_bins − 1 (−1: not collected — how a start_time / stop_time window is expressed).  The
+ *     lookup rounds first, as the reference does: t_r = rint(time), ties to even (Julia's round(Int, ·)), then finds k with
+ *     edges[k] ≤ t_r < edges[k+1].  cf_calendar_bin is that lookup as a pure host function (no context, no device): a time
+ *     outside the table — below edges[0], at or beyond the last edge, or not finite — is CF_ERR_INVALID, and so are
+ *     n_edges < 2, a NULL argument, edges that are not strictly increasing and finite, and an interval bin below −1.
+ *   cf_attach_climatology copies the table.  cf_time_steps and cf_time_steps_coupled then collect `c` at every step s
+ *     (global index) with (s + 1) % stride == 0, stamped time_origin + (s + 1) · step_seconds (cf_attach_integrals' clock),
+ *     into the bin the lookup gives, with weight stride · step_weight — after the averager slots, before the integrator and
+ *     the monitor.  One climatology per context; NULL detaches; cf_climatology_destroy detaches too.  A call any of whose
+ *     collected steps falls outside the table fails with CF_ERR_INVALID before it launches anything.  A run split into
+ *     CF_PIPELINE_CONTINUING calls collects what one call collects.  With nothing attached the step loops issue exactly the
+ *     launches they issued before.
+ *   Errors (CF_ERR_INVALID, nothing allocated or launched).  create: a wrong struct_size, n_fields outside
+ *     1 … CF_CLIMATOLOGY_MAX_FIELDS, n_bins outside 1 … CF_CLIMATOLOGY_MAX_BINS, a NULL source or bins, a total or a bin
+ *     block whose bytes (a parent array; n_bins parent arrays) overlap a source's parent array or another output,
+ *     max_workgroups < 0, reserved != 0.  collect: a bin outside −1 … n_bins − 1, a weight that is not > 0 and finite.
+ *     extremes: a field outside 0 … n_fields − 1, every bin empty.  attach: a climatology of another context, stride < 1,
+ *     a step weight that is not > 0 and finite, a non-finite origin or step, a bad table (above) or an interval bin beyond
+ *     n_bins − 1.  A climatology outlived by its context may still be destroyed; every other call on it fails.
+ *   cf_climatology_reset   all weights 0: the next collection stores into the total and into its bin.  No device work.
+ *   cf_climatology_weights the total weight and collection count since the reset, and per bin (arrays of n_bins); any
+ *                          pointer may be NULL.  Host bookkeeping only.
+ * Slabs: each context bins its own rows; there is nothing to combine.  Only fields that exist are binned (no derived or
+ * budget terms), and the calendar is the caller's table (coflux.models.calendar_bins builds the proleptic Gregorian one).
+ * ---------------------------------------------------------------------------------------- */
+#define CF_CLIMATOLOGY_MAX_FIELDS 16
+#define CF_CLIMATOLOGY_MAX_BINS 32
+typedef struct cf_climatology_desc {
+    int32_t struct_size;      /* sizeof(cf_climatology_desc) */
+    int32_t n_fields;         /* 1…CF_CLIMATOLOGY_MAX_FIELDS */
+    int32_t n_bins;           /* 1…CF_CLIMATOLOGY_MAX_BINS */
+    int32_t max_workgroups;   /* 0: the library's choice; > 0 caps the launch (scheduling only: never a bit of a result) */
+    const double* sources[CF_CLIMATOLOGY_MAX_FIELDS];   /* ocean-grid f64, halo layout, borrowed */
+    double* totals[CF_CLIMATOLOGY_MAX_FIELDS];          /* mean over every collected sample; NULL: this field keeps no total */
+    double* bins[CF_CLIMATOLOGY_MAX_FIELDS];            /* n_bins parent arrays back to back */
+    int32_t reserved[2];
+} cf_climatology_desc;
+typedef struct cf_climatology cf_climatology;
+int cf_climatology_create(cf_ctx* ctx, const cf_climatology_desc* desc, cf_climatology** out);
+int cf_climatology_destroy(cf_climatology* c);
+int cf_climatology_reset(cf_climatology* c);
+/* Footprint: reads the sources on I; reads and writes (or only writes) the totals and bin `bin` on I.  Nothing else.   */
+int cf_climatology_collect(cf_climatology* c, int32_t bin, double weight);
+int cf_climatology_weights(cf_climatology* c, double* total, int64_t* samples, double* bin_totals, int64_t* bin_samples);
+/* Footprint: reads the non-empty bins of `field` on I; writes the outputs that are not NULL on I.                      */
+int cf_climatology_extremes(cf_climatology* c, int32_t field, double* d_min, double* d_max, int32_t* d_argmin, int32_t* d_argmax);
+int cf_calendar_bin(const double* edges, const int32_t* bin_of_interval, int32_t n_edges, double time, int32_t* bin);
+/* Footprint: the step loops' own, and cf_climatology_collect's at every collected step.                                */
+int cf_attach_climatology(cf_ctx* ctx, cf_climatology* c, int32_t stride, double step_weight, double time_origin,
+                          double step_seconds, const double* edges, const int32_t* bin_of_interval, int32_t n_edges);
 
 /* ------------------------------------------------------------------------------------------
  * A fixed sparse surface operator applied on the device: the conservative regridding of surface fields onto the shared
