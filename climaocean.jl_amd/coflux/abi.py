@@ -50,6 +50,8 @@ INTEGRAND_ONE, INTEGRAND_FIELD, INTEGRAND_PRODUCT, INTEGRAND_ABOVE = 0, 1, 2, 3
 MONITOR_MAX_ENTRIES = 16                             # entries of one surface monitor (cf_monitor_create)
 MONITOR_VALUE, MONITOR_ABS = 0, 1                    # cf_monitor_entry.kind: y = x | y = |x|
 CLIMATOLOGY_MAX_FIELDS, CLIMATOLOGY_MAX_BINS = 16, 32   # fields / calendar bins of one climatology (cf_climatology_create)
+CHECKPOINT_MAX_SECTIONS = 256                        # sections of one checkpoint handle (cf_checkpoint_add_*)
+CHECKPOINT_DIRECT = 1                                # cf_checkpoint_desc.flags
 REGRID_MAX_FIELDS = 16                               # fields of one apply of a surface regridder (cf_regrid_apply)
 REGRID_MEAN, REGRID_SUM = 0, 1
 SOLVER_PATH_EXACT, SOLVER_PATH_CERTIFIED = 0, 1      # how the Monin–Obukhov fixed point is reached (include/coflux.h)
@@ -302,6 +304,10 @@ class RegridDesc(C.Structure):
                 ("max_workgroups", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CheckpointDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("flags", C.c_int32), ("max_workgroups", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PrefetchStats(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("pending", C.c_int32)] + [(n, C.c_uint64) for n in (
         "requests", "launched_aux", "launched_tail", "launched_merged", "launched_ice_tail", "launched_own",
@@ -338,6 +344,9 @@ EXPORTED_SYMBOLS = (
     "cf_climatology_extremes", "cf_calendar_bin", "cf_attach_climatology",
     "cf_regrid_create", "cf_regrid_destroy", "cf_regrid_apply",
     "cf_prepare_coupled_step", "cf_time_steps_coupled",
+    "cf_checkpoint_create", "cf_checkpoint_destroy", "cf_checkpoint_add_array", "cf_checkpoint_add_average", "cf_checkpoint_add_climatology",
+    "cf_checkpoint_add_integrals", "cf_checkpoint_add_monitor", "cf_checkpoint_set_host_blob", "cf_checkpoint_capture", "cf_checkpoint_wait",
+    "cf_checkpoint_restore", "cf_checkpoint_verify", "cf_checkpoint_hash", "cf_checkpoint_host_blob",
 )
 
 PACKAGE_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -506,6 +515,18 @@ def load_library(path=None):
     lib.cf_regrid_create.argtypes = [vp, C.POINTER(RegridDesc), C.POINTER(vp)]
     lib.cf_regrid_destroy.argtypes = [vp]
     lib.cf_regrid_apply.argtypes = [vp, C.c_int32, C.POINTER(vp), C.POINTER(vp), vp]
+    lib.cf_checkpoint_create.argtypes = [vp, C.POINTER(CheckpointDesc), C.POINTER(vp)]
+    lib.cf_checkpoint_destroy.argtypes = [vp]
+    lib.cf_checkpoint_add_array.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
+    for kind in ("average", "climatology", "integrals", "monitor"):
+        getattr(lib, "cf_checkpoint_add_" + kind).argtypes = [vp, C.c_char_p, vp]
+    lib.cf_checkpoint_set_host_blob.argtypes = [vp, vp, C.c_size_t]
+    lib.cf_checkpoint_capture.argtypes = [vp]
+    lib.cf_checkpoint_wait.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    lib.cf_checkpoint_restore.argtypes = [vp, vp, C.c_size_t]
+    lib.cf_checkpoint_verify.argtypes = [vp, C.c_size_t]
+    lib.cf_checkpoint_hash.argtypes = [vp, C.c_size_t, C.POINTER(C.c_uint64)]
+    lib.cf_checkpoint_host_blob.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("cf_last_error", "cf_device_alloc", "cf_window_host_buffer", "cf_build_stamp"):

@@ -590,6 +590,12 @@ class FluxContext:
                                                    int(edges.size)), "cf_attach_climatology")
         self._attached_climatology = clim   # kept alive while attached
 
+    # -- checkpoint and pickup --------------------------------------------------------------------
+    def checkpoint(self, direct=False, max_workgroups=0):
+        """A checkpoint handle (cf_checkpoint_create): register arrays and handles, capture() … wait() → image,
+        restore(image) in the next process.  `direct`: no device staging image."""
+        return Checkpoint(self, direct, max_workgroups)
+
     # -- sparse surface operators -----------------------------------------------------------------
     def regridder(self, row_ptr, col, weight, mask=None, mode="mean", max_workgroups=0):
         """A fixed sparse surface operator on the device (cf_regrid_create): CSR over destination rows — row_ptr (n_rows + 1),
@@ -657,7 +663,7 @@ BUDGET_KINDS = dict(heat_shortwave=abi.BUDGET_HEAT_SHORTWAVE, heat_longwave_up=a
 
 
 class _ChildHandle:
-    """What TimeAverager, Climatology, SurfaceIntegrator, SurfaceMonitor, SurfaceRegridder and SnapshotWindow share: a handle `_h` made on the context
+    """What TimeAverager, Climatology, SurfaceIntegrator, SurfaceMonitor, SurfaceRegridder, Checkpoint and SnapshotWindow share: a handle `_h` made on the context
     `ctx` that may outlive it (the library then fails every call but the `_destroy` one with "… has been destroyed")."""
     _destroy = None   # name of the cf_*_destroy entry point
 
@@ -960,6 +966,105 @@ class Climatology(_ChildHandle):
             made.append(t)
         self._check(self.lib.cf_climatology_extremes(self._h, int(field), *[_ptr(t) for t in made]), "cf_climatology_extremes")
         return tuple(made)
+
+
+def _host_bytes(data):
+    """(keep-alive object, address, length) of a bytes-like object, without copying where it is writable or bytes."""
+    if isinstance(data, bytes):
+        return data, C.cast(C.c_char_p(data), C.c_void_p), len(data)
+    a = np.frombuffer(data, dtype=np.uint8)
+    if not a.flags.c_contiguous:
+        a = np.ascontiguousarray(a)
+    return a, C.c_void_p(a.ctypes.data), a.size
+
+
+def checkpoint_hash(data):
+    """The section hash of a checkpoint image over `data` (bytes-like): cf_checkpoint_hash, a pure host function —
+    Σ mix64(w_k XOR K·(k + 1)) mod 2⁶⁴ over the 8-byte little-endian words, the last one zero padded."""
+    lib = abi.load_library()
+    keep, p, n = _host_bytes(data)
+    out = C.c_uint64()
+    if lib.cf_checkpoint_hash(p, n, C.byref(out)) != 0:
+        raise ValueError(lib.cf_last_error(None).decode())
+    return out.value
+
+
+def checkpoint_verify(image):
+    """Checks a checkpoint image (bytes-like) without a device: cf_checkpoint_verify.  ValueError names the header field or
+    the section that is wrong."""
+    lib = abi.load_library()
+    keep, p, n = _host_bytes(image)
+    if lib.cf_checkpoint_verify(p, n) != 0:
+        raise ValueError(lib.cf_last_error(None).decode())
+
+
+def checkpoint_host_blob(image):
+    """The caller's blob inside a checkpoint image (cf_checkpoint_host_blob; the image is verified first)."""
+    lib = abi.load_library()
+    keep, p, n = _host_bytes(image)
+    blob, size = C.c_void_p(), C.c_size_t()
+    if lib.cf_checkpoint_host_blob(p, n, C.byref(blob), C.byref(size)) != 0:
+        raise ValueError(lib.cf_last_error(None).decode())
+    return C.string_at(blob.value, size.value) if size.value else b""
+
+
+class Checkpoint(_ChildHandle):
+    """cf_checkpoint_*: packs registered device arrays and the private state of TimeAveragers, Climatologies,
+    SurfaceIntegrators and SurfaceMonitors into one self-describing image (this library's own format, not JLD2) and puts such
+    an image back, bit for bit.  capture() is stream ordered and returns at once — one launch packs and hashes every section,
+    the image drains on the handle's own stream while later steps run; wait() returns the finished image; restore(image)
+    refuses whatever does not match the registration before it writes a byte.  `direct`: no device staging image (sections
+    are copied one by one on the context's stream).  The library borrows arrays and handles: they are kept alive here."""
+    _destroy = "cf_checkpoint_destroy"
+
+    def __init__(self, ctx, direct=False, max_workgroups=0):
+        self._adopt(ctx)
+        self.names, self._keep = [], []
+        flags = abi.CHECKPOINT_DIRECT if direct else 0
+        desc = abi.CheckpointDesc(C.sizeof(abi.CheckpointDesc), flags, int(max_workgroups), 0)
+        ctx._check(self.lib.cf_checkpoint_create(ctx._h, C.byref(desc), C.byref(self._h)), "cf_checkpoint_create")
+
+    def add_array(self, name, tensor):
+        """A contiguous device tensor of any dtype (a whole parent array, a [k] slab of one): all its bytes."""
+        if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.is_contiguous()):
+            raise ValueError(f"section {name!r}: a contiguous device tensor")
+        self._check(self.lib.cf_checkpoint_add_array(self._h, name.encode(), C.c_void_p(tensor.data_ptr()), tensor.numel() * tensor.element_size()),
+                    "cf_checkpoint_add_array")
+        self.names.append(name)
+        self._keep.append(tensor)
+
+    def add(self, name, handle):
+        """The library-private state of a TimeAverager, Climatology, SurfaceIntegrator or SurfaceMonitor of the same context
+        (its weights, counts, times, records, status); the arrays it writes into are registered with add_array."""
+        for cls, kind in ((TimeAverager, "average"), (Climatology, "climatology"), (SurfaceIntegrator, "integrals"), (SurfaceMonitor, "monitor")):
+            if isinstance(handle, cls):
+                what = "cf_checkpoint_add_" + kind
+                self._check(getattr(self.lib, what)(self._h, name.encode(), handle._h), what)
+                self.names.append(name)
+                self._keep.append(handle)
+                return
+        raise ValueError(f"section {name!r}: {type(handle).__name__} has no state a checkpoint keeps")
+
+    def set_host_blob(self, data):
+        keep, p, n = _host_bytes(data)
+        self._check(self.lib.cf_checkpoint_set_host_blob(self._h, p, n), "cf_checkpoint_set_host_blob")
+
+    def capture(self):
+        self._check(self.lib.cf_checkpoint_capture(self._h), "cf_checkpoint_capture")
+
+    def wait(self, copy=True):
+        """Waits for the drain of the last capture (and for the check of the last restore) and returns the image: bytes, or
+        with copy=False a memoryview of the library's pinned buffer, valid until the next capture, restore or close.  None when
+        nothing was captured."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self.lib.cf_checkpoint_wait(self._h, C.byref(p), C.byref(n)), "cf_checkpoint_wait")
+        if not p.value:
+            return None
+        return C.string_at(p.value, n.value) if copy else memoryview((C.c_ubyte * n.value).from_address(p.value)).cast("B")
+
+    def restore(self, image):
+        keep, p, n = _host_bytes(image)
+        self._check(self.lib.cf_checkpoint_restore(self._h, p, n), "cf_checkpoint_restore")
 
 
 REGRID_MODES = dict(mean=abi.REGRID_MEAN, sum=abi.REGRID_SUM)

@@ -632,6 +632,7 @@ int cf_sync(cf_ctx* ctx) {
                         st == 1 ? "south" : "north");
         }
     }
+    if (!ctx->checkpoints.empty()) CHECK(checkpoint_settle_restores(ctx));
     return CF_OK;
 }
 

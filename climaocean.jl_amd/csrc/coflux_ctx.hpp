@@ -224,6 +224,8 @@ struct cf_ctx {
     int prof_capacity = 0, prof_count = 0;
     // every averager, integrator, monitor, regridder and window made on this context (cf_destroy orphans them)
     std::vector<cf_child*> children;
+    // the checkpoint handles among them: cf_sync reports a restore whose device-side hashes do not match (coflux_checkpoint.cpp)
+    std::vector<struct cf_checkpoint*> checkpoints;
     // time averages (coflux_average.cpp): the ones the step loops collect, in slot order (cf_attach_average_slot; slot 0 is
     // cf_attach_average's)
     struct AverageSlot {
@@ -310,6 +312,8 @@ int average_collect(cf_average* a, double weight);
 // entry); the bin of `time` in a calendar table that cf_attach_climatology has validated (false: outside the table)
 int climatology_collect(cf_climatology* c, int32_t bin, double weight);
 bool calendar_lookup(const std::vector<double>& edges, const std::vector<int32_t>& bin_of_interval, double time, int32_t* bin);
+// coflux_checkpoint.cpp: waits for the restores of ctx's checkpoint handles that are still unchecked and compares their hashes
+int checkpoint_settle_restores(cf_ctx* ctx);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state); *route is the counter of
 // ctx->prefetch_stats that names the launch it left in
 extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx, uint64_t* route);
@@ -355,6 +359,7 @@ inline void child_leave(cf_child* child) {
 inline void orphan_children(cf_ctx* ctx) {
     for (cf_child* child : ctx->children) child->ctx = nullptr;
     ctx->children.clear();
+    ctx->checkpoints.clear();
     for (auto& slot : ctx->averages) slot.handle = nullptr;
     ctx->integrals.detach();
     ctx->monitor.detach();

@@ -788,4 +788,64 @@ time_steps_coupled!(b, first_step, nsteps, sched::CfRunSchedule, src, w, fluxes,
                         Ptr{CfSeaIceFields}, Ref{CfNetOceanFluxes}, Ref{CfCoupledStep}),
                        b.ctx, first_step, nsteps, sched, src, w, fluxes, ice, net, coupled))
 
+# ---- checkpoint and pickup (run!(sim; pickup = true), omip_simulation.jl:241-247; Checkpointer, omip_diagnostics.jl:220-225) ----
+# A checkpoint packs registered device arrays (whole parent arrays) and the private state of averagers, climatologies,
+# integrators and monitors into one byte string — this library's own format, not JLD2 — and puts it back bit for bit:
+#   cp = CoFluxCheckpoint(b); add!(cp, "T", pointer(T), sizeof(T)); add!(cp, "averages", avg); set_host_blob!(cp, codeunits(json))
+#   capture!(cp); …further steps…; write(io, wait_image(cp))          # the image drains while the steps run
+#   restore!(cp, read(path)); sync(b)                                 # in the next process, after the same registration
+const CF_CHECKPOINT_MAX_SECTIONS, CF_CHECKPOINT_DIRECT = 256, 1
+struct CfCheckpointDesc
+    struct_size::Int32; flags::Int32; max_workgroups::Int32; reserved::Int32
+end
+mutable struct CoFluxCheckpoint
+    ptr::Ptr{Cvoid}
+    backend::CoFluxBackend
+    kept::Vector{Any}   # the registered handles and the blob stay alive with the checkpoint
+end
+function CoFluxCheckpoint(b::CoFluxBackend; direct = false, max_workgroups = 0)
+    desc = CfCheckpointDesc(sizeof(CfCheckpointDesc), direct ? CF_CHECKPOINT_DIRECT : 0, max_workgroups, 0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(b.ctx, ccall((:cf_checkpoint_create, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfCheckpointDesc}, Ref{Ptr{Cvoid}}), b.ctx, desc, out))
+    cp = CoFluxCheckpoint(out[], b, Any[])
+    finalizer(x -> ccall((:cf_checkpoint_destroy, libcoflux), Cint, (Ptr{Cvoid},), x.ptr), cp)
+    return cp
+end
+add!(cp::CoFluxCheckpoint, name::String, d_ptr::Ptr, bytes::Integer) =
+    check(C_NULL, ccall((:cf_checkpoint_add_array, libcoflux), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cvoid}, Csize_t), cp.ptr, name, d_ptr, bytes))
+function add!(cp::CoFluxCheckpoint, name::String, a::CoFluxAverage)
+    check(C_NULL, ccall((:cf_checkpoint_add_average, libcoflux), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cvoid}), cp.ptr, name, a.ptr)); push!(cp.kept, a); nothing
+end
+function add!(cp::CoFluxCheckpoint, name::String, c::CoFluxClimatology)
+    check(C_NULL, ccall((:cf_checkpoint_add_climatology, libcoflux), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cvoid}), cp.ptr, name, c.ptr)); push!(cp.kept, c); nothing
+end
+function add!(cp::CoFluxCheckpoint, name::String, q::CoFluxIntegrals)
+    check(C_NULL, ccall((:cf_checkpoint_add_integrals, libcoflux), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cvoid}), cp.ptr, name, q.ptr)); push!(cp.kept, q); nothing
+end
+function add!(cp::CoFluxCheckpoint, name::String, m::CoFluxMonitor)
+    check(C_NULL, ccall((:cf_checkpoint_add_monitor, libcoflux), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cvoid}), cp.ptr, name, m.ptr)); push!(cp.kept, m); nothing
+end
+set_host_blob!(cp::CoFluxCheckpoint, blob::AbstractVector{UInt8}) =
+    check(C_NULL, ccall((:cf_checkpoint_set_host_blob, libcoflux), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Csize_t), cp.ptr, blob, length(blob)))
+capture!(cp::CoFluxCheckpoint) = check(C_NULL, ccall((:cf_checkpoint_capture, libcoflux), Cint, (Ptr{Cvoid},), cp.ptr))
+# the finished image (a copy: the library's pinned buffer is reused by the next capture)
+function wait_image(cp::CoFluxCheckpoint)
+    p = Ref{Ptr{Cvoid}}(C_NULL); n = Ref{Csize_t}(0)
+    check(C_NULL, ccall((:cf_checkpoint_wait, libcoflux), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Csize_t}), cp.ptr, p, n))
+    return copy(unsafe_wrap(Array, Ptr{UInt8}(p[]), Int(n[])))
+end
+restore!(cp::CoFluxCheckpoint, image::Vector{UInt8}) =
+    check(C_NULL, ccall((:cf_checkpoint_restore, libcoflux), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Csize_t), cp.ptr, image, length(image)))
+checkpoint_verify(image::Vector{UInt8}) = check(C_NULL, ccall((:cf_checkpoint_verify, libcoflux), Cint, (Ptr{UInt8}, Csize_t), image, length(image)))
+function checkpoint_hash(bytes::Vector{UInt8})
+    h = Ref{UInt64}(0)
+    check(C_NULL, ccall((:cf_checkpoint_hash, libcoflux), Cint, (Ptr{UInt8}, Csize_t, Ref{UInt64}), bytes, length(bytes), h))
+    return h[]
+end
+function checkpoint_host_blob(image::Vector{UInt8})
+    p = Ref{Ptr{Cvoid}}(C_NULL); n = Ref{Csize_t}(0)
+    check(C_NULL, ccall((:cf_checkpoint_host_blob, libcoflux), Cint, (Ptr{UInt8}, Csize_t, Ref{Ptr{Cvoid}}, Ref{Csize_t}), image, length(image), p, n))
+    return image[(Int(p[] - pointer(image)) + 1):(Int(p[] - pointer(image)) + Int(n[]))]
+end
+
 end # module

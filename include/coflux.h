@@ -1669,6 +1669,91 @@ typedef struct cf_prefetch_stats {
 } cf_prefetch_stats;
 int cf_debug_prefetch_stats(cf_ctx* ctx, cf_prefetch_stats* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Checkpoint and pickup: every production launch of the reference ends in run!(sim; pickup = true) (experiments/
+ * OMIPSimulations/scripts/launch.sh:154-173, omip_simulation.jl:241-247) and add_omip_diagnostics! always installs a
+ * Checkpointer (omip_diagnostics.jl:220-225).  A checkpoint handle packs device arrays of the caller and the library-private
+ * state of averagers, climatologies, integrators and monitors into one self-describing byte string, and puts such an image
+ * back.  A run split in two PROCESSES by capture → restore yields, bit for bit, what the unsplit run yields.  The format is
+ * this library's own (not JLD2).  Still ABI 5: additive.
+ *   Registration.  Sections are named (1 … 47 bytes, unique per handle); their order is the caller's and part of the image; at
+ *     most CF_CHECKPOINT_MAX_SECTIONS.  cf_checkpoint_add_array: a caller-owned device array, `bytes` long (any length, 0
+ *     included), base 8-byte aligned, borrowed — whole parent arrays, halos included; an array that shares a byte with an
+ *     earlier array section is CF_ERR_INVALID.  cf_checkpoint_add_average / _climatology / _integrals / _monitor: a handle of
+ *     the same context (borrowed: it outlives the checkpoint handle), each at most once; what goes into the image is
+ *       average      total (f64), samples (i64)
+ *       climatology  weight, samples, bin_weight[n_bins] (f64), bin_samples[n_bins] (i64)
+ *       integrals    records [count][n_entries] f64 from the device, zero padded to 16 bytes, then times[count]
+ *       monitor      the 16-byte status and the records [count][n_entries] × 64 bytes from the device, then times[count]
+ *     The arrays those handles write into (means, totals, bin blocks) are the caller's: register them as arrays.
+ *     cf_checkpoint_set_host_blob: opaque caller bytes carried in the image (copied at the call; clocks, schedules).
+ *   Image, little endian.  Header, 96 bytes: magic "CFLXCKPT" | u32 version (1) | u32 n_sections | u64 total_bytes | i32 nx, ny,
+ *     hx, hy | u64 directory_hash (the section hash of the directory's bytes) | u64 blob_bytes | u64 blob_offset | u64
+ *     blob_hash | 16 reserved zero bytes | u64 header_hash (of the 88 bytes before it).  Directory: one 96-byte entry per
+ *     section: name[48] NUL padded | u32 kind (0 array, 1 average, 2 climatology, 3 integrals, 4 monitor) | u32 n_entries
+ *     (climatology: n_bins; arrays, averages: 0) | u64 payload bytes | u64 payload offset | u64 hash | i64 count (records of a
+ *     series, else 0) | 8 reserved zero bytes.  Then the payloads in directory order, each at the next multiple of 16 and
+ *     zero padded to one, then the host blob likewise; total_bytes ends there.  An image has exactly one encoding.
+ *   Section hash.  hash = Σ_k mix64(w_k XOR (K·(k + 1) mod 2⁶⁴)) mod 2⁶⁴ over the payload's 8-byte little-endian words w_k, the
+ *     last one zero padded; K and mix64 are the surface monitor's (above).  Known answers: the doubles [0.0, −0.0, 1.0, NaN
+ *     0x7FF8000000000000, +Inf, −1.5] hash to 0xbc9733db8e1747df (the monitor's), [0.0] to 0xe220a8397b1dcdaf, no bytes to 0,
+ *     the bytes 01 02 … 0b to 0x21e51a3dd06edc89, the byte 01 to 0xe4d971771b652c20.  cf_checkpoint_hash is that function on
+ *     the host.
+ *   cf_checkpoint_capture  stream ordered on the context's stream, no host synchronisation.  The host-kept state (weights,
+ *     counts, times, the blob) is copied at the call; ONE launch packs every device byte into a device staging image and forms
+ *     every section's hash (wrapping 64-bit sums: lane → wave → one integer atomic per section and workgroup; the bits depend
+ *     on the bytes alone, never on max_workgroups, the tile size, the CU count or the form); the image then drains to a pinned
+ *     host buffer on a stream the handle owns, behind an event: steps issued after the call run meanwhile and cannot change
+ *     the image.  Staging and pinned buffers are sized by the first capture — with every registered series at its
+ *     capacity, so that a filling series never makes a later capture allocate — and reused.  With CF_CHECKPOINT_DIRECT there is
+ *     no staging image (no extra device memory): the same kernel forms the hashes only and the sections are copied to the
+ *     pinned image one by one on the CONTEXT's stream, which holds later steps back for as long.  Both forms give the same
+ *     bytes.  A second capture before cf_checkpoint_wait is CF_ERR_INVALID.
+ *   cf_checkpoint_wait     synchronises the drain only, completes the image (header, directory, host-kept bytes) and hands
+ *     out the pinned image: valid until the next capture, restore or destroy.  Either output may be NULL.
+ *   cf_checkpoint_verify   a pure host function (no context, no device): the magic, the version, the total length, the header's,
+ *     the directory's, every section's and the blob's hash, every name (terminated, unique), kind, n_entries / count / payload
+ *     size combination, every offset and length against the image size without overflow, and that all padding is zero.
+ *     CF_ERR_INVALID with a message that names the header field or the section.  cf_checkpoint_host_blob verifies likewise and
+ *     points at the blob inside the image.
+ *   cf_checkpoint_restore  refuses — CF_ERR_INVALID, the message names the section, nothing written or launched — an image
+ *     that fails the verification, another grid (nx, ny, hx, hy), a directory that differs from the registration in number,
+ *     name, kind or order, an array of another length, a climatology with other n_bins, a series with other n_entries or more
+ *     records than the handle's capacity, and a capture in flight.  Otherwise: one host-to-device copy and ONE unpack launch on
+ *     the context's stream (with CF_CHECKPOINT_DIRECT: one copy per section and the hash-only launch), no host synchronisation;
+ *     the handles' weights, counts and times are set at once.  The launch hashes what it wrote; a mismatch with the image is
+ *     reported — CF_ERR_HIP, naming the section — by the next cf_checkpoint_wait or cf_sync.
+ *   What is not in an image: records the caller has read and reset away, the atmosphere window and whatever was requested
+ *     ahead (cf_discard_prefetched_atmosphere_state after a pickup), trip hints and chunk tables — rebuilt, never a bit.
+ *   max_workgroups caps the launch (scheduling only: never a bit).
+ * Slabs: each context writes its own image; section hashes of slabs add mod 2⁶⁴ as the monitor's do.
+ * ---------------------------------------------------------------------------------------- */
+#define CF_CHECKPOINT_MAX_SECTIONS 256
+#define CF_CHECKPOINT_DIRECT 1
+typedef struct cf_checkpoint_desc {
+    int32_t struct_size;     /* sizeof(cf_checkpoint_desc) */
+    int32_t flags;           /* 0 or CF_CHECKPOINT_DIRECT */
+    int32_t max_workgroups;  /* 0: the library's choice; > 0 caps the launch */
+    int32_t reserved;
+} cf_checkpoint_desc;
+typedef struct cf_checkpoint cf_checkpoint;
+int cf_checkpoint_create(cf_ctx* ctx, const cf_checkpoint_desc* desc, cf_checkpoint** out);
+int cf_checkpoint_destroy(cf_checkpoint* cp);
+int cf_checkpoint_add_array(cf_checkpoint* cp, const char* name, void* d_ptr, size_t bytes);
+int cf_checkpoint_add_average(cf_checkpoint* cp, const char* name, cf_average* a);
+int cf_checkpoint_add_climatology(cf_checkpoint* cp, const char* name, cf_climatology* c);
+int cf_checkpoint_add_integrals(cf_checkpoint* cp, const char* name, cf_integrals* q);
+int cf_checkpoint_add_monitor(cf_checkpoint* cp, const char* name, cf_monitor* m);
+int cf_checkpoint_set_host_blob(cf_checkpoint* cp, const void* h_blob, size_t bytes);
+/* Footprint: reads exactly the registered bytes; writes no caller array.                                               */
+int cf_checkpoint_capture(cf_checkpoint* cp);
+int cf_checkpoint_wait(cf_checkpoint* cp, const void** h_image, size_t* bytes);
+/* Footprint: writes exactly the registered bytes (of a series: the image's records), nothing beside them.              */
+int cf_checkpoint_restore(cf_checkpoint* cp, const void* h_image, size_t bytes);
+int cf_checkpoint_verify(const void* h_image, size_t bytes);
+int cf_checkpoint_hash(const void* h_bytes, size_t n, uint64_t* out);
+int cf_checkpoint_host_blob(const void* h_image, size_t bytes, const void** h_blob, size_t* blob_bytes);
+
 #ifdef __cplusplus
 }
 #endif
