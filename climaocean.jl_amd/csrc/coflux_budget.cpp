@@ -1,7 +1,7 @@
 // coflux_budget.cpp — cf_average_create_budget (include/coflux.h): checks a table of budget kinds, turns the kinds' "reads"
-// column into the load mask of the kernel (a NULL input pointer: not read) and hands back an ordinary cf_average whose
-// collections go to the kernel of coflux_budget.hip (average_collect, coflux_average.cpp, chooses the launch).  Nothing is
-// allocated on the device.
+// column into the load mask of the kernel (a NULL input pointer: not read) and hands back a cf_average whose collections
+// go to the kernel of coflux_budget.hip (cf_average::collect, coflux_average.cpp, chooses the launch).  Nothing is allocated
+// on the device.
 #include "coflux_ctx.hpp"
 
 namespace {
@@ -110,9 +110,7 @@ extern "C" int cf_average_create_budget(cf_ctx* ctx, const cf_budget_desc* desc,
                 return fail(ctx, CF_ERR_INVALID, "cf_average_create_budget: means %d and %d overlap", u, t);
     }
     cf_average* a = new cf_average();
-    a->nfields = n;
-    a->budget = true;
-    a->budget_terms = A;
+    a->args = A;
     child_adopt(ctx, a);
     *out = a;
     return CF_OK;

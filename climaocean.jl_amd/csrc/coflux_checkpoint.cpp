@@ -4,9 +4,8 @@
 // staging image, the pinned host image and the kernel's tables.  A capture lays the image out from the handles' state at the
 // call (the plan), copies what the host keeps, issues one launch for every device byte and drains behind an event;
 // cf_checkpoint_wait writes the header, the directory and the host-kept bytes into the drained image.  A restore refuses
-// before it touches anything, then runs the plan backwards.
-#include "coflux_checkpoint.hpp"
-#include "coflux_checkpoint_image.hpp"
+// before it touches anything, then runs the plan backwards.  What a handle's section holds is the handle's to say (cf_child,
+// coflux_ctx.hpp): this file lays out arrays and walks the registration.
 #include "coflux_series.hpp"
 
 struct cf_checkpoint : cf_child {
@@ -15,12 +14,9 @@ struct cf_checkpoint : cf_child {
     struct Section {
         std::string name;
         uint32_t kind = cfck::KIND_ARRAY;
-        unsigned char* ptr = nullptr;   // arrays
+        unsigned char* ptr = nullptr;   // an array's bytes …
         size_t bytes = 0;
-        cf_average* average = nullptr;
-        cf_climatology* climatology = nullptr;
-        cf_integrals* integrals = nullptr;
-        cf_monitor* monitor = nullptr;
+        cf_child* child = nullptr;      // … or the handle whose private state goes along
     };
     std::vector<Section> sections;
     std::vector<unsigned char> blob;
@@ -60,11 +56,6 @@ static_assert(CF_CHECKPOINT_MAX_SECTIONS == cfck::MAX_SECTIONS && CF_MONITOR_MAX
 constexpr bool STREAMING_STORES_DEFAULT = true;
 constexpr unsigned char SENTINEL = 0xA5;   // fresh staging and pinned buffers are filled with it: a byte nobody wrote shows
 
-const char* kind_name(uint32_t kind) {
-    static const char* names[] = {"array", "average", "climatology", "integrals", "monitor"};
-    return kind < cfck::KINDS ? names[kind] : "unknown";
-}
-
 int check_name(cf_checkpoint* cp, const char* fn, const char* name) {
     cf_ctx* ctx = cp->ctx;
     if (!name || !name[0]) return fail(ctx, CF_ERR_INVALID, "%s: the name is NULL or empty", fn);
@@ -76,32 +67,18 @@ int check_name(cf_checkpoint* cp, const char* fn, const char* name) {
     return CF_OK;
 }
 
-template <class Handle>
-int add_handle(cf_checkpoint* cp, const char* fn, const char* name, Handle* h, uint32_t kind, Handle* cf_checkpoint::Section::*member) {
+int add_handle(cf_checkpoint* cp, const char* fn, const char* name, cf_child* h, uint32_t kind) {
     CHECK(live(cp, fn, "checkpoint"));
     CHECK(check_name(cp, fn, name));
-    if (!h || h->ctx != cp->ctx) return fail(cp->ctx, CF_ERR_INVALID, "%s: section \"%s\": the %s is NULL or belongs to another context", fn, name, kind_name(kind));
+    if (!h || h->ctx != cp->ctx) return fail(cp->ctx, CF_ERR_INVALID, "%s: section \"%s\": the %s is NULL or belongs to another context", fn, name, cfck::kind_name(kind));
     for (const auto& s : cp->sections)
-        if (s.*member == h) return fail(cp->ctx, CF_ERR_INVALID, "%s: section \"%s\": this %s is registered already as \"%s\"", fn, name, kind_name(kind), s.name.c_str());
+        if (s.child == h) return fail(cp->ctx, CF_ERR_INVALID, "%s: section \"%s\": this %s is registered already as \"%s\"", fn, name, cfck::kind_name(kind), s.name.c_str());
     cf_checkpoint::Section s;
     s.name = name;
-    s.kind = kind;
-    s.*member = h;
+    s.kind = h->section_kind();
+    s.child = h;
     cp->sections.push_back(std::move(s));
     return CF_OK;
-}
-
-// records and times of a series section with `count` records
-template <class Series>
-void plan_series(cf_checkpoint::Plan& P, const Series* s, uint32_t section, uint64_t offset, int64_t count, unsigned char* status) {
-    uint64_t at = offset, word = 0;
-    if (status) {
-        P.segments.push_back(CheckpointSegment{status, at, cfck::MONITOR_STATUS_BYTES, word, section, 0});
-        at += cfck::MONITOR_STATUS_BYTES;
-        word += cfck::MONITOR_STATUS_BYTES / 8;
-    }
-    const uint64_t records = (uint64_t)count * (uint64_t)s->n_entries * sizeof(*s->d_series.get());
-    if (records) P.segments.push_back(CheckpointSegment{reinterpret_cast<unsigned char*>(s->d_series.get()), at, records, word, section, 0});
 }
 
 // Lays the image out.  `counts`: per section the records of a series (NULL: what the handles hold now).  With `image` the
@@ -120,56 +97,14 @@ void make_plan(cf_checkpoint* cp, const int64_t* counts, const unsigned char* im
         std::snprintf(E.name, sizeof E.name, "%s", S.name.c_str());
         E.kind = S.kind;
         E.offset = cursor;
-        std::vector<unsigned char>& tail = P.tail[k];
-        auto put_f64 = [&tail](double v) {
-            uint64_t bits;
-            std::memcpy(&bits, &v, 8);
-            tail.resize(tail.size() + 8);
-            cfck::put64(tail.data() + tail.size() - 8, bits);
-        };
-        auto put_i64 = [&tail](int64_t v) {
-            tail.resize(tail.size() + 8);
-            cfck::put64(tail.data() + tail.size() - 8, (uint64_t)v);
-        };
-        switch (S.kind) {
-            case cfck::KIND_ARRAY:
-                E.bytes = S.bytes;
-                P.device_bytes[k] = S.bytes;
-                if (S.bytes) P.segments.push_back(CheckpointSegment{S.ptr, cursor, S.bytes, 0, (uint32_t)k, 0});
-                break;
-            case cfck::KIND_AVERAGE:
-                E.bytes = 16;
-                put_f64(S.average->total);
-                put_i64(S.average->samples);
-                break;
-            case cfck::KIND_CLIMATOLOGY: {
-                const cf_climatology* c = S.climatology;
-                E.n_entries = (uint32_t)c->n_bins;
-                E.bytes = 16 + 16 * (uint64_t)c->n_bins;
-                put_f64(c->weight);
-                put_i64(c->samples);
-                for (int b = 0; b < c->n_bins; ++b) put_f64(c->bin_weight[b]);
-                for (int b = 0; b < c->n_bins; ++b) put_i64(c->bin_samples[b]);
-                break;
-            }
-            default: {   // the two series
-                const bool is_monitor = S.kind == cfck::KIND_MONITOR;
-                const int64_t count = counts ? counts[k] : (is_monitor ? S.monitor->count : S.integrals->count);
-                E.n_entries = (uint32_t)(is_monitor ? S.monitor->n_entries : S.integrals->n_entries);
-                E.count = count;
-                const uint64_t dev = cfck::series_device_bytes(S.kind, E.n_entries, count);
-                P.device_bytes[k] = dev;
-                E.bytes = cfck::round_up(dev) + 8 * (uint64_t)count;
-                if (is_monitor) plan_series(P, S.monitor, (uint32_t)k, cursor, count, reinterpret_cast<unsigned char*>(S.monitor->args.status));
-                else plan_series(P, S.integrals, (uint32_t)k, cursor, count, nullptr);
-                tail.assign((size_t)(cfck::round_up(dev) - dev), 0);
-                const std::vector<double>& times = is_monitor ? S.monitor->times : S.integrals->times;
-                if (!image)
-                    for (int64_t r = 0; r < count; ++r) put_f64(times[(size_t)r]);
-                break;
-            }
+        if (S.child) {
+            S.child->plan_section(SectionPlan{(uint32_t)k, cursor, E, P.device_bytes[k], P.tail[k], P.segments}, counts ? &counts[k] : nullptr);
+        } else {
+            E.bytes = S.bytes;
+            P.device_bytes[k] = S.bytes;
+            if (S.bytes) P.segments.push_back(CheckpointSegment{S.ptr, cursor, S.bytes, 0, (uint32_t)k, 0});
         }
-        if (image) tail.assign(image + cursor + P.device_bytes[k], image + cursor + E.bytes);
+        if (image) P.tail[k].assign(image + cursor + P.device_bytes[k], image + cursor + E.bytes);
         cursor += cfck::round_up(E.bytes);
     }
     P.sections_end = P.blob_offset = cursor;
@@ -188,11 +123,8 @@ uint64_t image_room(const cf_checkpoint* cp) {
     const cf_checkpoint::Plan& P = cp->plan;
     uint64_t room = P.total + 4096;
     for (size_t k = 0; k < cp->sections.size(); ++k) {
-        const cf_checkpoint::Section& S = cp->sections[k];
-        if (S.kind != cfck::KIND_INTEGRALS && S.kind != cfck::KIND_MONITOR) continue;
-        const int64_t capacity = S.kind == cfck::KIND_MONITOR ? S.monitor->capacity : S.integrals->capacity;
-        const uint64_t full = cfck::round_up(cfck::round_up(cfck::series_device_bytes(S.kind, P.entries[k].n_entries, capacity)) + 8 * (uint64_t)capacity);
-        const uint64_t now = cfck::round_up(P.entries[k].bytes);
+        if (!cp->sections[k].child) continue;
+        const uint64_t full = cfck::round_up(cp->sections[k].child->section_room()), now = cfck::round_up(P.entries[k].bytes);
         if (full > now) room += full - now;
     }
     return room;
@@ -344,16 +276,16 @@ int cf_checkpoint_add_array(cf_checkpoint* cp, const char* name, void* d_ptr, si
 }
 
 int cf_checkpoint_add_average(cf_checkpoint* cp, const char* name, cf_average* a) {
-    return add_handle(cp, "cf_checkpoint_add_average", name, a, cfck::KIND_AVERAGE, &cf_checkpoint::Section::average);
+    return add_handle(cp, "cf_checkpoint_add_average", name, a, cfck::KIND_AVERAGE);
 }
 int cf_checkpoint_add_climatology(cf_checkpoint* cp, const char* name, cf_climatology* c) {
-    return add_handle(cp, "cf_checkpoint_add_climatology", name, c, cfck::KIND_CLIMATOLOGY, &cf_checkpoint::Section::climatology);
+    return add_handle(cp, "cf_checkpoint_add_climatology", name, c, cfck::KIND_CLIMATOLOGY);
 }
 int cf_checkpoint_add_integrals(cf_checkpoint* cp, const char* name, cf_integrals* q) {
-    return add_handle(cp, "cf_checkpoint_add_integrals", name, q, cfck::KIND_INTEGRALS, &cf_checkpoint::Section::integrals);
+    return add_handle(cp, "cf_checkpoint_add_integrals", name, q, cfck::KIND_INTEGRALS);
 }
 int cf_checkpoint_add_monitor(cf_checkpoint* cp, const char* name, cf_monitor* m) {
-    return add_handle(cp, "cf_checkpoint_add_monitor", name, m, cfck::KIND_MONITOR, &cf_checkpoint::Section::monitor);
+    return add_handle(cp, "cf_checkpoint_add_monitor", name, m, cfck::KIND_MONITOR);
 }
 
 int cf_checkpoint_set_host_blob(cf_checkpoint* cp, const void* h_blob, size_t bytes) {
@@ -502,28 +434,11 @@ int cf_checkpoint_restore(cf_checkpoint* cp, const void* h_image, size_t bytes) 
         cfck::read_entry(image + cfck::HEADER_BYTES + cfck::ENTRY_BYTES * k, &E);
         if (S.name != E.name) return fail(ctx, CF_ERR_INVALID, "%s: section %zu is \"%s\" in the image and \"%s\" in the registration", fn, k, E.name, S.name.c_str());
         if (S.kind != E.kind)
-            return fail(ctx, CF_ERR_INVALID, "%s: section \"%s\" is of kind %s in the image and %s in the registration", fn, E.name, kind_name(E.kind), kind_name(S.kind));
+            return fail(ctx, CF_ERR_INVALID, "%s: section \"%s\" is of kind %s in the image and %s in the registration", fn, E.name, cfck::kind_name(E.kind), cfck::kind_name(S.kind));
         counts[k] = E.count;
-        switch (S.kind) {
-            case cfck::KIND_ARRAY:
-                if (E.bytes != S.bytes) return fail(ctx, CF_ERR_INVALID, "%s: section \"%s\" has %llu bytes in the image and %zu in the registration", fn, E.name, (unsigned long long)E.bytes, S.bytes);
-                break;
-            case cfck::KIND_AVERAGE:
-                break;
-            case cfck::KIND_CLIMATOLOGY:
-                if ((int)E.n_entries != S.climatology->n_bins)
-                    return fail(ctx, CF_ERR_INVALID, "%s: section \"%s\" has %u bins in the image, the climatology has %d", fn, E.name, E.n_entries, S.climatology->n_bins);
-                break;
-            default: {
-                const bool is_monitor = S.kind == cfck::KIND_MONITOR;
-                const int entries = is_monitor ? S.monitor->n_entries : S.integrals->n_entries;
-                const int64_t capacity = is_monitor ? S.monitor->capacity : S.integrals->capacity;
-                if ((int)E.n_entries != entries) return fail(ctx, CF_ERR_INVALID, "%s: section \"%s\" has %u entries in the image, the %s has %d", fn, E.name, E.n_entries, kind_name(S.kind), entries);
-                if (E.count > capacity)
-                    return fail(ctx, CF_ERR_INVALID, "%s: section \"%s\" holds %lld records, the %s's series has room for %lld", fn, E.name, (long long)E.count, kind_name(S.kind), (long long)capacity);
-                break;
-            }
-        }
+        if (S.child) CHECK(S.child->check_entry(E, fn));
+        else if (E.bytes != S.bytes)
+            return fail(ctx, CF_ERR_INVALID, "%s: section \"%s\" has %llu bytes in the image and %zu in the registration", fn, E.name, (unsigned long long)E.bytes, S.bytes);
     }
     // nothing has been written or launched up to here
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -564,43 +479,8 @@ int cf_checkpoint_restore(cf_checkpoint* cp, const void* h_image, size_t bytes) 
     }
     cp->restoring = true;
     // the handles' host state, at once
-    auto f64_at = [](const unsigned char* p) {
-        const uint64_t bits = cfck::get64(p);
-        double v;
-        std::memcpy(&v, &bits, 8);
-        return v;
-    };
-    for (size_t k = 0; k < n; ++k) {
-        const cf_checkpoint::Section& S = cp->sections[k];
-        const unsigned char* t = P.tail[k].data();
-        switch (S.kind) {
-            case cfck::KIND_ARRAY:
-                break;
-            case cfck::KIND_AVERAGE:
-                S.average->total = f64_at(t);
-                S.average->samples = (int64_t)cfck::get64(t + 8);
-                break;
-            case cfck::KIND_CLIMATOLOGY: {
-                cf_climatology* c = S.climatology;
-                c->weight = f64_at(t);
-                c->samples = (int64_t)cfck::get64(t + 8);
-                for (int b = 0; b < c->n_bins; ++b) {
-                    c->bin_weight[b] = f64_at(t + 16 + 8 * (size_t)b);
-                    c->bin_samples[b] = (int64_t)cfck::get64(t + 16 + 8 * (size_t)(c->n_bins + b));
-                }
-                break;
-            }
-            default: {
-                const bool is_monitor = S.kind == cfck::KIND_MONITOR;
-                const int64_t count = counts[k];
-                std::vector<double>& times = is_monitor ? S.monitor->times : S.integrals->times;
-                const unsigned char* at = t + (P.tail[k].size() - 8 * (size_t)count);
-                for (int64_t r = 0; r < count; ++r) times[(size_t)r] = f64_at(at + 8 * (size_t)r);
-                (is_monitor ? S.monitor->count : S.integrals->count) = count;
-                break;
-            }
-        }
-    }
+    for (size_t k = 0; k < n; ++k)
+        if (cp->sections[k].child) cp->sections[k].child->load_tail(P.tail[k], counts[k]);
     return CF_OK;
 }
 

@@ -9,16 +9,6 @@
 
 namespace cfck {
 
-uint32_t get32(const unsigned char* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
-uint64_t get64(const unsigned char* p) { return (uint64_t)get32(p) | (uint64_t)get32(p + 4) << 32; }
-void put32(unsigned char* p, uint32_t v) {
-    for (int b = 0; b < 4; ++b) p[b] = (unsigned char)(v >> (8 * b));
-}
-void put64(unsigned char* p, uint64_t v) {
-    put32(p, (uint32_t)v);
-    put32(p + 4, (uint32_t)(v >> 32));
-}
-
 uint64_t hash_bytes(const void* data, size_t n, uint64_t first_word) {
     const unsigned char* p = static_cast<const unsigned char*>(data);
     uint64_t h = 0, k = first_word;

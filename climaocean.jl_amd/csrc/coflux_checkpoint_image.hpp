@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 namespace cfck {
 
@@ -12,6 +13,10 @@ constexpr uint32_t VERSION = 1;
 constexpr size_t HEADER_BYTES = 96, ENTRY_BYTES = 96, NAME_BYTES = 48, ALIGN = 16;
 constexpr uint32_t MAX_SECTIONS = 256;
 constexpr uint32_t KIND_ARRAY = 0, KIND_AVERAGE = 1, KIND_CLIMATOLOGY = 2, KIND_INTEGRALS = 3, KIND_MONITOR = 4, KINDS = 5;
+inline const char* kind_name(uint32_t kind) {
+    constexpr const char* names[KINDS] = {"array", "average", "climatology", "integrals", "monitor"};
+    return kind < KINDS ? names[kind] : "unknown";
+}
 constexpr size_t MONITOR_STATUS_BYTES = 16, MONITOR_RECORD_BYTES = 64;
 constexpr uint64_t MAX_COUNT = 1ull << 31, MAX_ENTRIES = 32;   // what a series can hold: keeps every size below 2⁴⁸
 
@@ -55,10 +60,27 @@ inline uint64_t series_device_bytes(uint32_t kind, uint32_t n_entries, int64_t c
                                 : 8 * (uint64_t)n_entries * (uint64_t)count;
 }
 
-uint32_t get32(const unsigned char* p);
-uint64_t get64(const unsigned char* p);
-void put32(unsigned char* p, uint32_t v);
-void put64(unsigned char* p, uint64_t v);
+// little endian; a double travels as its bits
+inline uint32_t get32(const unsigned char* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+inline uint64_t get64(const unsigned char* p) { return (uint64_t)get32(p) | (uint64_t)get32(p + 4) << 32; }
+inline void put32(unsigned char* p, uint32_t v) {
+    for (int b = 0; b < 4; ++b) p[b] = (unsigned char)(v >> (8 * b));
+}
+inline void put64(unsigned char* p, uint64_t v) {
+    put32(p, (uint32_t)v);
+    put32(p + 4, (uint32_t)(v >> 32));
+}
+inline double get_f64(const unsigned char* p) {
+    const uint64_t bits = get64(p);
+    double v;
+    std::memcpy(&v, &bits, 8);
+    return v;
+}
+inline void put_f64(unsigned char* p, double v) {
+    uint64_t bits;
+    std::memcpy(&bits, &v, 8);
+    put64(p, bits);
+}
 void write_entry(unsigned char* at, const Entry& e);
 void read_entry(const unsigned char* at, Entry* e);
 

@@ -1,22 +1,11 @@
 // coflux_climatology.cpp — calendar-binned means of surface fields accumulated on the device (include/coflux.h:
 // cf_climatology_*, cf_calendar_bin, cf_attach_climatology; the kernels are coflux_climatology.hip).  The host keeps the total
 // weight of every collection since the reset and of each bin, turns a collection of (bin, weight) into the two pairs of
-// running-mean coefficients exactly as average_collect does for one, and looks a step's time up in the calendar table; the
-// device does one launch per collection.  The handle owns no device resource: every array is the caller's.
+// running-mean coefficients by the averagers' rule (RunningWeight, coflux_collect.hpp), and looks a step's time up in the
+// calendar table; the device does one launch per collection.  The handle owns no device resource: every array is the caller's.
 #include "coflux_ctx.hpp"
 
 namespace {
-
-// the running-mean coefficients of a destination that has received `before` and now receives `weight` (store: its first sample)
-struct Blend {
-    bool store;
-    double c_prev, c_new;
-};
-Blend blend_of(double before, int64_t samples, double weight) {
-    const double total = before + weight;
-    const bool store = samples == 0;
-    return Blend{store, store ? 0.0 : before / total, store ? 1.0 : weight / total};
-}
 
 // CF_ERR_INVALID unless (edges, bin_of_interval, n_edges) is a calendar table; `fn` names the entry point
 int check_calendar(cf_ctx* ctx, const char* fn, const double* edges, const int32_t* bin_of_interval, int32_t n_edges) {
@@ -45,29 +34,46 @@ bool lookup(const double* edges, const int32_t* bin_of_interval, size_t n, doubl
 
 }  // namespace
 
-bool calendar_lookup(const std::vector<double>& edges, const std::vector<int32_t>& bin_of_interval, double time, int32_t* bin) {
-    return edges.size() >= 2 && lookup(edges.data(), bin_of_interval.data(), edges.size(), time, bin);
-}
-
-int climatology_collect(cf_climatology* c, int32_t bin, double weight) {
-    cf_ctx* ctx = c->ctx;
+int cf_climatology::collect(int32_t bin, double w) {
     const GridDesc& G = ctx->grid;
-    const Blend T = blend_of(c->weight, c->samples, weight), B = blend_of(c->bin_weight[bin], c->bin_samples[bin], weight);
+    const RunningWeight::Blend T = weight.next(w), B = bin_weight[bin].next(w);
     const size_t parent = (size_t)G.sj * (size_t)(G.ny + 2 * G.hy);
     ClimatologyFields F{};
-    for (int f = 0; f < c->n_fields; ++f) {
-        F.src[f] = c->src[f];
-        F.total[f] = c->total[f];
-        F.bin[f] = c->bins[f] + parent * (size_t)bin;
+    for (int f = 0; f < n_fields; ++f) {
+        F.src[f] = src[f];
+        F.total[f] = total[f];
+        F.bin[f] = bins[f] + parent * (size_t)bin;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_climatology(ctx->stream, F, c->n_fields, G, T.store, B.store, ClimatologyBlend{T.c_prev, T.c_new, B.c_prev, B.c_new},
-                                    c->max_blocks));
-    c->weight += weight;
-    ++c->samples;
-    c->bin_weight[bin] += weight;
-    ++c->bin_samples[bin];
+    HIP_TRY(ctx, launch_climatology(ctx->stream, F, n_fields, G, T.store, B.store, ClimatologyBlend{T.c_prev, T.c_new, B.c_prev, B.c_new},
+                                    max_blocks));
+    weight.add(w);
+    bin_weight[bin].add(w);
     return CF_OK;
+}
+
+int cf_climatology::check_entry(const cfck::Entry& E, const char* fn) const {
+    if ((int)E.n_entries != n_bins)
+        return fail(ctx, CF_ERR_INVALID, "%s: section \"%s\" has %u bins in the image, the climatology has %d", fn, E.name, E.n_entries, n_bins);
+    return CF_OK;
+}
+
+// an attached climatology whose calendar table does not cover a step it would collect: nothing is launched
+int cf_climatology::admit(const Attachment& at, const char* fn, int64_t first_step, int nsteps) const {
+    int32_t bin;
+    for (int64_t step = first_step; step < first_step + nsteps; ++step)
+        if (at.when.due(step) && !lookup(edges.data(), bin_of_interval.data(), edges.size(), at.when.stamp(step), &bin))
+            return fail(ctx, CF_ERR_INVALID, "%s: step %lld at time %.17g lies outside the attached climatology's calendar table "
+                        "[%.17g, %.17g)", fn, (long long)step, at.when.stamp(step), edges.front(), edges.back());
+    return CF_OK;
+}
+
+// the averagers' rule, into the bin the calendar gives the step's time (−1: outside the analysis window, nothing is collected;
+// the table covers the step: admit)
+int cf_climatology::collect_step(const Attachment& at, int64_t step) {
+    int32_t bin = -1;
+    lookup(edges.data(), bin_of_interval.data(), edges.size(), at.when.stamp(step), &bin);
+    return bin >= 0 ? collect(bin, at.when.stride * at.step_weight) : CF_OK;
 }
 
 extern "C" {
@@ -129,7 +135,6 @@ int cf_climatology_create(cf_ctx* ctx, const cf_climatology_desc* desc, cf_clima
 
 int cf_climatology_destroy(cf_climatology* c) {
     if (!c) return CF_OK;
-    if (c->ctx && c->ctx->climatology.handle == c) c->ctx->climatology.detach();
     child_leave(c);
     delete c;
     return CF_OK;
@@ -137,28 +142,28 @@ int cf_climatology_destroy(cf_climatology* c) {
 
 int cf_climatology_reset(cf_climatology* c) {
     CHECK(live(c, "cf_climatology_reset", "climatology"));
-    c->weight = 0.0;
-    c->samples = 0;
-    std::fill(std::begin(c->bin_weight), std::end(c->bin_weight), 0.0);
-    std::fill(std::begin(c->bin_samples), std::end(c->bin_samples), (int64_t)0);
+    c->weight.reset();
+    for (RunningWeight& b : c->bin_weight) b.reset();
     return CF_OK;
 }
 
 int cf_climatology_collect(cf_climatology* c, int32_t bin, double weight) {
     CHECK(live(c, "cf_climatology_collect", "climatology"));
     if (bin < -1 || bin >= c->n_bins) return fail(c->ctx, CF_ERR_INVALID, "cf_climatology_collect: bin %d (−1…%d)", bin, c->n_bins - 1);
-    if (!(weight > 0.0) || !std::isfinite(weight) || !std::isfinite(c->weight + weight))
+    if (!c->weight.accepts(weight))
         return fail(c->ctx, CF_ERR_INVALID, "cf_climatology_collect: weight %g (> 0 and finite)", weight);
     if (bin < 0) return CF_OK;
-    return climatology_collect(c, bin, weight);
+    return c->collect(bin, weight);
 }
 
 int cf_climatology_weights(cf_climatology* c, double* total, int64_t* samples, double* bin_totals, int64_t* bin_samples) {
     CHECK(live(c, "cf_climatology_weights", "climatology"));
-    if (total) *total = c->weight;
-    if (samples) *samples = c->samples;
-    if (bin_totals) std::copy(c->bin_weight, c->bin_weight + c->n_bins, bin_totals);
-    if (bin_samples) std::copy(c->bin_samples, c->bin_samples + c->n_bins, bin_samples);
+    if (total) *total = c->weight.total;
+    if (samples) *samples = c->weight.samples;
+    for (int b = 0; b < c->n_bins; ++b) {
+        if (bin_totals) bin_totals[b] = c->bin_weight[b].total;
+        if (bin_samples) bin_samples[b] = c->bin_weight[b].samples;
+    }
     return CF_OK;
 }
 
@@ -168,7 +173,7 @@ int cf_climatology_extremes(cf_climatology* c, int32_t field, double* d_min, dou
     if (field < 0 || field >= c->n_fields) return fail(ctx, CF_ERR_INVALID, "cf_climatology_extremes: field %d (0…%d)", field, c->n_fields - 1);
     ClimatologyBinList L{};
     for (int b = 0; b < c->n_bins; ++b)
-        if (c->bin_samples[b] > 0) L.bin[L.n++] = (uint8_t)b;
+        if (c->bin_weight[b].samples > 0) L.bin[L.n++] = (uint8_t)b;
     if (L.n == 0) return fail(ctx, CF_ERR_INVALID, "cf_climatology_extremes: field %d has no available bins (nothing collected since the reset)", field);
     if (!d_min && !d_max && !d_argmin && !d_argmax) return CF_OK;
     const GridDesc& G = ctx->grid;
@@ -191,7 +196,7 @@ int cf_attach_climatology(cf_ctx* ctx, cf_climatology* c, int32_t stride, double
     const char* fn = "cf_attach_climatology";
     if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
     if (!c) {
-        ctx->climatology.detach();
+        ctx->attached[cf_ctx::AT_CLIMATOLOGY] = Attachment{};
         return CF_OK;
     }
     if (c->ctx != ctx) return fail(ctx, CF_ERR_INVALID, "%s: the climatology belongs to another context", fn);
@@ -203,15 +208,9 @@ int cf_attach_climatology(cf_ctx* ctx, cf_climatology* c, int32_t stride, double
     for (int32_t k = 0; k + 1 < n_edges; ++k)
         if (bin_of_interval[k] >= c->n_bins)
             return fail(ctx, CF_ERR_INVALID, "%s: bin_of_interval[%d] = %d, the climatology has %d bins", fn, k, bin_of_interval[k], c->n_bins);
-    ClimatologyAttachment at;
-    at.handle = c;
-    at.stride = stride;
-    at.step_weight = step_weight;
-    at.time_origin = time_origin;
-    at.step_seconds = step_seconds;
-    at.edges.assign(edges, edges + n_edges);
-    at.bin_of_interval.assign(bin_of_interval, bin_of_interval + (n_edges - 1));
-    ctx->climatology = std::move(at);
+    c->edges.assign(edges, edges + n_edges);
+    c->bin_of_interval.assign(bin_of_interval, bin_of_interval + (n_edges - 1));
+    ctx->attached[cf_ctx::AT_CLIMATOLOGY] = Attachment{c, StepSchedule{stride, time_origin, step_seconds}, step_weight};
     return CF_OK;
 }
 

@@ -14,9 +14,13 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "../../include/coflux.h"
+#include "coflux_checkpoint.hpp"
+#include "coflux_checkpoint_image.hpp"
+#include "coflux_collect.hpp"
 #include "coflux_fast.hpp"
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
@@ -47,43 +51,48 @@ struct RcclApi {
     ncclResult_t (*CommCuDevice)(const ncclComm_t, int*) = nullptr;
 };
 
-// What averagers, integrators, monitors, regridders and snapshot windows share: a handle made on a context may outlive it.  cf_destroy
-// orphans every child (orphan_children); calls that need the context then fail through live(), destroy still works.
+// What the step loops know of an attached handle (cf_ctx::attached): the handle and when it is due; a collection of an averager
+// or the climatology weighs stride · step_weight.  Steps are numbered globally (StepSchedule, coflux_collect.hpp).
+struct cf_child;
+struct Attachment {
+    cf_child* handle = nullptr;
+    StepSchedule when;
+    double step_weight = 0.0;
+    bool collects(int64_t step) const { return handle && when.due(step); }
+};
+
+// One section of a checkpoint image as its handle lays it out (plan_section): n_entries, count and bytes of the directory entry,
+// how many of the payload's bytes the device holds, the runs of them (the payload starts at image offset `offset`) and the
+// host-kept bytes that follow them
+struct SectionPlan {
+    uint32_t section;
+    uint64_t offset;
+    cfck::Entry& entry;
+    uint64_t& device_bytes;
+    std::vector<unsigned char>& tail;
+    std::vector<CheckpointSegment>& segments;
+};
+
+// What every handle made on a context is (averagers, climatologies, integrators, monitors, regridders, snapshot windows,
+// checkpoints): it may outlive the context.  cf_destroy orphans every child (orphan_children); calls that need the context then
+// fail through live(), destroy still works.  The step loops and the checkpoint ask the handle itself; the defaults are those of
+// a handle that is never attached or registered.
 struct cf_child {
     cf_ctx* ctx = nullptr;   // NULL once the context is destroyed
     int device = 0;
-};
-
-// What cf_time_steps knows of an attached series recorder (coflux_series.hpp; cf_attach_integrals, cf_attach_monitor).  Steps are
-// numbered globally, so a run split into several calls collects the same steps and stamps them with the same times.
-template <class Handle>
-struct SeriesAttachment {
-    Handle* handle = nullptr;
-    int32_t stride = 1;
-    double time_origin = 0.0, step_seconds = 0.0;
-    void detach() { handle = nullptr; }
-    bool collects(int64_t step) const { return handle && (step + 1) % stride == 0; }
-    double stamp(int64_t step) const { return time_origin + (double)(step + 1) * step_seconds; }
-    // of the steps [first_step, first_step + nsteps): those s with (s + 1) % stride == 0
-    int64_t collections(int64_t first_step, int nsteps) const { return (first_step + nsteps) / stride - first_step / stride; }
-};
-
-// What the step loops know of an attached climatology (coflux_climatology.cpp; cf_attach_climatology): the integrals' clock and a
-// copy of the caller's calendar table
-struct cf_climatology;
-struct ClimatologyAttachment {
-    cf_climatology* handle = nullptr;
-    int32_t stride = 1;
-    double step_weight = 0.0, time_origin = 0.0, step_seconds = 0.0;
-    std::vector<double> edges;
-    std::vector<int32_t> bin_of_interval;
-    void detach() {
-        handle = nullptr;
-        edges.clear();
-        bin_of_interval.clear();
-    }
-    bool collects(int64_t step) const { return handle && (step + 1) % stride == 0; }
-    double stamp(int64_t step) const { return time_origin + (double)(step + 1) * step_seconds; }
+    virtual ~cf_child() = default;
+    // attached as `at`: CF_ERR_INVALID (the refusal of `fn`) unless the steps [first_step, first_step + nsteps) may run — asked
+    // before anything is launched — and the collection of a due step
+    virtual int admit(const Attachment& /*at*/, const char* /*fn*/, int64_t /*first_step*/, int /*nsteps*/) const { return CF_OK; }
+    virtual int collect_step(const Attachment& /*at*/, int64_t /*step*/) { return CF_OK; }
+    // registered with a checkpoint (coflux_checkpoint.cpp): the section's kind (cfck::KIND_*); its layout — as the handle stands
+    // now or, with `image_count`, as an image with so many records states it (whose host-kept bytes the caller takes from the
+    // image); the payload bytes it can grow to; CF_ERR_INVALID unless an image's entry fits the handle; the host-kept bytes back
+    virtual uint32_t section_kind() const { return cfck::KINDS; }
+    virtual void plan_section(const SectionPlan&, const int64_t* /*image_count*/) const {}
+    virtual uint64_t section_room() const { return 0; }
+    virtual int check_entry(const cfck::Entry&, const char* /*fn*/) const { return CF_OK; }
+    virtual void load_tail(const std::vector<unsigned char>&, int64_t /*count*/) {}
 };
 
 // Ownership: every stream, event, device buffer and IPC mapping below is a cf:: owner (coflux_owned.hpp) and releases itself
@@ -226,19 +235,11 @@ struct cf_ctx {
     std::vector<cf_child*> children;
     // the checkpoint handles among them: cf_sync reports a restore whose device-side hashes do not match (coflux_checkpoint.cpp)
     std::vector<struct cf_checkpoint*> checkpoints;
-    // time averages (coflux_average.cpp): the ones the step loops collect, in slot order (cf_attach_average_slot; slot 0 is
-    // cf_attach_average's)
-    struct AverageSlot {
-        cf_average* handle = nullptr;
-        int32_t stride = 1;
-        double step_weight = 0.0;
-        bool collects(int64_t step) const { return handle && (step + 1) % stride == 0; }
-    } averages[CF_ATTACHED_AVERAGES_MAX];
-    // the series recorders cf_time_steps collects after it: surface integrals (cf_attach_integrals), then the monitor (cf_attach_monitor)
-    SeriesAttachment<cf_integrals> integrals;
-    SeriesAttachment<cf_monitor> monitor;
-    // the calendar-binned means the step loops collect between the averager slots and the integrator (cf_attach_climatology)
-    ClimatologyAttachment climatology;
+    // what the step loops collect behind every step, in this order: the time averages in slot order (cf_attach_average_slot; slot 0
+    // is cf_attach_average's), the calendar-binned means (cf_attach_climatology), then the series recorders: surface integrals
+    // (cf_attach_integrals) and the monitor (cf_attach_monitor)
+    enum { AT_CLIMATOLOGY = CF_ATTACHED_AVERAGES_MAX, AT_INTEGRALS, AT_MONITOR, AT_COUNT };
+    Attachment attached[AT_COUNT];
 };
 
 // One cf_time_steps call's step loop, as CF_OPT_LAND_ZEROS sees it: open for exactly the scope's lifetime
@@ -256,15 +257,24 @@ struct LandZeroScope {
     LandZeroScope& operator=(const LandZeroScope&) = delete;
 };
 
+// time averages: what cf_average_create (coflux_average.cpp), cf_average_create_derived (coflux_derived.cpp) and
+// cf_average_create_budget (coflux_budget.cpp) hand back differs in the arguments of a collection's launch only
+struct PlainAverageArgs {
+    int nfields;
+    AverageFields fields;
+};
 struct cf_average : cf_child {
-    int nfields = 0;
-    AverageFields fields{};
-    double total = 0.0;      // the window's total weight
-    int64_t samples = 0;
-    bool derived = false;    // made by cf_average_create_derived (coflux_derived.cpp): `terms` replaces `fields`
-    DerivedArgs terms{};
-    bool budget = false;     // made by cf_average_create_budget (coflux_budget.cpp): `budget_terms` replaces `fields`
-    BudgetArgs budget_terms{};
+    std::variant<PlainAverageArgs, DerivedArgs, BudgetArgs> args;
+    RunningWeight weight;    // of the window
+    int collect(double w);   // one collection (cf_average_collect without the argument checks of the ABI entry)
+    int collect_step(const Attachment& at, int64_t) override { return collect(at.when.stride * at.step_weight); }
+    uint32_t section_kind() const override { return cfck::KIND_AVERAGE; }
+    void plan_section(const SectionPlan& P, const int64_t*) const override {
+        P.entry.bytes = RunningWeight::BYTES;
+        P.tail.resize(RunningWeight::BYTES);
+        weight.put(P.tail.data());
+    }
+    void load_tail(const std::vector<unsigned char>& tail, int64_t) override { weight.get(tail.data()); }
 };
 
 // calendar-binned means (coflux_climatology.cpp): the pointers are the caller's, the weights are host bookkeeping — the handle
@@ -274,10 +284,22 @@ struct cf_climatology : cf_child {
     const double* src[CF_CLIMATOLOGY_MAX_FIELDS] = {};
     double* total[CF_CLIMATOLOGY_MAX_FIELDS] = {};
     double* bins[CF_CLIMATOLOGY_MAX_FIELDS] = {};
-    double weight = 0.0;       // of every collection since the reset
-    int64_t samples = 0;
-    double bin_weight[CF_CLIMATOLOGY_MAX_BINS] = {};
-    int64_t bin_samples[CF_CLIMATOLOGY_MAX_BINS] = {};
+    RunningWeight weight;       // of every collection since the reset
+    RunningWeight bin_weight[CF_CLIMATOLOGY_MAX_BINS];
+    std::vector<double> edges;               // while attached: a copy of the caller's calendar table (cf_attach_climatology)
+    std::vector<int32_t> bin_of_interval;
+    int collect(int32_t bin, double w);   // one collection into bin ≥ 0 (cf_climatology_collect without the argument checks)
+    int admit(const Attachment& at, const char* fn, int64_t first_step, int nsteps) const override;   // the table covers every due step
+    int collect_step(const Attachment& at, int64_t step) override;
+    uint32_t section_kind() const override { return cfck::KIND_CLIMATOLOGY; }
+    void plan_section(const SectionPlan& P, const int64_t*) const override {
+        P.entry.n_entries = (uint32_t)n_bins;
+        P.entry.bytes = RunningWeight::BYTES + 16 * (uint64_t)n_bins;
+        P.tail.resize((size_t)P.entry.bytes);
+        put_binned_weights(P.tail.data(), weight, bin_weight, n_bins);
+    }
+    int check_entry(const cfck::Entry& E, const char* fn) const override;
+    void load_tail(const std::vector<unsigned char>& tail, int64_t) override { get_binned_weights(tail.data(), &weight, bin_weight, n_bins); }
 };
 
 struct cf_regrid : cf_child {
@@ -306,12 +328,6 @@ int cf_fail(cf_ctx* ctx, int code, const char* fmt, ...);
 
 // coflux_steps.cpp: the stand-alone peer-direct exchange kernel for `F` (counts the exchange in ctx->peer_seq)
 extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows);
-// coflux_average.cpp: one collection of `a` (cf_average_collect without the argument checks of the ABI entry)
-int average_collect(cf_average* a, double weight);
-// coflux_climatology.cpp: one collection of `c` into bin ≥ 0 (cf_climatology_collect without the argument checks of the ABI
-// entry); the bin of `time` in a calendar table that cf_attach_climatology has validated (false: outside the table)
-int climatology_collect(cf_climatology* c, int32_t bin, double weight);
-bool calendar_lookup(const std::vector<double>& edges, const std::vector<int32_t>& bin_of_interval, double time, int32_t* bin);
 // coflux_checkpoint.cpp: waits for the restores of ctx's checkpoint handles that are still unchecked and compares their hashes
 int checkpoint_settle_restores(cf_ctx* ctx);
 // coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state); *route is the counter of
@@ -347,23 +363,25 @@ inline bool ranges_overlap(const void* p, uintptr_t bytes_p, const void* q, uint
     return x < y + bytes_q && y < x + bytes_p;
 }
 
-// The child handles: `child` joins ctx's list / leaves it (a no-op once orphaned) / cf_destroy orphans them all
+// The child handles: `child` joins ctx's list / leaves it and whichever attachment holds it (a no-op once orphaned) / cf_destroy
+// orphans them all
 inline void child_adopt(cf_ctx* ctx, cf_child* child) {
     child->ctx = ctx;
     child->device = ctx->device;
     ctx->children.push_back(child);
 }
 inline void child_leave(cf_child* child) {
-    if (cf_ctx* ctx = child->ctx) ctx->children.erase(std::remove(ctx->children.begin(), ctx->children.end(), child), ctx->children.end());
+    cf_ctx* ctx = child->ctx;
+    if (!ctx) return;
+    ctx->children.erase(std::remove(ctx->children.begin(), ctx->children.end(), child), ctx->children.end());
+    for (Attachment& at : ctx->attached)
+        if (at.handle == child) at = Attachment{};
 }
 inline void orphan_children(cf_ctx* ctx) {
     for (cf_child* child : ctx->children) child->ctx = nullptr;
     ctx->children.clear();
     ctx->checkpoints.clear();
-    for (auto& slot : ctx->averages) slot.handle = nullptr;
-    ctx->integrals.detach();
-    ctx->monitor.detach();
-    ctx->climatology.detach();
+    for (Attachment& at : ctx->attached) at = Attachment{};
 }
 // CF_ERR_INVALID unless `child` is a handle whose context is alive: live(a, "cf_average_reset", "averager")
 inline int live(const cf_child* child, const char* fn, const char* kind) {

@@ -1,5 +1,5 @@
 // coflux_derived.cpp — cf_average_create_derived (include/coflux.h): checks a term table, numbers its distinct source arrays
-// and hands back an ordinary cf_average whose collections go to the kernel of coflux_derived.hip (average_collect,
+// and hands back a cf_average whose collections go to the kernel of coflux_derived.hip (cf_average::collect,
 // coflux_average.cpp, chooses the launch).  Nothing is allocated on the device.
 #include "coflux_ctx.hpp"
 
@@ -85,9 +85,7 @@ extern "C" int cf_average_create_derived(cf_ctx* ctx, const cf_average_desc* des
             if (overlap(A.mean[t], A.mean[u])) return fail(ctx, CF_ERR_INVALID, "cf_average_create_derived: means %d and %d overlap", u, t);
     }
     cf_average* a = new cf_average();
-    a->nfields = n;
-    a->derived = true;
-    a->terms = A;
+    a->args = A;
     child_adopt(ctx, a);
     *out = a;
     return CF_OK;

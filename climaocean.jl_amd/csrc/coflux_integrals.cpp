@@ -4,6 +4,12 @@
 // pass and one combination launch per collection.
 #include "coflux_series.hpp"
 
+int cf_integrals::collect(double time) {
+    return series_collect(this, time, "cf_integrals_collect", [this](double* record) {
+        return launch_integrals(ctx->stream, args, ctx->grid, record, max_blocks);
+    });
+}
+
 extern "C" {
 
 int cf_integrals_create(cf_ctx* ctx, const cf_integrals_desc* desc, int32_t capacity, cf_integrals** out) {
@@ -64,12 +70,11 @@ int cf_integrals_create(cf_ctx* ctx, const cf_integrals_desc* desc, int32_t capa
     return CF_OK;
 }
 
-int cf_integrals_destroy(cf_integrals* q) { return series_destroy(q, &cf_ctx::integrals); }
+int cf_integrals_destroy(cf_integrals* q) { return series_destroy(q); }
 
 int cf_integrals_collect(cf_integrals* q, double time) {
-    return series_collect(q, time, "cf_integrals_collect", "integrator", [q](double* record) {
-        return launch_integrals(q->ctx->stream, q->args, q->ctx->grid, record, q->max_blocks);
-    });
+    CHECK(live(q, "cf_integrals_collect", "integrator"));
+    return q->collect(time);
 }
 
 int cf_integrals_count(cf_integrals* q, int64_t* records) { return series_count(q, records, "cf_integrals_count", "integrator"); }
@@ -85,7 +90,7 @@ int cf_integrals_reset(cf_integrals* q) {
 }
 
 int cf_attach_integrals(cf_ctx* ctx, cf_integrals* q, int32_t stride, double time_origin, double step_seconds) {
-    return series_attach(ctx, &cf_ctx::integrals, q, stride, time_origin, step_seconds, "cf_attach_integrals", "integrator");
+    return series_attach(ctx, cf_ctx::AT_INTEGRALS, q, stride, time_origin, step_seconds, "cf_attach_integrals", "integrator");
 }
 
 }  // extern "C"

@@ -4,6 +4,12 @@
 // does one pass and one combination launch per collection.
 #include "coflux_series.hpp"
 
+int cf_monitor::collect(double time) {
+    return series_collect(this, time, "cf_monitor_collect", [this](cf_monitor_value* record) {
+        return launch_monitor(ctx->stream, args, ctx->grid, record, count, max_blocks);
+    });
+}
+
 extern "C" {
 
 int cf_monitor_create(cf_ctx* ctx, const cf_monitor_desc* desc, int32_t capacity, cf_monitor** out) {
@@ -47,12 +53,11 @@ int cf_monitor_create(cf_ctx* ctx, const cf_monitor_desc* desc, int32_t capacity
     return CF_OK;
 }
 
-int cf_monitor_destroy(cf_monitor* m) { return series_destroy(m, &cf_ctx::monitor); }
+int cf_monitor_destroy(cf_monitor* m) { return series_destroy(m); }
 
 int cf_monitor_collect(cf_monitor* m, double time) {
-    return series_collect(m, time, "cf_monitor_collect", "monitor", [m](cf_monitor_value* record) {
-        return launch_monitor(m->ctx->stream, m->args, m->ctx->grid, record, m->count, m->max_blocks);
-    });
+    CHECK(live(m, "cf_monitor_collect", "monitor"));
+    return m->collect(time);
 }
 
 int cf_monitor_count(cf_monitor* m, int64_t* records) { return series_count(m, records, "cf_monitor_count", "monitor"); }
@@ -83,7 +88,7 @@ int cf_monitor_reset(cf_monitor* m) {
 }
 
 int cf_attach_monitor(cf_ctx* ctx, cf_monitor* m, int32_t stride, double time_origin, double step_seconds) {
-    return series_attach(ctx, &cf_ctx::monitor, m, stride, time_origin, step_seconds, "cf_attach_monitor", "monitor");
+    return series_attach(ctx, cf_ctx::AT_MONITOR, m, stride, time_origin, step_seconds, "cf_attach_monitor", "monitor");
 }
 
 }  // extern "C"

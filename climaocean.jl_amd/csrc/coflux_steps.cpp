@@ -441,18 +441,10 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
             CHECK(check_coupled_prepare(ctx, &P));
         }
     }
-    CHECK(series_room(ctx, ctx->integrals, first_step, nsteps, "integrator"));   // a series that would overflow: nothing is launched
-    CHECK(series_room(ctx, ctx->monitor, first_step, nsteps, "monitor"));
-    // an attached climatology whose calendar table does not cover a step it would collect: nothing is launched either
-    if (ctx->climatology.handle)
-        for (int64_t step = first_step; step < first_step + nsteps; ++step) {
-            int32_t bin;
-            if (ctx->climatology.collects(step) &&
-                !calendar_lookup(ctx->climatology.edges, ctx->climatology.bin_of_interval, ctx->climatology.stamp(step), &bin))
-                return fail(ctx, CF_ERR_INVALID, "%s: step %lld at time %.17g lies outside the attached climatology's calendar table "
-                            "[%.17g, %.17g)", name, (long long)step, ctx->climatology.stamp(step), ctx->climatology.edges.front(),
-                            ctx->climatology.edges.back());
-        }
+    // what is attached says whether the call may run — a series that would overflow, a calendar table that does not cover a step
+    // it would collect: nothing is launched.  (The series are asked first: which refusal a call with two gets is part of the ABI.)
+    for (int k : {cf_ctx::AT_INTEGRALS, cf_ctx::AT_MONITOR, cf_ctx::AT_CLIMATOLOGY})
+        if (const Attachment& at = ctx->attached[k]; at.handle) CHECK(at.handle->admit(at, name, first_step, nsteps));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (int n = 0; n < S->n_ocean_states; ++n) {
         if (ctx->dev.mask_kind != CF_MASK_NONE && !S->ocean_states[n].mask) return fail(ctx, CF_ERR_INVALID, "ocean state %d has no mask", n);
@@ -554,22 +546,11 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
         } else {
             CHECK(cf_update_state(ctx, &s, w, o, a, fluxes, ice, net));
         }
-        // the attached averagers (cf_attach_average, cf_attach_average_slot), in slot order, collect on the GLOBAL step index: a run
-        // split into several calls collects the same steps.  Queued behind every launch of the step — the face stresses of the
-        // merged and tail forms included
-        for (const auto& slot : ctx->averages)
-            if (slot.collects(step)) CHECK(average_collect(slot.handle, slot.stride * slot.step_weight));
-        // the attached climatology (cf_attach_climatology): the same rule, into the bin its calendar gives the step's time (−1:
-        // outside the analysis window, nothing is collected; the table covers the step: checked before the first launch)
-        if (ctx->climatology.collects(step)) {
-            const ClimatologyAttachment& at = ctx->climatology;
-            int32_t bin = -1;
-            calendar_lookup(at.edges, at.bin_of_interval, at.stamp(step), &bin);
-            if (bin >= 0) CHECK(climatology_collect(at.handle, bin, at.stride * at.step_weight));
-        }
-        // an attached integrator, then an attached monitor (SeriesAttachment): the same rule, one record per collected step
-        if (ctx->integrals.collects(step)) CHECK(cf_integrals_collect(ctx->integrals.handle, ctx->integrals.stamp(step)));
-        if (ctx->monitor.collects(step)) CHECK(cf_monitor_collect(ctx->monitor.handle, ctx->monitor.stamp(step)));
+        // what is attached collects where its schedule says the step is due, in the order of cf_ctx::attached: the averagers in
+        // slot order, the climatology, the integrator, the monitor.  Queued behind every launch of the step — the
+        // face stresses of the merged and tail forms included
+        for (const Attachment& at : ctx->attached)
+            if (at.collects(step)) CHECK(at.handle->collect_step(at, step));
     }
     return CF_OK;
 }
