@@ -21,7 +21,6 @@ int cf_fail(cf_ctx* ctx, int code, const char* fmt, ...) {
 }
 
 static int wait_for_halos(cf_ctx* ctx);
-int cf_flush_deferred_prefetch(cf_ctx* ctx);  // coflux_steps.cpp
 
 static bool roughness_ok(const cf_roughness& r, bool scalar) {
     if (scalar) {
@@ -600,9 +599,7 @@ int cf_set_stream(cf_ctx* ctx, void* hip_stream) {
     if (next != ctx->stream) {
         // a requested-ahead atmosphere state that was launched ON the old stream is consumed by stream order alone (no event):
         // the new stream has to wait for it
-        bool pending = false;
-        for (auto& p : ctx->prefetch) pending |= p.valid && p.on_main;
-        if (pending) {
+        if (ctx->ahead.any_left_on_main()) {
             HIP_TRY(ctx, hipSetDevice(ctx->device));
             cf::Event ev;
             HIP_TRY(ctx, ev.create(hipEventDisableTiming));
@@ -618,7 +615,8 @@ int cf_sync(cf_ctx* ctx) {
     if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));  // one process may drive several contexts / devices
     if (int rc = wait_for_halos(ctx)) return rc;
-    CHECK(cf_flush_deferred_prefetch(ctx));
+    const AheadLedger::Work flush = ctx->ahead.leave_aux();
+    CHECK(cf_ahead_perform(ctx, &flush));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->aux.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux.stream.get()));
     if (ctx->d_peer_status && ctx->peer_seq) {  // a peer-direct exchange whose neighbour never arrived
@@ -752,10 +750,8 @@ int cf_debug_prefetch_stats(cf_ctx* ctx, cf_prefetch_stats* out) {
     if (!ctx || !out) return fail(ctx, CF_ERR_INVALID, "cf_debug_prefetch_stats: bad arguments");
     if (out->struct_size != (int32_t)sizeof(cf_prefetch_stats))
         return fail(ctx, CF_ERR_INVALID, "cf_prefetch_stats.struct_size = %d, library expects %zu", out->struct_size, sizeof(cf_prefetch_stats));
-    *out = ctx->prefetch_stats;
+    *out = ctx->ahead.stats();
     out->struct_size = (int32_t)sizeof(cf_prefetch_stats);
-    out->pending = ctx->deferred.valid ? 1 : 0;
-    for (const auto& p : ctx->prefetch) out->pending += p.valid ? 1 : 0;
     return CF_OK;
 }
 
@@ -853,22 +849,6 @@ int cf_compute_net_ocean_fluxes(cf_ctx* ctx, const cf_ocean_surface* ocean, cons
     return CF_OK;
 }
 
-// A deferred next-step interpolation (cf_prefetch_atmosphere_state) that has just been launched on the MAIN stream — as the
-// solver launch's tail workgroups, inside the face-stress launch, or as a plain launch: stream order replaces the event.
-int deferred_went_out_on_main(cf_ctx* ctx, uint64_t* route) {
-    cf_ctx::Prefetch* slot = ctx->prefetch_slot(ctx->deferred.out.u);
-    // (never taken: the request was refused when it was made, cf_prefetch_atmosphere_state — a kernel has been launched by now)
-    if (!slot) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
-    ++*route;
-    slot->key = ctx->deferred.out.u;
-    slot->src = ctx->deferred.src;
-    slot->w = ctx->deferred.w;
-    slot->valid = true;
-    slot->on_main = true;
-    ctx->deferred.valid = false;
-    return CF_OK;
-}
-
 // hold_tail_work (cf_update_state_sea_ice with CF_OPT_MERGED_PREFETCH = 2): the face stresses and a requested next-step
 // interpolation are NOT launched here — they ride in the tail of the sea-ice interface launch that follows, whose workgroups
 // retire over a much longer span than the ocean solver's; *stress_held tells the caller whether the stresses are still due.
@@ -893,30 +873,21 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     if (rec) HIP_TRY(ctx, hipEventRecord(ev[0].get(), ctx->stream));
     // a prefetched atmosphere state (cf_prefetch_atmosphere_state) for exactly this step and this set of exchange
     // fields is already on its way on the auxiliary stream: wait for it instead of interpolating again
-    bool prefetched = false;
-    if (ctx->deferred.valid && ctx->deferred.out.u == atmos->u) CHECK(cf_flush_deferred_prefetch(ctx));  // asked for THIS step
-    for (auto& p : ctx->prefetch) {
-        if (!p.valid || p.key != atmos->u) continue;
-        if (!p.on_main) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p.done, 0));  // also orders a mismatched prefetch before our writes
-        prefetched = same_interpolation(p.src, p.w, *src, *w);
-        p.valid = false;
-        ++(prefetched ? ctx->prefetch_stats.consumed : ctx->prefetch_stats.mismatched);
-    }
+    const AheadLedger::Stepped stepped = ctx->ahead.step(atmos->u, *src, *w);
+    CHECK(cf_ahead_perform(ctx, &stepped.work));
     // Fused forms.  Net fluxes: the cell-local part of compute_net_ocean_fluxes! (everything but the two face stresses,
     // which need the west / south neighbour's ρτ) is computed in the solver's epilogue from registers, and a thin stress
     // kernel follows — bitwise the same numbers as the three-launch sequence (shared arithmetic, contraction off).
     const bool fuse = net_fluxes_fused(ctx);
-    if (!prefetched) {
-        HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, src, w, atmos));
-        ++ctx->prefetch_stats.step_interpolations;
-    }
+    if (stepped.interpolate) HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, src, w, atmos));
     if (rec) HIP_TRY(ctx, hipEventRecord(ev[1].get(), ctx->stream));
     CHECK(wait_for_halos(ctx));  // the interpolation above overlapped the halo rows
-    // CF_OPT_MERGED_PREFETCH = 2: a requested next-step interpolation becomes the TAIL workgroups of this solver launch
+    // A requested next-step interpolation that this step's launches may carry (cf_prefetch_atmosphere_state).
+    // CF_OPT_MERGED_PREFETCH = 2: it becomes the TAIL workgroups of this solver launch
+    const AheadLedger::Record* next = ctx->ahead.waiting_for_other_set(atmos->u);
     const bool tail_lean = ctx->launch.d_lean_info && ctx->fast.specialization == SOLVER_OCEAN_LEAN && ctx->launch.solver == CF_SOLVER_TABLES;
     const bool tail_ly = ctx->fast.specialization == SOLVER_LY && ctx->launch.solver == CF_SOLVER_TABLES;
-    const bool tail = fuse && !hold_tail_work && ctx->merged_prefetch == 2 && ctx->deferred.valid &&
-                      interp_tile_fits(ctx, 40960) && ctx->deferred.out.u != atmos->u && (tail_lean || tail_ly);
+    const bool tail = fuse && !hold_tail_work && ctx->merged_prefetch == 2 && next && interp_tile_fits(ctx, 40960) && (tail_lean || tail_ly);
     // With sea ice (cf_update_state_sea_ice): the ocean solve itself is handed to the caller, whose interface-solve launch carries
     // its workgroups behind its own (ice_ocean_kernel) — the stresses then follow that launch
     const bool ride = hold_tail_work && ocean_rider && fuse && tail_lean && !rec;
@@ -972,27 +943,30 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
         interpolate_grid(L, ctx->grid, &rows, &blocks);
         if (tail_lean)
             HIP_TRY(ctx, launch_ao_fluxes_lean(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
-                                               ctx->d_land_freshwater, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out, rows, blocks, halo));
+                                               ctx->d_land_freshwater, &next->src, &next->w, &next->out, rows, blocks, halo));
         else
             HIP_TRY(ctx, launch_ly_fluxes_with_tail(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
-                                                    ctx->d_land_freshwater, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out, rows, blocks));
-        CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_tail));
+                                                    ctx->d_land_freshwater, &next->src, &next->w, &next->out, rows, blocks));
+        ctx->ahead.leave_main(next, AheadLedger::TAIL);
     } else
     HIP_TRY(ctx, launch_ao_fluxes(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes,
                                   fuse ? ice : nullptr, fuse ? net : nullptr, ctx->d_land_freshwater));
     if (ctx->step_loop.open && !keep_land) ++ctx->step_loop.zero_launches;
-    // A requested next-step interpolation (cf_prefetch_atmosphere_state).  CF_OPT_MERGED_PREFETCH: it rides in THIS step's
+    // CF_OPT_MERGED_PREFETCH = 1: the requested next-step interpolation rides in THIS step's
     // face-stress launch on the main stream — two independent memory-bound kernels, one launch boundary fewer (on a
     // latitude slab a boundary is a tenth of the step).  Otherwise it goes out on the auxiliary stream right behind the
     // solver: the solver's workgroups are dispatched first, the gather kernel takes what they leave free.
-    const bool merge = fuse && !hold_tail_work && ctx->merged_prefetch == 1 && ctx->deferred.valid && interp_tile_fits(ctx, 65536) &&
-                       ctx->deferred.out.u != atmos->u;
-    if (ctx->merged_prefetch == 0) CHECK(cf_flush_deferred_prefetch(ctx));
+    // (`next` is as fetched above: the tail form is mode 2's and the flush below mode 0's — under mode 1 nothing has carried it)
+    const bool merge = fuse && !hold_tail_work && ctx->merged_prefetch == 1 && next && interp_tile_fits(ctx, 65536);
+    if (ctx->merged_prefetch == 0) {
+        const AheadLedger::Work behind_solver = ctx->ahead.leave_aux();
+        CHECK(cf_ahead_perform(ctx, &behind_solver));
+    }
     if (rec) HIP_TRY(ctx, hipEventRecord(ev[2].get(), ctx->stream));
     if (merge) {
-        HIP_TRY(ctx, launch_interpolate_and_stress(ctx->stream, ctx->launch, ctx->dev, ctx->grid, &ctx->deferred.src, &ctx->deferred.w,
-                                                   &ctx->deferred.out, ocean, fluxes, ice, net));
-        CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_merged));
+        HIP_TRY(ctx, launch_interpolate_and_stress(ctx->stream, ctx->launch, ctx->dev, ctx->grid, &next->src, &next->w, &next->out, ocean,
+                                                   fluxes, ice, net));
+        ctx->ahead.leave_main(next, AheadLedger::MERGED);
     } else if (fuse && hold_tail_work) {
         if (stress_held) *stress_held = true;   // (the caller's next launch carries them)
     } else if (fuse)
@@ -1003,11 +977,12 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
         HIP_TRY(ctx, hipEventRecord(ev[3].get(), ctx->stream));
         ++ctx->prof_count;
     }
-    if (!hold_tail_work && ctx->merged_prefetch != 0 && ctx->deferred.valid && ctx->deferred.out.u != atmos->u) {
+    next = ctx->ahead.waiting_for_other_set(atmos->u);   // (still waiting: no launch above carried it)
+    if (!hold_tail_work && ctx->merged_prefetch != 0 && next) {
         // neither merged form applies to this step (another solver kernel, un-fused net fluxes …): the requested interpolation
         // goes out as a launch of its own on the same stream — the sequence of an un-pipelined step, one step early
-        HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out));
-        CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_own));
+        HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &next->src, &next->w, &next->out));
+        ctx->ahead.leave_main(next, AheadLedger::OWN);
     }
     if (ctx->step_loop.open) ctx->step_loop.last_way = way;   // (every launch of the step is queued: the next step may rely on its land)
     return CF_OK;
@@ -1390,6 +1365,7 @@ int cf_update_state_sea_ice(cf_ctx* ctx, const cf_atmos_source* src, const cf_in
                             ice_tail ? &rider : nullptr));
     AiTail T{};
     bool interp_rides = false;
+    const AheadLedger::Record* next = ctx->ahead.waiting_for_other_set(atmos->u);   // (held back by the step above under ice_tail)
     const bool stress_after = rider.valid && stress_held;
     if (rider.valid) {
         T.ocean = &rider;
@@ -1403,11 +1379,11 @@ int cf_update_state_sea_ice(cf_ctx* ctx, const cf_atmos_source* src, const cf_in
             T.stress_ice = ice_partition;
             T.stress_net = net;
         }
-        if (ctx->deferred.valid && ctx->deferred.out.u != atmos->u && interp_tile_fits(ctx, 40960)) {
+        if (next && interp_tile_fits(ctx, 40960)) {
             interpolate_grid(ctx->launch, ctx->grid, &T.interp_rows, &T.interp_blocks);
-            T.next_src = &ctx->deferred.src;
-            T.w = &ctx->deferred.w;
-            T.next_out = &ctx->deferred.out;
+            T.next_src = &next->src;
+            T.w = &next->w;
+            T.next_out = &next->out;
             interp_rides = true;
         }
     }
@@ -1420,10 +1396,11 @@ int cf_update_state_sea_ice(cf_ctx* ctx, const cf_atmos_source* src, const cf_in
                        net_in_epilogue ? net_ice->top_heat : nullptr, net_in_epilogue ? net_ice->bottom_heat : nullptr};
     CHECK(atmosphere_sea_ice_fluxes_impl(ctx, ice_state, ocean, atmos, ai_fluxes, any_tail ? &T : nullptr, net_in_epilogue ? &NI : nullptr));
     if (stress_after) HIP_TRY(ctx, launch_net_stress(ctx->stream, ctx->dev, ctx->grid, ocean, ao_fluxes, ice_partition, net));
-    if (interp_rides) CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_ice_tail));
-    if (ice_tail && ctx->deferred.valid && ctx->deferred.out.u != atmos->u) {   // (no tiled interpolation configured: a launch of its own)
-        HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out));
-        CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_own));
+    if (interp_rides) {
+        ctx->ahead.leave_main(next, AheadLedger::ICE_TAIL);
+    } else if (ice_tail && next) {   // (no tiled interpolation configured: a launch of its own)
+        HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &next->src, &next->w, &next->out));
+        ctx->ahead.leave_main(next, AheadLedger::OWN);
     }
     if (net_in_epilogue) return CF_OK;
     return cf_compute_net_sea_ice_fluxes(ctx, ice_state, ocean, atmos, ai_fluxes, frazil_heat, interface_heat, net_ice);

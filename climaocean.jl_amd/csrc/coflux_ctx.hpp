@@ -25,6 +25,7 @@
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
 #include "coflux_owned.hpp"
+#include "coflux_request_ahead.hpp"
 #include "coflux_tables.h"
 
 using namespace coflux;
@@ -162,41 +163,14 @@ struct cf_ctx {
     std::string error;
     std::mutex error_mutex;  // cf_window_wait_slot may fail on a reader thread while the stepping thread reads the text
     // auxiliary stream: the next step's interpolation runs here while the current step's solver runs on `stream`
-    // (cf_prefetch_atmosphere_state); one record per exchange-field set, matched by cf_update_state
+    // (cf_prefetch_atmosphere_state).  The context owns the HIP objects; who is on the lane, who waits to get there and every
+    // counter of cf_debug_prefetch_stats are `ahead`'s (coflux_request_ahead.hpp), whose record k owns done[k]
     struct AuxLane {
         cf::Stream stream;
-        cf::Event ev_gate;
-        cf::Event done[2];   // prefetch[k].done views done[k]
+        cf::Event ev_gate;   // recorded on `stream` at the point after which a requested set is free to be overwritten
+        cf::Event done[2];
     } aux;
-    struct Prefetch {
-        const double* key = nullptr;  // exchange set, identified by its u pointer
-        cf_atmos_source src{};        // what was interpolated: the source's arrays and shape, the levels and the fraction …
-        cf_interp_weights w{};        // … through which map (same_interpolation compares both with what a step asks for)
-        hipEvent_t done = nullptr;    // a view of aux.done[k]: NULL until the auxiliary lane exists
-        bool valid = false;
-        bool on_main = false;         // launched on the main stream (merged with the face stresses): stream order, no event
-    } prefetch[2];
-    // a prefetch that has been requested but not launched yet: it goes out right AFTER the next solver launch, so
-    // that the solver's workgroups are dispatched first and the interpolation only fills what they leave free
-    struct Deferred {
-        bool valid = false;
-        bool gated = false;  // aux.ev_gate was recorded when the request was made (not with merged_prefetch: the request
-                             // normally leaves on the main stream, where stream order gates it; a flush records it late)
-        cf_atmos_source src{};
-        cf_interp_weights w{};
-        cf_exchange_fields out{};
-    } deferred;
-    // which way every request went (cf_debug_prefetch_stats): plain host counters, bumped where the decision is taken.
-    // requests = consumed + mismatched + voided + superseded + discarded + pending, at every point (`pending` is counted on demand)
-    cf_prefetch_stats prefetch_stats{};
-    // the record a state for exchange set `key` would be booked in: the one that holds that set, else a free one, else NULL
-    Prefetch* prefetch_slot(const double* key) {
-        for (auto& p : prefetch)
-            if (p.valid && p.key == key) return &p;
-        for (auto& p : prefetch)
-            if (!p.valid) return &p;
-        return nullptr;
-    }
+    AheadLedger ahead;
     // peer-direct halo rows (coflux_halo.hip)
     PeerMailbox peer{};                                  // raw views of the three below
     cf::DeviceBuffer<char> peer_mine;                    // this context's mailbox (fine-grained)
@@ -330,26 +304,14 @@ int cf_fail(cf_ctx* ctx, int code, const char* fmt, ...);
 extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows);
 // coflux_checkpoint.cpp: waits for the restores of ctx's checkpoint handles that are still unchecked and compares their hashes
 int checkpoint_settle_restores(cf_ctx* ctx);
-// coflux_abi.cpp: books ctx->deferred as launched on the main stream (see cf_update_state); *route is the counter of
-// ctx->prefetch_stats that names the launch it left in
-extern "C" __attribute__((visibility("hidden"))) int deferred_went_out_on_main(cf_ctx* ctx, uint64_t* route);
+// coflux_steps.cpp: queues what a transition of ctx->ahead answered with (AheadLedger::Work)
+extern "C" __attribute__((visibility("hidden"))) int cf_ahead_perform(cf_ctx* ctx, const AheadLedger::Work* work);
 // coflux_abi.cpp: the argument checks of cf_prepare_coupled_step and of the cf_update_state_sea_ice of a coupled step loop,
 // without their launches (cf_time_steps_coupled validates a whole call before its first launch)
 extern "C" __attribute__((visibility("hidden"))) int check_coupled_prepare(cf_ctx* ctx, const cf_coupled_prepare* p);
 extern "C" __attribute__((visibility("hidden"))) int check_coupled_update(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
                                                                           const cf_run_schedule* S, const cf_interface_fluxes* fluxes,
                                                                           const cf_net_ocean_fluxes* net, const cf_interface_fluxes* ai_fluxes);
-
-// Whether the atmosphere state requested ahead from (a, wa) is the one a step asks for with (b, wb): the same source arrays and
-// shape, levels and time fraction, through the same map.  Levels and fraction alone do not say so: two snapshot windows, a
-// re-bound in-memory atmosphere or a second weight map give another field under the same clock.
-inline bool same_interpolation(const cf_atmos_source& a, const cf_interp_weights& wa, const cf_atmos_source& b, const cf_interp_weights& wb) {
-    for (int v = 0; v < CF_JRA55_NVARS; ++v)
-        if (a.data[v] != b.data[v]) return false;
-    return a.ns_x == b.ns_x && a.ns_y == b.ns_y && a.n_levels == b.n_levels && a.level1 == b.level1 && a.level2 == b.level2 &&
-           a.time_fraction == b.time_fraction && wa.separable == wb.separable && wa.fi == wb.fi && wa.fj == wb.fj &&
-           wa.cos_rot == wb.cos_rot && wa.sin_rot == wb.sin_rot && wa.latitude == wb.latitude;
-}
 
 // whether two ocean-grid fields (halos included) at p and q share bytes: what the averagers refuse between a mean and anything else
 inline bool fields_overlap(const GridDesc& G, const void* p, const void* q) {

@@ -22,66 +22,38 @@ static int ensure_aux_stream(cf_ctx* ctx) {
     HIP_TRY(ctx, lane.ev_gate.create(hipEventDisableTiming));
     for (cf::Event& e : lane.done) HIP_TRY(ctx, e.create(hipEventDisableTiming));
     ctx->aux = std::move(lane);
-    for (int k = 0; k < 2; ++k) ctx->prefetch[k].done = ctx->aux.done[k].get();
     return CF_OK;
 }
 
-// Launch the interpolation of `src` into `out` on the auxiliary stream, gated on the lane's gate event (recorded by the caller
-// on the main stream at the point after which `out` is free to be overwritten).
-int cf_launch_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w, const cf_exchange_fields* out) {
-    cf_ctx::Prefetch* rec = ctx->prefetch_slot(out->u);
-    // (never taken: request_prefetch refuses a request that would find no record, before anything is launched or booked)
-    if (!rec) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
-    if (!ctx->deferred.gated) HIP_TRY(ctx, hipEventRecord(ctx->aux.ev_gate.get(), ctx->stream));  // (a later gate than needed: still ordered)
-    ctx->deferred.gated = false;
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux.stream.get(), ctx->aux.ev_gate.get(), 0));
-    // the LDS-free gather kernel (≤ 56 VGPRs, no LDS): it is resident BESIDE the solver's workgroups, which fill
-    // the CU's LDS and 456 of 512 registers per SIMD; the tiled kernel would wait for them to retire
-    HIP_TRY(ctx, launch_interpolate_background(ctx->aux.stream.get(), ctx->grid, src, w, out));
-    HIP_TRY(ctx, hipEventRecord(rec->done, ctx->aux.stream.get()));
-    ++ctx->prefetch_stats.launched_aux;
-    rec->key = out->u;
-    rec->src = *src;
-    rec->w = *w;
-    rec->valid = true;
-    rec->on_main = false;
+// Queues what a transition of the ledger answered with, in Work's order.  A request that leaves on the auxiliary stream is
+// gated on the lane's gate event (recorded on the main stream at the point after which its set is free to be overwritten).
+int cf_ahead_perform(cf_ctx* ctx, const AheadLedger::Work* work) {
+    if (const int k = work->launch_aux; k >= 0) {
+        const AheadLedger::Record& r = work->launched;
+        if (work->gate_late) HIP_TRY(ctx, hipEventRecord(ctx->aux.ev_gate.get(), ctx->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux.stream.get(), ctx->aux.ev_gate.get(), 0));
+        // the LDS-free gather kernel (≤ 56 VGPRs, no LDS): it is resident BESIDE the solver's workgroups, which fill
+        // the CU's LDS and 456 of 512 registers per SIMD; the tiled kernel would wait for them to retire
+        HIP_TRY(ctx, launch_interpolate_background(ctx->aux.stream.get(), ctx->grid, &r.src, &r.w, &r.out));
+        HIP_TRY(ctx, hipEventRecord(ctx->aux.done[k].get(), ctx->aux.stream.get()));
+    }
+    for (int k = 0; k < 2; ++k)
+        if (work->wait_done >> k & 1) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux.done[k].get(), 0));
+    if (work->gate_now) HIP_TRY(ctx, hipEventRecord(ctx->aux.ev_gate.get(), ctx->stream));
     return CF_OK;
 }
 
-// A deferred request goes out now (cf_update_state calls this right after its solver launch; cf_sync and a second
-// request flush it).  The gate event was recorded when the request was made.
-int cf_flush_deferred_prefetch(cf_ctx* ctx) {
-    if (!ctx->deferred.valid) return CF_OK;
-    ctx->deferred.valid = false;
-    return cf_launch_prefetch(ctx, &ctx->deferred.src, &ctx->deferred.w, &ctx->deferred.out);
-}
-
-static int request_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
-                            const cf_exchange_fields* out, bool defer);
-
-// An earlier state of the exchange set `key` that no step asked for (another clock, a switch of CF_OPT_MERGED_PREFETCH in
-// between): a new request into that set supersedes it, now — the set never has two states on the books.  One that went out on
-// the auxiliary stream: whichever stream writes the set next — the main stream in the merged forms — is ordered behind that
-// kernel.  One that went out on the main stream: stream order and the new request's gate are the order.
-static int supersede_states(cf_ctx* ctx, const double* key) {
-    for (auto& p : ctx->prefetch)
-        if (p.valid && p.key == key) {
-            if (!p.on_main && p.done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p.done, 0));
-            p.valid = false;
-            ++ctx->prefetch_stats.superseded;
-        }
+// Books a request and queues what that implies; *rec: its record.  defer: it waits for the next solver launch
+static int book_request(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w, const cf_exchange_fields* out, bool defer,
+                        const AheadLedger::Record** rec = nullptr) {
+    const AheadLedger::Booked B = ctx->ahead.request(*src, *w, *out, ctx->merged_prefetch, defer);
+    CHECK(cf_ahead_perform(ctx, &B.work));
+    if (!B.rec) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
+    if (rec) *rec = B.rec;
     return CF_OK;
 }
 
-extern "C" {
-
-int cf_prefetch_atmosphere_state(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
-                                 const cf_exchange_fields* out) {
-    return request_prefetch(ctx, src, w, out, true);
-}
-
-}  // extern "C"
-
+// cf_prefetch_atmosphere_state (defer) and a request that leaves on the auxiliary stream at once
 static int request_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
                             const cf_exchange_fields* out, bool defer) {
     if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
@@ -95,24 +67,20 @@ static int request_prefetch(cf_ctx* ctx, const cf_atmos_source* src, const cf_in
                     src->n_levels);
     CHECK(ensure_aux_stream(ctx));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    CHECK(cf_flush_deferred_prefetch(ctx));  // at most one request waits for a solver launch
-    // two states of OTHER sets are pending: there is no record for this one.  Refused here, where nothing has been launched or
-    // booked for it — not behind the launch that would carry it, whose writes would then be on nobody's books
-    if (!ctx->prefetch_slot(out->u)) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
-    CHECK(supersede_states(ctx, out->u));
-    ++ctx->prefetch_stats.requests;
-    // the set written was last read by kernels already queued on the main stream: everything queued so far gates it.
-    // With CF_OPT_MERGED_PREFETCH the request leaves inside a main-stream launch (stream order is the gate) and an event
-    // per step would only put a barrier packet into the queue; the rare flush to the auxiliary stream records it then.
-    ctx->deferred.gated = !(defer && ctx->merged_prefetch != 0);
-    if (ctx->deferred.gated) HIP_TRY(ctx, hipEventRecord(ctx->aux.ev_gate.get(), ctx->stream));
-    if (!defer) return cf_launch_prefetch(ctx, src, w, out);
-    ctx->deferred.src = *src;
-    ctx->deferred.w = *w;
-    ctx->deferred.out = *out;
-    ctx->deferred.valid = true;
-    return CF_OK;
+    CHECK(book_request(ctx, src, w, out, defer));
+    if (defer) return CF_OK;
+    const AheadLedger::Work now = ctx->ahead.leave_aux();
+    return cf_ahead_perform(ctx, &now);
 }
+
+extern "C" {
+
+int cf_prefetch_atmosphere_state(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
+                                 const cf_exchange_fields* out) {
+    return request_prefetch(ctx, src, w, out, true);
+}
+
+}  // extern "C"
 
 // cf_destroy: the mailbox of a context that goes away must not be handed to a later cf_peer_halo_connect of this process
 void cf_peer_forget_local(const char* mailbox) {
@@ -273,16 +241,10 @@ int cf_fold_north_halo(cf_ctx* ctx, double* const* d_fields, const int* location
 int cf_discard_prefetched_atmosphere_state(cf_ctx* ctx) {
     if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->deferred.valid) ++ctx->prefetch_stats.discarded;
-    ctx->deferred.valid = false;   // requested, not launched: never will be
-    for (auto& p : ctx->prefetch)
-        if (p.valid) {
-            // launched on the auxiliary stream: whatever the caller does to that exchange set next is ordered behind it
-            if (!p.on_main && p.done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p.done, 0));
-            p.valid = false;
-            ++ctx->prefetch_stats.discarded;
-        }
-    return CF_OK;
+    // requested, not launched: never will be.  Launched on the auxiliary stream: whatever the caller does to that exchange set
+    // next is ordered behind it
+    const AheadLedger::Work W = ctx->ahead.discard();
+    return cf_ahead_perform(ctx, &W);
 }
 
 // ---- run!(simulation) -------------------------------------------------------------------------
@@ -461,29 +423,18 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
     if (S->pipeline && nsteps > 0) {  // the first step's atmosphere, unless a previous call already started it
         const cf_atmos_source s0 = source_at(first_step);
         const cf_exchange_fields* a0 = &S->atmos[first_step % 2];
-        bool pending = false;
-        for (auto& p : ctx->prefetch) pending |= p.valid && p.key == a0->u && same_interpolation(p.src, p.w, s0, *w);
-        if (!pending && ctx->deferred.valid && ctx->deferred.out.u == a0->u) {
-            pending = same_interpolation(ctx->deferred.src, ctx->deferred.w, s0, *w);
-            if (pending) CHECK(cf_flush_deferred_prefetch(ctx));
-        }
-        if (!pending) {
-            if (ctx->merged_prefetch != 0) {
-                // the merged forms keep everything on the context's stream: so does the first step's interpolation
-                CHECK(cf_flush_deferred_prefetch(ctx));
-                if (!ctx->prefetch_slot(a0->u)) return fail(ctx, CF_ERR_INVALID, "two prefetched atmosphere states are already pending");
-                // a state of this set that is not the one this step asks for — and may have left on the auxiliary stream, under
-                // CF_OPT_MERGED_PREFETCH = 0 before a switch or by the flush above: the launch below is ordered behind it
-                CHECK(supersede_states(ctx, a0->u));
-                HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &s0, w, a0));
-                ++ctx->prefetch_stats.requests;
-                ctx->deferred.src = s0;
-                ctx->deferred.w = *w;
-                ctx->deferred.out = *a0;
-                CHECK(deferred_went_out_on_main(ctx, &ctx->prefetch_stats.launched_own));
-            } else {
-                CHECK(request_prefetch(ctx, &s0, w, a0, false));
-            }
+        const AheadLedger::FirstStep F = ctx->ahead.first_step_of_call(a0->u, s0, *w);
+        CHECK(cf_ahead_perform(ctx, &F.work));
+        if (F.needed && ctx->merged_prefetch != 0) {
+            // the merged forms keep everything on the context's stream: so does the first step's interpolation.  (A state of
+            // this set that is not the one this step asks for may have left on the auxiliary stream — under
+            // CF_OPT_MERGED_PREFETCH = 0 before a switch, or sent off by this very request: the launch is ordered behind it)
+            const AheadLedger::Record* rec;
+            CHECK(book_request(ctx, &s0, w, a0, true, &rec));
+            HIP_TRY(ctx, launch_interpolate(ctx->stream, ctx->launch, ctx->grid, &s0, w, a0));
+            ctx->ahead.leave_main(rec, AheadLedger::OWN);
+        } else if (F.needed) {
+            CHECK(request_prefetch(ctx, &s0, w, a0, false));
         }
     }
     // CF_OPT_LAND_ZEROS: the steps below are one loop over fixed outputs, one mask pointer and one chunk table (checked above) —

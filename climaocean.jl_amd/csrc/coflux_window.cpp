@@ -85,16 +85,9 @@ int cf_window_commit(cf_window* w, int32_t slot, int64_t time_index) {
     // An interpolation requested AHEAD that reads this slot (cf_prefetch_atmosphere_state, cf_time_steps with
     // CF_PIPELINE_CONTINUING) was computed — or would be — from the snapshot this commit replaces: it is void.  The step it
     // was meant for then interpolates again, from the window's current contents.
-    for (auto& p : ctx->prefetch)
-        if (p.valid && (p.src.level1 == slot || p.src.level2 == slot)) {
-            if (!p.on_main && p.done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p.done, 0));  // its writes must not race the redo
-            p.valid = false;
-            ++ctx->prefetch_stats.voided;
-        }
-    if (ctx->deferred.valid && (ctx->deferred.src.level1 == slot || ctx->deferred.src.level2 == slot)) {
-        ctx->deferred.valid = false;
-        ++ctx->prefetch_stats.voided;
-    }
+    // One that left on the auxiliary stream: its writes must not race the redo.
+    const AheadLedger::Work voided = ctx->ahead.commit_slot(slot);
+    CHECK(cf_ahead_perform(ctx, &voided));
     // the device copy of this slot may only be overwritten once every interpolation already queued has read it
     HIP_TRY(ctx, hipEventRecord(w->ev_compute.get(), ctx->stream));
     HIP_TRY(ctx, hipStreamWaitEvent(w->copy_stream.get(), w->ev_compute.get(), 0));
