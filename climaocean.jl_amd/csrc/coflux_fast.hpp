@@ -126,7 +126,8 @@ struct PsiArg {
 };
 
 // No logarithm: the table is indexed by the floating-point representation of x itself (two tiers, coflux_tables.h).
-// |ζ| > 1e9 (never a converged state) and NaN are evaluated at the table edge.
+// |ζ| > 1e9 and NaN are evaluated at the table edge: never a state an ocean solve stops on.  The sea-ice interface solve
+// does stop there (psi_beyond_tables below).
 __device__ __forceinline__ PsiArg psi_arg_x(double x_unclamped, bool unstable) {
     PsiArg a;
     static_assert(PSI_BINADES == 34, "the clamp below is the largest double under 2^PSI_BINADES");
@@ -147,6 +148,22 @@ __device__ __forceinline__ PsiArg psi_arg_x(double x_unclamped, bool unstable) {
 }
 __device__ __forceinline__ PsiArg psi_arg(double zeta) {
     return psi_arg_x(__builtin_fma(PSI_A, fabs(zeta), 1.0), zeta < 0.0);
+}
+
+// Beyond the tables, x = 1 + PSI_A |ζ| ≥ 2^PSI_BINADES.  Calm air over thick cold ice: the interface solve converges on
+// u★ ≈ 3e-6 m/s, where ζ = h κ b★ / u★² is 1e9 … 6e9, and its collapsed cells lie further out still.  There its two bodies
+// take (ψ_m, ψ_h)(h / L) from the closed forms of coflux_device.hpp — in a SECOND pass (template flag BEYOND) that the
+// launch runs only on the lanes whose first pass left the tables on some trip (`left_tables`), from the same start.  The first
+// pass is the iteration as it always was, plus one sticky flag: a call inside it costs the sea-ice step a tenth of its time
+// (spills around the call site in a loop that sits at its register bound), and a lane inside the tables keeps its bits.
+constexpr double PSI_X_EDGE = 0x1p34;
+static_assert(PSI_BINADES == 34, "PSI_X_EDGE is 2^PSI_BINADES");
+static __device__ __noinline__ double2 psi_beyond_tables(int stability, double zeta) {
+    if (stability == CF_STABILITY_EDSON2013)
+        return make_double2(psi_momentum<CF_STABILITY_EDSON2013>(zeta), psi_scalar<CF_STABILITY_EDSON2013>(zeta));
+    if (stability == CF_STABILITY_SHEBA)
+        return make_double2(psi_momentum<CF_STABILITY_SHEBA>(zeta), psi_scalar<CF_STABILITY_SHEBA>(zeta));
+    return make_double2(psi_momentum<CF_STABILITY_LARGE_YEAGER>(zeta), psi_scalar<CF_STABILITY_LARGE_YEAGER>(zeta));
 }
 
 // fn: 0 = ψ_m, 1 = ψ_h.  Table layout: [side][coefficient][segment]{ψ_m, ψ_h} (coflux_tables.cpp).
@@ -643,9 +660,9 @@ __device__ __forceinline__ double svp_ice_fast(const DevParams& P, const double*
     return svp_ice_from(P, svp_arg(P, logt, T, inv_T));
 }
 
-template <bool COARE, bool LIN>  // LIN: CF_SKIN_LINEARISED (I.skin_scheme = 2); otherwise I.skin_scheme picks explicit / semi-implicit
+template <bool COARE, bool LIN, bool BEYOND = false>  // LIN: CF_SKIN_LINEARISED (I.skin_scheme = 2); otherwise I.skin_scheme picks explicit / semi-implicit
 __device__ __forceinline__ Scales ice_iterate(const DevParams& P, const LoopParams& L, const IceParams& I,
-                                              const IceConsts& c, const double* tab, bool active, double& Ts) {
+                                              const IceConsts& c, const double* tab, bool active, double& Ts, bool& left_tables) {
     const double* logt = tab + LOG_OFFSET;
     double us = 1e-4, ts = 1e-4, qq = 1e-4, drift = 0.0;
     int it = 0;
@@ -725,7 +742,12 @@ __device__ __forceinline__ Scales ice_iterate(const DevParams& P, const LoopPara
                                                               lu, us, frcp(air_viscosity(P.rt, Ts)));
 
             const double inv_L = (bstar == 0.0) ? 0.0 : (L.kappa * bstar) * (inv_us * inv_us);
-            const double2 psi_h2 = psi_eval_pair(tab, psi_arg(L.h_ref * inv_L));
+            const double zeta_h = L.h_ref * inv_L;
+            double2 psi_h2 = psi_eval_pair(tab, psi_arg(zeta_h));
+            if (__builtin_fma(PSI_A, fabs(zeta_h), 1.0) >= PSI_X_EDGE) {
+                if constexpr (BEYOND) psi_h2 = psi_beyond_tables(P.stability, zeta_h);
+                else left_tables = true;
+            }
             double Du = L.log_h - log_lu - psi_h2.x;
             double Dq = L.log_h - log_lq - psi_h2.y;
             double Dt = L.log_h - log_lt - psi_h2.y;

@@ -384,9 +384,9 @@ struct LeanIceConsts {
     double rho, cp, qav, Ls, Ti, hk, Qd, theta_a, pa, inv_pa, inv_rho_Rv, dU2;
 };
 
-template <bool COARE, bool LIN>  // LIN: CF_SKIN_LINEARISED (see ice_iterate)
+template <bool COARE, bool LIN, bool BEYOND = false>  // LIN: CF_SKIN_LINEARISED; BEYOND: the second pass (see ice_iterate, psi_beyond_tables)
 __device__ __forceinline__ Scales ice_iterate_lean(const DevParams& P, const LoopParams& L, const IceParams& I, const LeanIceConsts& c,
-                                                   const double* tab, bool active, double& Ts) {
+                                                   const double* tab, bool active, double& Ts, bool& left_tables) {
     const double* logt = tab + LOG_OFFSET;
     double us = 1e-4, ius = 1e4, ts = 1e-4, qq = 1e-4, drift = __builtin_inf();
     int it = 0, work = 0;
@@ -457,7 +457,12 @@ __device__ __forceinline__ Scales ice_iterate_lean(const DevParams& P, const Loo
             } else {
                 sqrt_rsqrt_lean(c.dU2 + L.min_gust2, U, rU);
             }
-            const double2 ps = psi_eval_pair(tab, psi_arg_x(__builtin_fma(L.x_scale, fabs(inv_L), 1.0), kb < 0.0));
+            const double xh = __builtin_fma(L.x_scale, fabs(inv_L), 1.0);
+            double2 ps = psi_eval_pair(tab, psi_arg_x(xh, kb < 0.0));
+            if (xh >= PSI_X_EDGE) {   // (see psi_beyond_tables)
+                if constexpr (BEYOND) ps = psi_beyond_tables(P.stability, L.h_ref * inv_L);
+                else left_tables = true;
+            }
             double Du = lgu - ps.x, Dq = lgq - ps.y, Dt = lgt - ps.y;
             if constexpr (!COARE) {
                 const double zu = lu * inv_L, zq = lq * inv_L, zt = lt * inv_L;

@@ -333,6 +333,13 @@ __device__ __forceinline__ void ice_zero_net(SolverArgsPtr K, const GridDesc& G,
     }
 }
 
+// the carried skin temperature of a list entry's cell, read again (the second pass of the interface solve, below)
+__device__ __forceinline__ double ice_carried_skin(SolverArgsPtr K, const GridDesc& G, int range_begin, unsigned entry, int wx, unsigned wx_rcp) {
+    const int idx = range_begin + (int)(entry & ((1u << AO_LIST_OFFSET_BITS) - 1u));
+    const int jj = row_of(idx, wx, wx_rcp);
+    return kread(&K->S).top_temperature[cell_index(G, idx - jj * wx - G.ring, jj - G.ring)];
+}
+
 // (a device routine: the kernel below, and ice_ocean_kernel, where the ocean solver's workgroups ride behind these)
 template <bool COARE, int SPEC, bool FUSE_NET, bool TAIL = false>
 __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int block) {
@@ -705,11 +712,24 @@ __device__ __forceinline__ void ao_flux_fast_body(SolverArgsPtr K_in, const int 
                 Scales s{0.0, 0.0, 0.0, 0, 0};
                 const bool solve = in_range && !ice_free;
                 if (__ballot(solve) != 0ull) {  // (a batch of open water — most of the surface — skips the solve altogether)
+                    // a lane whose h / L left the ψ tables on some trip (calm air over cold ice) is solved again from the same start
+                    // with ψ from the closed forms out there (psi_beyond_tables); the carried skin is read again, not kept
+                    bool left = false, unused = false;
                     if constexpr (seaice_lean_spec(SPEC)) {
                         const LeanIceConsts lc{c.rho, c.cp, c.qav, c.Ls, c.Ti, c.hk, c.Qd, c.theta_a, c.pa, frcp1(c.pa), frcp1(c.rho * P.R_v), c.dU2};
-                        s = ice_iterate_lean<COARE, seaice_lin_spec(SPEC)>(P, L, Ice, lc, tab, solve, Ts);
+                        s = ice_iterate_lean<COARE, seaice_lin_spec(SPEC)>(P, L, Ice, lc, tab, solve, Ts, left);
+                        if (__ballot(left) != 0ull) {
+                            double Ts2 = ice_carried_skin(opaque(K), G, range_begin, list[qc], wx, wx_rcp) + Ice.T_offset;
+                            const Scales s2 = ice_iterate_lean<COARE, seaice_lin_spec(SPEC), true>(P, L, Ice, lc, tab, left, Ts2, unused);
+                            if (left) { s = s2; Ts = Ts2; }
+                        }
                     } else {
-                        s = ice_iterate<COARE, seaice_lin_spec(SPEC)>(P, L, Ice, c, tab, solve, Ts);
+                        s = ice_iterate<COARE, seaice_lin_spec(SPEC)>(P, L, Ice, c, tab, solve, Ts, left);
+                        if (__ballot(left) != 0ull) {
+                            double Ts2 = ice_carried_skin(opaque(K), G, range_begin, list[qc], wx, wx_rcp) + Ice.T_offset;
+                            const Scales s2 = ice_iterate<COARE, seaice_lin_spec(SPEC), true>(P, L, Ice, c, tab, left, Ts2, unused);
+                            if (left) { s = s2; Ts = Ts2; }
+                        }
                     }
                 }
                 if (ice_free) s = Scales{0.0, 0.0, 0.0, 0, 0};  // zero_interface_state: no fluxes; the skin temperature stays the input

@@ -174,26 +174,28 @@ def table(current="rest", nonfinite=True):
     return cols
 
 
-def layout(kind, shift=0):
+def layout(kind, shift=0, a=None):
     """(nx, ny, ids): `ids` an int [wy, wx] array over the ring-inclusive window, row-major = the solver's index order,
     the atlas entry each window cell carries.  "cyclic": cell n carries entry n mod A on the mask atlas' base shape (about
     four copies, each in another lane, batch and chunk).  "blocks": entry (n // 64) mod A — every aligned run of 64 cells,
     a whole wave, is one entry; the window is the smallest 323-wide one that holds 64 · A cells.  `shift` moves every entry
-    that many places on (the second state of a stepped run)."""
+    that many places on (the second state of a stepped run).  `a`: the length of another atlas that shares the layouts
+    (tests/interface_atlas.py); this one's by default."""
+    a = A if a is None else a
     if kind == "cyclic":
         nx, ny = ma.SHAPES["base"]
     else:
         assert kind == "blocks"
         nx = 321
-        ny = -(-64 * A // (nx + 2 * RING)) - 2 * RING
+        ny = -(-64 * a // (nx + 2 * RING)) - 2 * RING
     wx, wy = ma.window_shape(nx, ny, RING)
     n = np.arange(wx * wy).reshape(wy, wx)
-    return nx, ny, ((n if kind == "cyclic" else n // 64) + shift) % A
+    return nx, ny, ((n if kind == "cyclic" else n // 64) + shift) % a
 
 
-def land_mask(kind, variant="checkerboard"):
+def land_mask(kind, variant="checkerboard", a=None):
     """The window's wet cells of a layout's land variant (a mask atlas mask) and its halo-inclusive uint8 array."""
-    nx, ny, ids = layout(kind)
+    nx, ny, ids = layout(kind, a=a)
     (_, wet), = ma.atlas(ids.shape[1], ids.shape[0], only=(variant,))
     return wet, ma.embed(wet, nx, ny)
 
@@ -238,11 +240,11 @@ def through_float32(atmos):
     return {k: v.astype(np.float32).astype(np.float64) for k, v in atmos.items()}
 
 
-def copies(ids, wet=None):
+def copies(ids, wet=None, a=None):
     """(order, starts): window cells (flat indices, wet ones only) sorted by the entry they carry, and where each entry's
     run starts — np.split(order, starts[1:]) lists every entry's copies."""
     flat = ids.reshape(-1)
     cells = np.arange(flat.size) if wet is None else np.flatnonzero(wet.reshape(-1))
     order = cells[np.argsort(flat[cells], kind="stable")]
-    starts = np.searchsorted(flat[order], np.arange(A))
+    starts = np.searchsorted(flat[order], np.arange(A if a is None else a))
     return order, starts
