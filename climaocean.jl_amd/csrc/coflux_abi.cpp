@@ -858,6 +858,9 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
                              bool hold_tail_work, bool* stress_held, OceanRider* ocean_rider = nullptr) {
     if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));  // one process may drive several contexts / devices
+    // the halo request of the enclosing cf_time_steps iteration is taken here, before anything can refuse: whichever way this
+    // call ends, the context holds none (a request is never carried to another call)
+    const cf_ctx::HaloRequest halo_request = std::exchange(ctx->halo_request, cf_ctx::HaloRequest{});
     CHECK(check_source(ctx, src));
     CHECK(check_weights(ctx, w));
     CHECK(check_ocean(ctx, ocean));
@@ -895,26 +898,22 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     // stepping loop's exact-path launch with tail workgroups, else the exchange kernel of its own, now, in front of the solver
     HaloRider halo_rider{};
     const HaloRider* halo = nullptr;
-    if (ctx->halo_request.valid) {
-        ctx->halo_request.valid = false;
+    if (halo_request.valid) {
         if (tail && tail_lean && !ride && ctx->d_halo_counters && lean_halo_rides(ctx->launch, ctx->fast)) {
+            // the sequence number and the riders' targets are worked out into the rider; the context takes them over once the
+            // launch that carries them is queued (below)
             HaloRider& H = halo_rider;
             H.M = ctx->peer;
-            H.F = ctx->halo_request.F;
+            H.F = halo_request.F;
             H.counters = ctx->d_halo_counters.get();
-            H.seq = ++ctx->peer_seq;
-            ++ctx->halo_in_launch_count;
-            for (int dir = 0; dir < 2; ++dir)
-                if ((dir == 0 ? ctx->peer.south : ctx->peer.north) != nullptr) {
-                    ctx->halo_expect_sent[dir] += (unsigned long long)H.F.n;
-                    ctx->halo_expect_done[dir] += (unsigned long long)H.F.n;
-                }
+            H.seq = ctx->peer_seq + 1;
             for (int dir = 0; dir < 2; ++dir) {
-                H.expect_sent[dir] = ctx->halo_expect_sent[dir];
-                H.expect_done[dir] = ctx->halo_expect_done[dir];
+                const bool neighbour = (dir == 0 ? ctx->peer.south : ctx->peer.north) != nullptr;
+                H.expect_sent[dir] = ctx->halo_expect_sent[dir] + (neighbour ? (unsigned long long)H.F.n : 0ull);
+                H.expect_done[dir] = ctx->halo_expect_done[dir] + (neighbour ? (unsigned long long)H.F.n : 0ull);
             }
             H.status = ctx->d_peer_status.get();
-            H.rows = ctx->halo_request.rows;
+            H.rows = halo_request.rows;
             H.blocks = 2 * H.F.n;
             H.chunk_south = ctx->launch.chunk_south;
             H.chunk_north = ctx->launch.chunk_north;
@@ -922,7 +921,7 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
             H.wait_north = ctx->peer.north != nullptr;
             halo = &halo_rider;
         } else {
-            CHECK(cf_peer_halo_launch_now(ctx, &ctx->halo_request.F, ctx->halo_request.rows));
+            CHECK(cf_peer_halo_launch_now(ctx, &halo_request.F, halo_request.rows));
         }
     }
     // CF_OPT_LAND_ZEROS: whether this step's solver and face-stress launches leave the land cells alone.  Automatic: only a step
@@ -941,10 +940,18 @@ static int update_state_impl(cf_ctx* ctx, const cf_atmos_source* src, const cf_i
     } else if (tail) {
         int rows = 4, blocks = 1;
         interpolate_grid(L, ctx->grid, &rows, &blocks);
-        if (tail_lean)
+        if (tail_lean) {
             HIP_TRY(ctx, launch_ao_fluxes_lean(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
                                                ctx->d_land_freshwater, &next->src, &next->w, &next->out, rows, blocks, halo));
-        else
+            if (halo) {   // the riders are queued: this exchange counts (a launch that failed is none, on any rank's books)
+                ctx->peer_seq = halo->seq;
+                ++ctx->halo_in_launch_count;
+                for (int dir = 0; dir < 2; ++dir) {
+                    ctx->halo_expect_sent[dir] = halo->expect_sent[dir];
+                    ctx->halo_expect_done[dir] = halo->expect_done[dir];
+                }
+            }
+        } else
             HIP_TRY(ctx, launch_ly_fluxes_with_tail(ctx->stream, L, ctx->dev, ctx->fast, ctx->grid, ocean, atmos, fluxes, ice, net,
                                                     ctx->d_land_freshwater, &next->src, &next->w, &next->out, rows, blocks));
         ctx->ahead.leave_main(next, AheadLedger::TAIL);
@@ -1505,10 +1512,10 @@ int cf_prepare_coupled_step(cf_ctx* ctx, const cf_coupled_prepare* p) {
     return CF_OK;
 }
 
-// cf_time_steps_coupled (coflux_steps.cpp): the NULL checks cf_update_state_sea_ice would make at the first step, made before
-// the first launch of the loop
-int check_coupled_update(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w, const cf_run_schedule* S,
-                         const cf_interface_fluxes* fluxes, const cf_net_ocean_fluxes* net, const cf_interface_fluxes* ai_fluxes) {
+// cf_time_steps (coflux_steps.cpp): the checks cf_update_state would make at any step of the schedule — every ocean state, every
+// exchange set —, in its order, made before the first launch of the loop
+int check_step_arguments(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w, const cf_run_schedule* S,
+                         const cf_interface_fluxes* fluxes, const cf_net_ocean_fluxes* net) {
     cf_atmos_source s0 = *src;   // (the levels are the loop's own: the clock was checked)
     s0.level1 = s0.level2 = 0;
     CHECK(check_source(ctx, &s0));
@@ -1517,6 +1524,13 @@ int check_coupled_update(cf_ctx* ctx, const cf_atmos_source* src, const cf_inter
     for (int n = 0; n < S->n_atmos_sets; ++n) CHECK(check_exchange(ctx, &S->atmos[n], true));
     CHECK(check_fluxes(ctx, fluxes));
     CHECK(check_net(ctx, net, w));
+    return CF_OK;
+}
+
+// cf_time_steps_coupled (coflux_steps.cpp): the same with the NULL checks cf_update_state_sea_ice would add
+int check_coupled_update(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w, const cf_run_schedule* S,
+                         const cf_interface_fluxes* fluxes, const cf_net_ocean_fluxes* net, const cf_interface_fluxes* ai_fluxes) {
+    CHECK(check_step_arguments(ctx, src, w, S, fluxes, net));
     if (check_fluxes(ctx, ai_fluxes) != CF_OK) return fail(ctx, CF_ERR_INVALID, "cf_time_steps_coupled: ai_fluxes fields are NULL");
     return CF_OK;
 }

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <variant>
 #include <vector>
 
@@ -231,6 +232,17 @@ struct LandZeroScope {
     LandZeroScope& operator=(const LandZeroScope&) = delete;
 };
 
+// One cf_time_steps / cf_time_steps_coupled call as CF_OPT_HALO_IN_SOLVER_LAUNCH sees it: a step's halo request is consumed by the
+// cf_update_state of its own iteration or dropped here — a call that fails between the two must not leave it, with the
+// caller's pointers, to the next cf_update_state on the context
+struct HaloRequestScope {
+    cf_ctx* ctx;
+    explicit HaloRequestScope(cf_ctx* c) : ctx(c) { ctx->halo_request = cf_ctx::HaloRequest{}; }
+    ~HaloRequestScope() { ctx->halo_request = cf_ctx::HaloRequest{}; }
+    HaloRequestScope(const HaloRequestScope&) = delete;
+    HaloRequestScope& operator=(const HaloRequestScope&) = delete;
+};
+
 // time averages: what cf_average_create (coflux_average.cpp), cf_average_create_derived (coflux_derived.cpp) and
 // cf_average_create_budget (coflux_budget.cpp) hand back differs in the arguments of a collection's launch only
 struct PlainAverageArgs {
@@ -306,9 +318,13 @@ extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_
 int checkpoint_settle_restores(cf_ctx* ctx);
 // coflux_steps.cpp: queues what a transition of ctx->ahead answered with (AheadLedger::Work)
 extern "C" __attribute__((visibility("hidden"))) int cf_ahead_perform(cf_ctx* ctx, const AheadLedger::Work* work);
-// coflux_abi.cpp: the argument checks of cf_prepare_coupled_step and of the cf_update_state_sea_ice of a coupled step loop,
-// without their launches (cf_time_steps_coupled validates a whole call before its first launch)
+// coflux_abi.cpp: the argument checks of cf_prepare_coupled_step, of the cf_update_state of every step of a schedule and of the
+// cf_update_state_sea_ice of a coupled step loop, without their launches (cf_time_steps and cf_time_steps_coupled validate a
+// whole call before its first launch)
 extern "C" __attribute__((visibility("hidden"))) int check_coupled_prepare(cf_ctx* ctx, const cf_coupled_prepare* p);
+extern "C" __attribute__((visibility("hidden"))) int check_step_arguments(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
+                                                                          const cf_run_schedule* S, const cf_interface_fluxes* fluxes,
+                                                                          const cf_net_ocean_fluxes* net);
 extern "C" __attribute__((visibility("hidden"))) int check_coupled_update(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
                                                                           const cf_run_schedule* S, const cf_interface_fluxes* fluxes,
                                                                           const cf_net_ocean_fluxes* net, const cf_interface_fluxes* ai_fluxes);

@@ -186,13 +186,19 @@ int cf_peer_halo_connect(cf_ctx* ctx, const void* south_handle, const void* nort
     return CF_OK;
 }
 
+// what a peer-direct exchange of `nfields` × `rows` needs of the context (cf_halo_exchange_rows_peer, and cf_time_steps for all
+// of its steps before the first of them)
+static int check_peer_rows(cf_ctx* ctx, int nfields, int rows) {
+    if (!ctx->peer_connected) return fail(ctx, CF_ERR_COMM, "cf_peer_halo_connect has not been called");
+    if (nfields > ctx->peer_max_fields || rows < 1 || rows > ctx->peer_max_rows || rows > ctx->grid.ny)
+        return fail(ctx, CF_ERR_INVALID, "cf_halo_exchange_rows_peer: %d fields / %d rows exceed the mailbox (%d / %d) or ny = %d",
+                    nfields, rows, ctx->peer_max_fields, ctx->peer_max_rows, ctx->grid.ny);
+    return CF_OK;
+}
+
 int cf_halo_exchange_rows_peer(cf_ctx* ctx, double* const* d_fields, int nfields, int rows) {
     if (!ctx || !d_fields || nfields <= 0) return fail(ctx, CF_ERR_INVALID, "cf_halo_exchange_rows_peer: bad arguments");
-    if (!ctx->peer_connected) return fail(ctx, CF_ERR_COMM, "cf_peer_halo_connect has not been called");
-    const GridDesc& G = ctx->grid;
-    if (nfields > ctx->peer_max_fields || rows < 1 || rows > ctx->peer_max_rows || rows > G.ny)
-        return fail(ctx, CF_ERR_INVALID, "cf_halo_exchange_rows_peer: %d fields / %d rows exceed the mailbox (%d / %d) or ny = %d",
-                    nfields, rows, ctx->peer_max_fields, ctx->peer_max_rows, G.ny);
+    CHECK(check_peer_rows(ctx, nfields, rows));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     PeerFields F{};
     F.n = nfields;
@@ -204,8 +210,10 @@ int cf_halo_exchange_rows_peer(cf_ctx* ctx, double* const* d_fields, int nfields
 }
 
 int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows) {
-    ++ctx->peer_seq;  // every rank counts its exchanges: the same number names the same step everywhere
-    HIP_TRY(ctx, launch_peer_halo(ctx->stream, ctx->peer, *F, ctx->grid, rows, ctx->peer_seq, ctx->d_peer_status.get()));
+    // every rank counts its exchanges: the same number names the same step everywhere — counted once the kernel is queued (a
+    // launch that failed is no exchange: this rank's sequence and mailbox parity would run ahead of its neighbours')
+    HIP_TRY(ctx, launch_peer_halo(ctx->stream, ctx->peer, *F, ctx->grid, rows, ctx->peer_seq + 1, ctx->d_peer_status.get()));
+    ++ctx->peer_seq;
     return CF_OK;
 }
 
@@ -216,14 +224,21 @@ int cf_peer_halo_stats(cf_ctx* ctx, unsigned long long* exchanges, unsigned long
     return CF_OK;
 }
 
+// what the fold of `rows` rows needs of the grid (cf_fold_north_halo, and cf_time_steps with fold_north before its first step)
+static int check_fold_geometry(cf_ctx* ctx, int rows) {
+    const GridDesc& G = ctx->grid;
+    if (rows < 1 || rows > G.hy || rows + 1 > G.ny)
+        return fail(ctx, CF_ERR_INVALID, "cf_fold_north_halo: rows = %d outside [1, min(hy, ny − 1)]", rows);
+    if (G.nx % 2) return fail(ctx, CF_ERR_INVALID, "cf_fold_north_halo: a tripolar grid has an even number of columns (nx = %d)", G.nx);
+    return CF_OK;
+}
+
 int cf_fold_north_halo(cf_ctx* ctx, double* const* d_fields, const int* locations, const double* signs, int nfields,
                        int rows) {
     if (!ctx || !d_fields || !locations || !signs || nfields <= 0 || nfields > PEER_MAX_FIELDS)
         return fail(ctx, CF_ERR_INVALID, "cf_fold_north_halo: bad arguments (1…%d fields)", PEER_MAX_FIELDS);
     const GridDesc& G = ctx->grid;
-    if (rows < 1 || rows > G.hy || rows + 1 > G.ny)
-        return fail(ctx, CF_ERR_INVALID, "cf_fold_north_halo: rows = %d outside [1, min(hy, ny − 1)]", rows);
-    if (G.nx % 2) return fail(ctx, CF_ERR_INVALID, "cf_fold_north_halo: a tripolar grid has an even number of columns (nx = %d)", G.nx);
+    CHECK(check_fold_geometry(ctx, rows));
     FoldFields F{};
     F.n = nfields;
     for (int f = 0; f < nfields; ++f) {
@@ -416,8 +431,19 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
         if (S->ocean_states[n].mask != S->ocean_states[0].mask)
             return fail(ctx, CF_ERR_INVALID, "%s: ocean state %d carries a different mask pointer than state 0; the states of a "
                         "schedule share one wet mask", name, n);
-        if (n == 0) CHECK(cf_ensure_chunk_table(ctx, S->ocean_states[n].mask));
     }
+    // cf_time_steps: everything one of its steps would refuse, at whichever step, is refused here — before the first launch and
+    // before anything of the context changes (the chunk table, the ledger of requested states, the halo request, the land-zero
+    // scope), as check_coupled_block does for the coupled form.  Behind the attachments: which refusal a call with two gets …
+    if (!K) {
+        CHECK(check_step_arguments(ctx, src, w, S, fluxes, net));
+        if (S->fold_north) CHECK(check_fold_geometry(ctx, ctx->grid.ring + 1));
+        if (S->halo_backend == CF_HALO_PEER) CHECK(check_peer_rows(ctx, 4, S->halo_rows));
+    }
+    CHECK(cf_ensure_chunk_table(ctx, S->ocean_states[0].mask));
+    // CF_OPT_HALO_IN_SOLVER_LAUNCH: a step's request lives from its arming below to the cf_update_state of the same iteration;
+    // by whatever way this function returns, none stays armed for a later cf_update_state of the host
+    HaloRequestScope halo_request_scope(ctx);
     static const int fold_loc[4] = {CF_FOLD_CENTER, CF_FOLD_CENTER, CF_FOLD_X_FACE, CF_FOLD_Y_FACE};
     static const double fold_sign[4] = {1.0, 1.0, -1.0, -1.0};
     if (S->pipeline && nsteps > 0) {  // the first step's atmosphere, unless a previous call already started it
@@ -449,8 +475,7 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
         if (S->halo_backend == CF_HALO_RCCL)
             CHECK(cf_halo_exchange_rows(ctx, rows, 4, S->halo_rows));
         else if (S->halo_backend == CF_HALO_PEER) {
-            if (ctx->halo_in_launch && ctx->peer_connected && 4 <= ctx->peer_max_fields && S->halo_rows <= ctx->peer_max_rows &&
-                S->halo_rows <= ctx->grid.ny) {
+            if (ctx->halo_in_launch) {   // (the mailbox takes 4 fields × halo_rows: check_peer_rows above)
                 // CF_OPT_HALO_IN_SOLVER_LAUNCH: left as a request — this step's solver launch carries the exchange as rider
                 // workgroups where it can, cf_update_state issues the exchange kernel in front of the solver where it cannot
                 ctx->halo_request.F = PeerFields{};

@@ -482,7 +482,12 @@ int cf_set_stream(cf_ctx* ctx, void* hip_stream);
                                    * latency passes under interior work.  Applies where the step's solver launch is the exact path of the
                                    * round-3 ocean kernel with tail workgroups (CF_OPT_MERGED_PREFETCH = 2 inside a pipelined cf_time_steps);
                                    * any other step gets the exchange kernel as before.  The rows that arrive are the same bits
-                                   * (tests/test_steps.py: 2 and 4 ranks, lat-lon and tripolar).  0 (default): the exchange kernel of its
+                                   * (tests/test_halo_in_launch.py: 2 and 4 ranks, lat-lon and tripolar; tests/test_halo_thin_slabs.py: slabs
+                                   * of 2 to 8 rows, where no chunk lies between the boundary sets or one chunk is both).  A step's
+                                   * request lives from its arming in cf_time_steps to the cf_update_state of the same step and no longer:
+                                   * however the call ends, none stays behind for a cf_update_state of the host, and an exchange counts
+                                   * (cf_peer_halo_stats, the sequence number its neighbours match) only once its launch is queued.
+                                   * 0 (default): the exchange kernel of its
                                    * own.  What it buys on N devices is UNMEASURED: no multi-GPU node has run either form;
                                    * one launch boundary and a 3–5 µs kernel per step are what it removes from a 26 µs slab step.        */
 #define CF_OPT_INTERP_TILE_ROWS 15 /* EXPERIMENT option.  Rows of 64 cells per wave tile of the tiled interpolation: 0 (default) = automatic
@@ -970,7 +975,14 @@ int cf_fold_north_halo(cf_ctx* ctx, double* const* d_fields, const int* location
  * hold the first step's zeros, which are what every step would write.  So nothing else may write `fluxes` or `net` while the
  * call's work is on the stream (reading them, cf_attach_average / _integrals included, is fine), and the wet mask — one
  * pointer per schedule — is not rewritten in between.  Between two calls anything may happen to them: every call starts over.
- * CF_OPT_LAND_ZEROS = 0 writes the land at every step.                                                          */
+ * CF_OPT_LAND_ZEROS = 0 writes the land at every step.
+ * Refusals: everything one of the call's steps would refuse, at whichever step — a NULL field in any ocean state, in either
+ * exchange set, in the source, the weights, `fluxes` or `net`; with fold_north, a grid the fold does not apply to (odd nx,
+ * ny < ring + 2); under CF_HALO_PEER, a mailbox that does not take 4 fields × halo_rows — is refused with CF_ERR_INVALID
+ * BEFORE the first launch and before anything of the context changes (behind the refusals of the schedule's own scalars
+ * and of what is attached, in that order).  A refused call has written nothing, requested no atmosphere state ahead and
+ * left nothing for a later call to trip over: the next cf_update_state or cf_time_steps on the context runs as if the
+ * refused call had not been made (tests/test_refused_step_calls.py).                                           */
 #define CF_PIPELINE_WITHIN_CALL 1
 #define CF_PIPELINE_CONTINUING 2
 #define CF_HALO_NONE 0

@@ -333,8 +333,9 @@ def _host_update_writes_every_land_zero(rig, states, label):
 @gpu
 @pytest.mark.parametrize("preset", ["default", "ncar"])
 def test_the_mark_does_not_outlive_a_call(preset):
-    """After a cf_time_steps call a host cf_update_state writes every land zero; so it does after a call that fails its argument
-    check at its second step (ocean state 1 without a temperature field: step 0 is queued, step 1 refused)."""
+    """After a cf_time_steps call a host cf_update_state writes every land zero; so it does after a call that is refused for what
+    its second step would read (ocean state 1 without a temperature field: the whole call is refused before its first launch,
+    and the step loop is never opened)."""
     from coflux.runtime import CofluxError
     rig = _Rig(preset, "u8")
     ctx = rig.ctx
@@ -347,7 +348,7 @@ def test_the_mark_does_not_outlive_a_call(preset):
     with pytest.raises(CofluxError, match="ocean surface fields are NULL"):
         rig.loop(0, 4, broken, rig.sets(False), fl, net, False)
     rig.done()
-    assert ctx.debug_land_zero_launches() == 1          # step 0 went out, with its zeros
+    assert ctx.debug_land_zero_launches() == 1          # (the count of the call before: the refused one opened no loop)
     _host_update_writes_every_land_zero(rig, states, (preset, "after a failed call"))
     ctx.close()
 
