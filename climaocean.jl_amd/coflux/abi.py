@@ -298,6 +298,13 @@ class ClimatologyDesc(C.Structure):
                 ("bins", C.c_void_p * CLIMATOLOGY_MAX_FIELDS), ("reserved", C.c_int32 * 2)]
 
 
+class DatasetDesc(C.Structure):
+    """cf_dataset_desc: a dataset staged on the device (cf_dataset_create)."""
+    _fields_ = [("struct_size", C.c_int32), ("ns_x", C.c_int32), ("ns_y", C.c_int32), ("n_levels", C.c_int32),
+                ("periodic_x", C.c_int32), ("max_sweeps", C.c_int32), ("sweeps_per_launch", C.c_int32), ("max_workgroups", C.c_int32),
+                ("fill_value", C.c_double), ("period", C.c_double), ("times", C.c_void_p), ("weights", InterpWeights)]
+
+
 class RegridDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("mode", C.c_int32), ("n_rows", C.c_int64), ("nnz", C.c_int64),
                 ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("weight", C.c_void_p), ("mask", C.c_void_p),
@@ -342,6 +349,8 @@ EXPORTED_SYMBOLS = (
     "cf_monitor_reset", "cf_attach_monitor",
     "cf_climatology_create", "cf_climatology_destroy", "cf_climatology_reset", "cf_climatology_collect", "cf_climatology_weights",
     "cf_climatology_extremes", "cf_calendar_bin", "cf_attach_climatology",
+    "cf_dataset_create", "cf_dataset_destroy", "cf_dataset_stage", "cf_dataset_level", "cf_dataset_read_source", "cf_dataset_stage_info",
+    "cf_dataset_time_index", "cf_dataset_evaluate", "cf_materialize_dataset_restoring", "cf_attach_restoring_dataset",
     "cf_regrid_create", "cf_regrid_destroy", "cf_regrid_apply",
     "cf_prepare_coupled_step", "cf_time_steps_coupled",
     "cf_checkpoint_create", "cf_checkpoint_destroy", "cf_checkpoint_add_array", "cf_checkpoint_add_average", "cf_checkpoint_add_climatology",
@@ -512,6 +521,16 @@ def load_library(path=None):
     lib.cf_climatology_extremes.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
     lib.cf_calendar_bin.argtypes = [c_double_p, c_int32_p, C.c_int32, C.c_double, c_int32_p]
     lib.cf_attach_climatology.argtypes = [vp, vp, C.c_int32, C.c_double, C.c_double, C.c_double, c_double_p, c_int32_p, C.c_int32]
+    lib.cf_dataset_create.argtypes = [vp, C.POINTER(DatasetDesc), C.POINTER(vp)]
+    lib.cf_dataset_destroy.argtypes = [vp]
+    lib.cf_dataset_stage.argtypes = [vp, C.c_int32, vp]
+    lib.cf_dataset_level.argtypes = [vp, C.c_int32, C.POINTER(vp)]
+    lib.cf_dataset_read_source.argtypes = [vp, vp]
+    lib.cf_dataset_stage_info.argtypes = [vp, C.c_int32, c_int32_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.cf_dataset_time_index.argtypes = [c_double_p, C.c_int32, C.c_double, C.c_double, c_int32_p, c_int32_p, c_double_p]
+    lib.cf_dataset_evaluate.argtypes = [vp, C.c_double, vp]
+    lib.cf_materialize_dataset_restoring.argtypes = [vp, C.c_double, vp, C.c_double, C.POINTER(OceanSurface), vp]
+    lib.cf_attach_restoring_dataset.argtypes = [vp, vp, C.c_double, C.c_double]
     lib.cf_regrid_create.argtypes = [vp, C.POINTER(RegridDesc), C.POINTER(vp)]
     lib.cf_regrid_destroy.argtypes = [vp]
     lib.cf_regrid_apply.argtypes = [vp, C.c_int32, C.POINTER(vp), C.POINTER(vp), vp]

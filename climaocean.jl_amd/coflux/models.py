@@ -184,12 +184,57 @@ class SurfaceFluxRestoring:
     """SurfaceFluxRestoring(DatasetRestoring(…; rate = piston_velocity / (Δz days))) — salinity_surface_restoring,
     omip_simulation.jl:507-523: a surface-only restoring toward `target` (2-D, halo-inclusive device array, g/kg) that rides
     on the ocean's top-flux boundary condition through `additional_surface_fluxes`.  piston_velocity in m/day as there."""
-    target: torch.Tensor
+    target: object   # a 2-D device array, or a DatasetRestoring: S★ then follows the dataset in time
     piston_velocity: float = 1.0 / 6.0
 
     @property
     def velocity(self):
         return self.piston_velocity / days
+
+
+class DatasetRestoring:
+    """DatasetRestoring(Metadata(:salinity; dataset = WOAMonthly()), arch; time_indices_in_memory = length(metadata)) —
+    salinity_surface_restoring, omip_simulation.jl:507-523: every level of the dataset resident on the device, each
+    land-inpainted on the dataset's own grid and interpolated to the ocean grid, blended linearly in time — cyclically over
+    `period` [s] when it is > 0, clamped at the ends otherwise.  `planes`: host array [n, ns_y, ns_x] on a global regular
+    latitude–longitude grid laid out as the JRA55 record is (NaN = missing); `times` [s]: the levels' times on the model's
+    clock.  Given as the `target` of a SurfaceFluxRestoring.  Staged once per context, on first use (cf_dataset_*)."""
+
+    def __init__(self, planes, times, period=0.0, *, periodic_x=True, max_sweeps=-1, fill_value=0.0, sweeps_per_launch=0):
+        self.planes = np.asarray(planes, dtype=np.float32)
+        self.times = [float(t) for t in times]
+        if self.planes.ndim != 3 or self.planes.shape[0] != len(self.times):
+            raise ValueError(f"DatasetRestoring: planes is [n, ns_y, ns_x] with one time per level, got {self.planes.shape} and {len(self.times)} times")
+        self.period = float(period)
+        self.options = dict(periodic_x=periodic_x, max_sweeps=max_sweeps, fill_value=fill_value, sweeps_per_launch=sweeps_per_launch)
+        self._staged = None   # (context, Dataset)
+
+    def dataset(self, ctx, grid):
+        """The staged runtime.Dataset on `ctx` (the levels are uploaded, inpainted and regridded the first time)."""
+        if self._staged is None or self._staged[0] is not ctx:
+            ns_y, ns_x = self.planes.shape[1:]
+            d = ctx.dataset(ns_x, ns_y, self.times, grid.interpolation_weights(ctx.to_device, ns_x, ns_y), period=self.period, **self.options)
+            for level, plane in enumerate(self.planes):
+                d.stage(level, plane)
+            self._staged = (ctx, d)
+        return self._staged[1]
+
+
+def set_from_dataset(field, plane, ctx, grid, *, periodic_x=True, max_sweeps=-1, fill_value=0.0):
+    """set!(field, Metadatum(…)) — the initial conditions of omip_simulation.jl:614-615, :634-635: one plane of a dataset
+    (host array [ns_y, ns_x], NaN = missing) inpainted and interpolated onto the ring window of `field`, a halo-inclusive 2-D
+    device array of the context's shape (the top level of a 3-D field, say)."""
+    plane = np.asarray(plane, dtype=np.float32)
+    ns_y, ns_x = plane.shape
+    d = ctx.dataset(ns_x, ns_y, [0.0], grid.interpolation_weights(ctx.to_device, ns_x, ns_y), periodic_x=periodic_x, max_sweeps=max_sweeps,
+                    fill_value=fill_value)
+    try:
+        d.stage(0, plane)
+        d.evaluate(0.0, field)
+        ctx.sync()
+    finally:
+        d.close()
+    return field
 
 
 @dataclass
@@ -763,8 +808,9 @@ def time_steps(model, dt, nsteps, normalize=None, averages=None, climatology=Non
         ctx.attach_climatology(climatology.climatology, climatology.table(t0, t0 + (nsteps + 1) * dt), stride, 1.0 / stride,
                                t0 - first * dt, dt)
     try:
-        _device_steps(model, dt, nsteps, normalize, clocks, first, lent, ai, state, stresses, exchange, ice_ocean, restoring)
+        _device_steps(model, dt, nsteps, normalize, clocks, first, lent, ai, state, stresses, exchange, ice_ocean, restoring, times)
     finally:
+        ctx.attach_restoring_dataset(None)
         for slot in range(len(attached)):
             ctx.attach_average(None, slot=slot)
         if climatology is not None:
@@ -779,10 +825,23 @@ def time_steps(model, dt, nsteps, normalize=None, averages=None, climatology=Non
         model.clock.iteration += 1
 
 
-def _device_steps(model, dt, nsteps, normalize, clocks, first, exchange_set, ai, state, stresses, exchange, ice_ocean, restoring):
+def _dataset_origin(time, step, dt):
+    """time_origin with which the dataset clock of the device loop, origin + step · Δt, gives exactly `time` at `step`, or None"""
+    base = float(step) * dt
+    guess = time - base
+    for origin in (guess, float(np.nextafter(guess, np.inf)), float(np.nextafter(guess, -np.inf))):
+        if origin + base == time:
+            return origin
+    return None
+
+
+def _device_steps(model, dt, nsteps, normalize, clocks, first, exchange_set, ai, state, stresses, exchange, ice_ocean, restoring, times=None):
     """time_steps' calls of cf_time_steps_coupled: one per stretch of steps on which the device loop's clocks agree with the host's"""
     itf, atm, ocean, land = model.interfaces, model.atmosphere, model.ocean, getattr(model, "land", None)
     ctx = itf.context
+    # a restoring that follows a dataset: the host loop materialises it at the model clock after the step (times[k], a repeated
+    # sum); the device loop's clock for it is origin + step · Δt, held to the same doubles stretch by stretch
+    dataset = restoring.target.dataset(ctx, ocean.grid) if restoring is not None and isinstance(restoring.target, DatasetRestoring) else None
     a = 0
     while a < nsteps:
         g = first + a
@@ -798,6 +857,12 @@ def _device_steps(model, dt, nsteps, normalize, clocks, first, exchange_set, ai,
         while b < nsteps and all(_clock_at(c[0], c[1], comp.n_levels, first + b, inc) == tuple(want[b])
                                  for (comp, want, inc), c in zip(clocks, based)):
             b += 1
+        if dataset is not None:
+            origin = _dataset_origin(times[a], g, dt)
+            if origin is None:
+                raise ValueError(f"time_steps: the dataset clock origin + step · Δt cannot give the model time {times[a]!r} at step {g}; use time_step")
+            b = next((k for k in range(a + 1, b) if origin + float(first + k) * dt != times[k]), b)
+            ctx.attach_restoring_dataset(dataset, time_origin=origin, step_seconds=dt)
         sch = ctx.make_schedule([ocean.surface_state()], [exchange_set], first_level=based[0][0],
                                 time_fraction=based[0][1], time_fraction_increment=clocks[0][2], fold_north=itf.fold_north)
         kw = {}
@@ -805,7 +870,8 @@ def _device_steps(model, dt, nsteps, normalize, clocks, first, exchange_set, ai,
             kw.update(friver=land.data["friver"], licalvf=land.data.get("licalvf"), land_out=itf.land_freshwater,
                       land_first_level=based[1][0], land_time_fraction=based[1][1], land_time_fraction_increment=clocks[1][2])
         if restoring is not None:
-            kw.update(piston_velocity=restoring.velocity, target=restoring.target, restoring_out=normalize.additional_buffer)
+            kw.update(piston_velocity=restoring.velocity, target=None if dataset is not None else restoring.target,
+                      restoring_out=normalize.additional_buffer)
         if normalize is not None:
             kw.update(normalize=True, area=normalize.area, mean_out=normalize.mean_total)
         block = ctx.make_coupled_step([state], ai["temperature"], ai, itf.net_fluxes._sea_ice_fields,
@@ -1831,7 +1897,11 @@ class NormalizeSalinity:
         ctx, ocean = model.interfaces.context, model.ocean
         if self.additional_fluxes is not None:
             r = self.additional_fluxes
-            ctx.materialize_salinity_restoring(r.velocity, r.target, ocean.surface_state(), self.additional_buffer)
+            if isinstance(r.target, DatasetRestoring):   # S★ at the model clock, formed per cell from the dataset's two levels
+                ctx.materialize_dataset_restoring(r.velocity, r.target.dataset(ctx, ocean.grid), model.clock.time, ocean.surface_state(),
+                                                  self.additional_buffer)
+            else:
+                ctx.materialize_salinity_restoring(r.velocity, r.target, ocean.surface_state(), self.additional_buffer)
         ctx.normalize_salinity_flux(self.flux_field, ocean.model.wet_mask, additional=self.additional_buffer, area=self.area,
                                     mean_out=self.mean_total)
 

@@ -590,6 +590,27 @@ class FluxContext:
                                                    int(edges.size)), "cf_attach_climatology")
         self._attached_climatology = clim   # kept alive while attached
 
+    # -- staged datasets ---------------------------------------------------------------------------
+    def dataset(self, ns_x, ns_y, times, weights, period=0.0, periodic_x=True, max_sweeps=-1, fill_value=0.0, sweeps_per_launch=0,
+                max_workgroups=0):
+        """A dataset staged on the device (cf_dataset_create): len(times) levels of an ns_y × ns_x source grid, each
+        stage(level, plane) land-inpainted, interpolated through `weights` (as interpolate_land_freshwater takes them) onto an
+        ocean-grid array the handle owns; evaluate(time) blends two levels — cyclically when period > 0, clamped otherwise."""
+        return Dataset(self, ns_x, ns_y, times, weights, period, periodic_x, max_sweeps, fill_value, sweeps_per_launch, max_workgroups)
+
+    def materialize_dataset_restoring(self, piston_velocity, dataset, time, ocean, out):
+        """materialize_salinity_restoring with S★ formed per cell from `dataset` at `time` (cf_materialize_dataset_restoring)."""
+        o = self.ocean_struct(ocean)
+        self._check(self.lib.cf_materialize_dataset_restoring(self._h, float(piston_velocity), dataset._h, float(time), C.byref(o), _ptr(out)),
+                    "cf_materialize_dataset_restoring")
+
+    def attach_restoring_dataset(self, dataset, time_origin=0.0, step_seconds=1.0):
+        """Step s of time_steps_coupled() restores toward `dataset` at time_origin + s · step_seconds, inside the preamble's
+        launch; the block's target_salinity is then None (cf_attach_restoring_dataset).  None detaches."""
+        h = dataset._h if dataset is not None else None
+        self._check(self.lib.cf_attach_restoring_dataset(self._h, h, float(time_origin), float(step_seconds)), "cf_attach_restoring_dataset")
+        self._attached_restoring_dataset = dataset   # kept alive while attached
+
     # -- checkpoint and pickup --------------------------------------------------------------------
     def checkpoint(self, direct=False, max_workgroups=0):
         """A checkpoint handle (cf_checkpoint_create): register arrays and handles, capture() … wait() → image,
@@ -966,6 +987,88 @@ class Climatology(_ChildHandle):
             made.append(t)
         self._check(self.lib.cf_climatology_extremes(self._h, int(field), *[_ptr(t) for t in made]), "cf_climatology_extremes")
         return tuple(made)
+
+
+def dataset_time_index(times, period, time):
+    """(level1, level2, fraction) of `time` in a dataset's level times: cf_dataset_time_index, a pure host function — cyclical
+    over `period` when it is > 0, clamped when 0.  ValueError for a time that is not finite or a bad table."""
+    lib = abi.load_library()
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    if times.ndim != 1:
+        raise ValueError("dataset_time_index: times is one-dimensional")
+    l1, l2, f = C.c_int32(-1), C.c_int32(-1), C.c_double(float("nan"))
+    rc = lib.cf_dataset_time_index(times.ctypes.data_as(abi.c_double_p), int(times.size), float(period), float(time), C.byref(l1),
+                                   C.byref(l2), C.byref(f))
+    if rc != 0:
+        raise ValueError(lib.cf_last_error(None).decode())
+    return l1.value, l2.value, f.value
+
+
+class Dataset(_ChildHandle):
+    """cf_dataset_*: a dataset on its own latitude–longitude grid, staged level by level — stage(level, plane) converts a host
+    float32 plane (NaN = missing) to f64, inpaints it by nearest-neighbour sweeps whose number the host knows beforehand, and
+    interpolates it onto the level's ocean-grid array — and followed in time by evaluate(time), materialize_dataset_restoring
+    and the coupled loop (FluxContext.attach_restoring_dataset).  The library borrows the weights: the tensors are kept here."""
+    _destroy = "cf_dataset_destroy"
+
+    def __init__(self, ctx, ns_x, ns_y, times, weights, period=0.0, periodic_x=True, max_sweeps=-1, fill_value=0.0, sweeps_per_launch=0,
+                 max_workgroups=0):
+        self._adopt(ctx)
+        self.ns_x, self.ns_y, self.period = int(ns_x), int(ns_y), float(period)
+        self.times = np.ascontiguousarray(times, dtype=np.float64)
+        if self.times.ndim != 1:
+            raise ValueError("times is one-dimensional")
+        self.n_levels = int(self.times.size)
+        self._keep = weights
+        desc = abi.DatasetDesc()
+        desc.struct_size = C.sizeof(abi.DatasetDesc)
+        desc.ns_x, desc.ns_y, desc.n_levels, desc.periodic_x = self.ns_x, self.ns_y, self.n_levels, 1 if periodic_x else 0
+        desc.max_sweeps, desc.sweeps_per_launch, desc.max_workgroups = int(max_sweeps), int(sweeps_per_launch), int(max_workgroups)
+        desc.fill_value, desc.period, desc.times = float(fill_value), self.period, self.times.ctypes.data
+        desc.weights = ctx.weights_struct(weights)
+        ctx._check(self.lib.cf_dataset_create(ctx._h, C.byref(desc), C.byref(self._h)), "cf_dataset_create")
+
+    def stage(self, level, plane):
+        """Queue the staging of `plane` (host array [ns_y, ns_x], NaN = missing) as level `level`; no synchronisation."""
+        plane = np.ascontiguousarray(plane, dtype=np.float32)
+        if plane.shape != (self.ns_y, self.ns_x):
+            raise ValueError(f"stage: the plane is [{self.ns_y}, {self.ns_x}], got {plane.shape}")
+        self._check(self.lib.cf_dataset_stage(self._h, int(level), plane.ctypes.data), "cf_dataset_stage")
+
+    def level(self, level):
+        """A copy of the level's ocean-grid array as a device tensor (synchronises; level_pointer gives the borrowed address)."""
+        host = np.empty(self.ctx.shape, dtype=np.float64)
+        self.ctx._check(self.lib.cf_d2h(self.ctx._h, host.ctypes.data, self.level_pointer(level), host.nbytes), "cf_d2h")
+        return torch.from_numpy(host).to(self.ctx.device)
+
+    def level_pointer(self, level):
+        """The device address of the level's ocean-grid array, borrowed from the dataset (cf_dataset_level)."""
+        p = C.c_void_p()
+        self._check(self.lib.cf_dataset_level(self._h, int(level), C.byref(p)), "cf_dataset_level")
+        return p.value
+
+    def read_source(self):
+        """The inpainted f64 plane [ns_y, ns_x] of the most recently staged level; synchronises."""
+        out = np.empty((self.ns_y, self.ns_x), dtype=np.float64)
+        self._check(self.lib.cf_dataset_read_source(self._h, out.ctypes.data), "cf_dataset_read_source")
+        return out
+
+    def stage_info(self, level):
+        """(sweeps queued, cells filled by a sweep, cells given the fill value) of a staged level: host bookkeeping."""
+        sweeps, filled, defaulted = C.c_int32(), C.c_int64(), C.c_int64()
+        self._check(self.lib.cf_dataset_stage_info(self._h, int(level), C.byref(sweeps), C.byref(filled), C.byref(defaulted)),
+                    "cf_dataset_stage_info")
+        return sweeps.value, filled.value, defaulted.value
+
+    def time_index(self, time):
+        return dataset_time_index(self.times, self.period, time)
+
+    def evaluate(self, time, out):
+        """S★ at `time` on the ring window of `out` (an ocean-grid float64 field); one launch."""
+        if not _is_field(out, self.ctx):
+            raise ValueError(f"evaluate: out is a contiguous float64 device array of shape {self.ctx.shape}")
+        self._check(self.lib.cf_dataset_evaluate(self._h, float(time), _ptr(out)), "cf_dataset_evaluate")
+        return out
 
 
 def _host_bytes(data):

@@ -1473,7 +1473,9 @@ int check_coupled_prepare(cf_ctx* ctx, const cf_coupled_prepare* p) {
     return CF_OK;
 }
 
-int cf_prepare_coupled_step(cf_ctx* ctx, const cf_coupled_prepare* p) {
+int cf_prepare_coupled_step(cf_ctx* ctx, const cf_coupled_prepare* p) { return prepare_coupled_step_levels(ctx, p, nullptr, 0.0); }
+
+int prepare_coupled_step_levels(cf_ctx* ctx, const cf_coupled_prepare* p, const double* level2, double fraction) {
     CHECK(check_coupled_prepare(ctx, p));
     const bool ice_job = p->ice_ocean_fluxes.interface_heat != nullptr;
     if (!p->land_freshwater && !ice_job && !p->restoring_buffer) return CF_OK;
@@ -1504,6 +1506,8 @@ int cf_prepare_coupled_step(cf_ctx* ctx, const cf_coupled_prepare* p) {
     if (p->restoring_buffer) {
         A.vp = p->piston_velocity;
         A.target = p->target_salinity;
+        A.target2 = level2;
+        A.fraction = level2 ? fraction : 0.0;
         A.restoring = p->restoring_buffer;
     }
     A.S = p->ocean.S;

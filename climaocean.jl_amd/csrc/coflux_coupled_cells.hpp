@@ -72,4 +72,26 @@ __device__ __forceinline__ double salinity_restoring_cell(bool wet, double vp, d
     return wet ? vp * (So - target[k]) : 0.0;
 }
 
+// S★ of a staged dataset (cf_dataset_*) between two of its levels: blend_levels' expression on doubles.  Every reader of a
+// blended S★ calls this one function and holds the result in a named variable before using it, so that the expression is
+// rounded the same way whatever follows it.
+__device__ __forceinline__ double dataset_blend(double a, double b, double f) { return b * f + a * (1.0 - f); }
+
+// S★ at element k: level1's value when the fraction is 0.0 (level2 is not read), else the blend
+__device__ __forceinline__ double dataset_target_cell(const double* __restrict__ level1, const double* __restrict__ level2, double fraction,
+                                                      size_t k) {
+    if (fraction == 0.0) return level1[k];
+    const double target = dataset_blend(level1[k], level2[k], fraction);
+    return target;
+}
+
+// the two-level form of the restoring cell: S★ formed from a dataset's two levels (fraction 0.0: the one-level form on level1)
+__device__ __forceinline__ double salinity_restoring_cell(bool wet, double vp, double So, const double* __restrict__ level1,
+                                                          const double* __restrict__ level2, double fraction, size_t k) {
+    if (fraction == 0.0) return salinity_restoring_cell(wet, vp, So, level1, k);
+    if (!wet) return 0.0;
+    const double target = dataset_blend(level1[k], level2[k], fraction);
+    return vp * (So - target);
+}
+
 }  // namespace coflux

@@ -22,6 +22,7 @@
 #include "coflux_checkpoint.hpp"
 #include "coflux_checkpoint_image.hpp"
 #include "coflux_collect.hpp"
+#include "coflux_dataset_rules.hpp"
 #include "coflux_fast.hpp"
 #include "coflux_kernel_types.hpp"
 #include "coflux_kernels.h"
@@ -215,6 +216,9 @@ struct cf_ctx {
     // (cf_attach_integrals) and the monitor (cf_attach_monitor)
     enum { AT_CLIMATOLOGY = CF_ATTACHED_AVERAGES_MAX, AT_INTEGRALS, AT_MONITOR, AT_COUNT };
     Attachment attached[AT_COUNT];
+    // the dataset the coupled loop's restoring job follows (cf_attach_restoring_dataset): not collected — step s restores toward
+    // S★ at when.time_origin + s · when.step_seconds
+    Attachment restoring_dataset;
 };
 
 // One cf_time_steps call's step loop, as CF_OPT_LAND_ZEROS sees it: open for exactly the scope's lifetime
@@ -288,6 +292,41 @@ struct cf_climatology : cf_child {
     void load_tail(const std::vector<unsigned char>& tail, int64_t) override { get_binned_weights(tail.data(), &weight, bin_weight, n_bins); }
 };
 
+// a dataset staged on the device (coflux_dataset.cpp): the handle owns its planes, its levels and the upload lane
+struct cf_dataset : cf_child {
+    int ns_x = 0, ns_y = 0, n_levels = 0, max_sweeps = -1, sweeps_per_launch = 0, max_blocks = 0;
+    bool periodic_x = false;
+    double fill_value = 0.0, period = 0.0;
+    std::vector<double> times;
+    cf_interp_weights weights{};              // borrowed device arrays
+    cf::DeviceBuffer<double> d_plane[2];      // the sweeps' p and q
+    cf::DeviceBuffer<float> d_upload;         // the plane as it arrived
+    cf::DeviceBuffer<double> d_levels;        // n_levels parent arrays back to back
+    cf::PinnedBuffer<float> h_upload[2];      // two slots: a stage call returns while its copy is still in flight
+    cf::Event uploaded[2];
+    int upload_slot = 0, current = 0;         // current: which plane holds the most recently staged level, inpainted
+    int last_level = -1;
+    struct Staged {
+        bool done = false;
+        int32_t sweeps = 0;
+        int64_t filled = 0, defaulted = 0;
+    } staged[CF_DATASET_MAX_LEVELS];
+    size_t parent() const { return (size_t)ctx->grid.sj * (size_t)(ctx->grid.ny + 2 * ctx->grid.hy); }
+    double* level(int l) const { return d_levels.get() + parent() * (size_t)l; }
+    int first_unstaged() const {
+        for (int l = 0; l < n_levels; ++l)
+            if (!staged[l].done) return l;
+        return -1;
+    }
+};
+// S★ of `d` at `time` as the kernels take it: CF_ERR_INVALID (the refusal of `fn`) unless every level is staged and the time finite
+struct DatasetTarget {
+    const double* level1;
+    const double* level2;
+    double fraction;
+};
+int dataset_target_at(const cf_dataset* d, const char* fn, double time, DatasetTarget* out);
+
 struct cf_regrid : cf_child {
     RegridTables tables{};
     int64_t n_rows = 0;
@@ -322,6 +361,10 @@ extern "C" __attribute__((visibility("hidden"))) int cf_ahead_perform(cf_ctx* ct
 // cf_update_state_sea_ice of a coupled step loop, without their launches (cf_time_steps and cf_time_steps_coupled validate a
 // whole call before its first launch)
 extern "C" __attribute__((visibility("hidden"))) int check_coupled_prepare(cf_ctx* ctx, const cf_coupled_prepare* p);
+// coflux_abi.cpp: cf_prepare_coupled_step whose restoring job reads S★ from two levels of a dataset — p->target_salinity is
+// level1, `level2` and `fraction` the rest (fraction 0.0: cf_prepare_coupled_step itself)
+extern "C" __attribute__((visibility("hidden"))) int prepare_coupled_step_levels(cf_ctx* ctx, const cf_coupled_prepare* p, const double* level2,
+                                                                                 double fraction);
 extern "C" __attribute__((visibility("hidden"))) int check_step_arguments(cf_ctx* ctx, const cf_atmos_source* src, const cf_interp_weights* w,
                                                                           const cf_run_schedule* S, const cf_interface_fluxes* fluxes,
                                                                           const cf_net_ocean_fluxes* net);
@@ -354,12 +397,14 @@ inline void child_leave(cf_child* child) {
     ctx->children.erase(std::remove(ctx->children.begin(), ctx->children.end(), child), ctx->children.end());
     for (Attachment& at : ctx->attached)
         if (at.handle == child) at = Attachment{};
+    if (ctx->restoring_dataset.handle == child) ctx->restoring_dataset = Attachment{};
 }
 inline void orphan_children(cf_ctx* ctx) {
     for (cf_child* child : ctx->children) child->ctx = nullptr;
     ctx->children.clear();
     ctx->checkpoints.clear();
     for (Attachment& at : ctx->attached) at = Attachment{};
+    ctx->restoring_dataset = Attachment{};
 }
 // CF_ERR_INVALID unless `child` is a handle whose context is alive: live(a, "cf_average_reset", "averager")
 inline int live(const cf_child* child, const char* fn, const char* kind) {

@@ -155,13 +155,29 @@ struct PrepareArgs {
     double* Qfr;
     double* ustar;
     double vp;                // restoring buffer → restoring on I
-    const double* target;
+    const double* target;     // S★, or level1 of a staged dataset …
+    const double* target2;    // … whose level2 and fraction these are (fraction 0.0: target alone is read)
+    double fraction;
     double* restoring;
     const double* S;          // read once for both interior jobs, like the mask
     const void* mask;
 };
 hipError_t launch_prepare_coupled_step(hipStream_t st, const DevParams& P, const GridDesc& G, const cf_interp_weights* w,
                                        const PrepareArgs& A);
+// cf_dataset_* (coflux_dataset.hip): a plane of the dataset's grid converted to f64, inpainted by `sweeps` nearest-neighbour sweeps
+// in one launch (1: one thread per cell; 2 … INPAINT_MAX_SWEEPS: overlapped LDS tiles — same bits), its remaining NaNs given the
+// fill value, interpolated onto W of an ocean-grid array; S★ from two levels on W; the restoring buffer with S★ formed per cell.
+// max_blocks: cf_dataset_desc.max_workgroups (0: the kernels' own cap)
+constexpr int INPAINT_MAX_SWEEPS = 8;
+hipError_t launch_dataset_convert(hipStream_t st, const float* in, double* out, size_t n, int max_blocks);
+hipError_t launch_dataset_default(hipStream_t st, double* plane, size_t n, double fill, int max_blocks);
+hipError_t launch_dataset_inpaint(hipStream_t st, const double* p, double* q, int ns_x, int ns_y, bool periodic, int sweeps, int max_blocks);
+hipError_t launch_dataset_regrid(hipStream_t st, const double* plane, int ns_x, int ns_y, const cf_interp_weights* w, const GridDesc& G,
+                                 double* out, int max_blocks);
+hipError_t launch_dataset_evaluate(hipStream_t st, const double* level1, const double* level2, double fraction, const GridDesc& G, double* out,
+                                   int max_blocks);
+hipError_t launch_dataset_restoring(hipStream_t st, const DevParams& P, const GridDesc& G, const void* mask, double vp, const double* level1,
+                                    const double* level2, double fraction, const double* S, double* out);
 constexpr int SALINITY_PARTIAL_BLOCKS = 512;
 hipError_t launch_salinity_partial_sums(hipStream_t st, const DevParams& P, const GridDesc& G, const double* flux,
                                         const double* additional, const double* area, const void* mask, double* partial,

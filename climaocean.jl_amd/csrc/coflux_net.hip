@@ -216,7 +216,10 @@ __global__ __launch_bounds__(NET_BLOCK) void prepare_coupled_step_kernel(DevPara
         if (A.Qfr) A.Qfr[k] = C.q_fr;
         if (A.ustar) A.ustar[k] = C.us;
     }
-    if (A.restoring) A.restoring[k] = salinity_restoring_cell(wet, A.vp, So, A.target, k);
+    // (a dataset attached to the coupled loop gives two levels and a fraction; fraction 0.0 is the static target's own form)
+    if (A.restoring)
+        A.restoring[k] = A.fraction == 0.0 ? salinity_restoring_cell(wet, A.vp, So, A.target, k)
+                                           : salinity_restoring_cell(wet, A.vp, So, A.target, A.target2, A.fraction, k);
 }
 
 hipError_t launch_prepare_coupled_step(hipStream_t st, const DevParams& P, const GridDesc& G, const cf_interp_weights* w,

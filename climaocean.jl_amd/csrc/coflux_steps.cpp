@@ -382,8 +382,17 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
         s.time_fraction = total - whole;
         return s;
     };
+    // the dataset the coupled block's restoring job follows, if one is attached and the block has the job: step s restores toward
+    // S★ at time_origin + s · step_seconds, the time of the ocean state it reads (checked for every step before the first launch)
+    const cf_dataset* dataset = K && K->restoring_buffer ? static_cast<const cf_dataset*>(ctx->restoring_dataset.handle) : nullptr;
+    auto target_at = [&](int64_t step) {
+        DatasetTarget T{};
+        const StepSchedule& when = ctx->restoring_dataset.when;
+        (void)dataset_target_at(dataset, name, when.time_origin + (double)step * when.step_seconds, &T);
+        return T;
+    };
     // the coupled block's preamble for step `step`: the land clock runs by source_at's arithmetic on the block's own fields
-    auto prepare_at = [&](int64_t step, const cf_ocean_surface* o, const cf_sea_ice_state* is) {
+    auto prepare_at =[&](int64_t step, const cf_ocean_surface* o, const cf_sea_ice_state* is) {
         cf_coupled_prepare P{};
         P.struct_size = (int32_t)sizeof(cf_coupled_prepare);
         P.ocean = *o;
@@ -406,13 +415,21 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
         }
         if (K->restoring_buffer) {
             P.piston_velocity = K->piston_velocity;
-            P.target_salinity = K->target_salinity;
+            P.target_salinity = dataset ? target_at(step).level1 : K->target_salinity;
             P.restoring_buffer = K->restoring_buffer;
         }
         return P;
     };
     if (K) {   // everything the steps' own entry points would refuse, before the first launch: the outputs stay untouched
         CHECK(check_coupled_block(ctx, S, src, w, fluxes, ice, net, K));
+        if (dataset) {
+            if (K->target_salinity)
+                return fail(ctx, CF_ERR_INVALID, "%s: target_salinity is given and a restoring dataset is attached (one of the two)", name);
+            DatasetTarget T{};
+            for (int64_t step = first_step; step < first_step + nsteps; ++step)
+                CHECK(dataset_target_at(dataset, name, ctx->restoring_dataset.when.time_origin +
+                                                           (double)step * ctx->restoring_dataset.when.step_seconds, &T));
+        }
         for (int n = 0; n < S->n_ocean_states; ++n) {
             const cf_coupled_prepare P = prepare_at(first_step, &S->ocean_states[n], &K->ice_states[0]);
             CHECK(check_coupled_prepare(ctx, &P));
@@ -491,7 +508,12 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
         const cf_sea_ice_state* is = K ? &K->ice_states[step % K->n_ice_states] : nullptr;
         if (K) {
             const cf_coupled_prepare P = prepare_at(step, o, is);
-            CHECK(cf_prepare_coupled_step(ctx, &P));
+            if (dataset) {
+                const DatasetTarget T = target_at(step);
+                CHECK(prepare_coupled_step_levels(ctx, &P, T.level2, T.fraction));
+            } else {
+                CHECK(cf_prepare_coupled_step(ctx, &P));
+            }
             if (K->land.friver) ctx->d_land_freshwater = K->land_freshwater;   // cf_set_land_freshwater
         }
         const cf_atmos_source s = source_at(step);

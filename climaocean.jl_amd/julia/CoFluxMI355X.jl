@@ -659,6 +659,73 @@ function attach_climatology!(b, c::Union{Nothing, CoFluxClimatology}, edges::Vec
                        b.ctx, isnothing(c) ? C_NULL : c.ptr, stride, step_weight, time_origin, step_seconds, edges, bin_of_interval, length(edges)))
 end
 
+# ---- a dataset staged on the device and followed in time (omip_simulation.jl:507-523, :614-615, :634-635) ----------------
+# DatasetRestoring(Metadata(:salinity; dataset = WOAMonthly()), …): stage!(d, level, plane) takes a host Matrix{Float32} of
+# the dataset's own grid (ns_x × ns_y, NaN = missing), inpaints it by nearest-neighbour sweeps and interpolates it onto the
+# level's ocean-grid array, with no host synchronisation; evaluate!(d, time, out) writes S★; attach_restoring_dataset! makes
+# time_steps_coupled! follow it (the block's target_salinity is then C_NULL).  Levels are 0-based, as in the C ABI.
+struct CfDatasetDesc
+    struct_size::Int32; ns_x::Int32; ns_y::Int32; n_levels::Int32
+    periodic_x::Int32; max_sweeps::Int32; sweeps_per_launch::Int32; max_workgroups::Int32
+    fill_value::Float64; period::Float64
+    times::Ptr{Float64}
+    weights::CfInterpWeights
+end
+mutable struct CoFluxDataset
+    ptr::Ptr{Cvoid}
+    backend::CoFluxBackend
+    ns_x::Int
+    ns_y::Int
+    times::Vector{Float64}
+    period::Float64
+end
+function CoFluxDataset(b::CoFluxBackend, ns_x, ns_y, times::Vector{Float64}, weights::CfInterpWeights; period = 0.0, periodic_x = true,
+                       max_sweeps = -1, fill_value = 0.0, sweeps_per_launch = 0, max_workgroups = 0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve times begin
+        desc = CfDatasetDesc(sizeof(CfDatasetDesc), ns_x, ns_y, length(times), periodic_x ? 1 : 0, max_sweeps, sweeps_per_launch,
+                             max_workgroups, fill_value, period, pointer(times), weights)
+        check(b.ctx, ccall((:cf_dataset_create, libcoflux), Cint, (Ptr{Cvoid}, Ref{CfDatasetDesc}, Ref{Ptr{Cvoid}}), b.ctx, desc, out))
+    end
+    d = CoFluxDataset(out[], b, ns_x, ns_y, copy(times), period)
+    finalizer(x -> ccall((:cf_dataset_destroy, libcoflux), Cint, (Ptr{Cvoid},), x.ptr), d)
+    return d
+end
+function stage!(d::CoFluxDataset, level, plane::Matrix{Float32})
+    size(plane) == (d.ns_x, d.ns_y) || error("CoFluxMI355X: the plane is $(d.ns_x) × $(d.ns_y)")
+    check(C_NULL, ccall((:cf_dataset_stage, libcoflux), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}), d.ptr, level, plane))
+end
+function dataset_level(d::CoFluxDataset, level)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(C_NULL, ccall((:cf_dataset_level, libcoflux), Cint, (Ptr{Cvoid}, Int32, Ref{Ptr{Float64}}), d.ptr, level, p))
+    return p[]
+end
+function read_source(d::CoFluxDataset)
+    out = zeros(Float64, d.ns_x, d.ns_y)
+    check(C_NULL, ccall((:cf_dataset_read_source, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Float64}), d.ptr, out))
+    return out
+end
+function stage_info(d::CoFluxDataset, level)
+    sweeps = Ref{Int32}(0); filled = Ref{Int64}(0); defaulted = Ref{Int64}(0)
+    check(C_NULL, ccall((:cf_dataset_stage_info, libcoflux), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}, Ref{Int64}, Ref{Int64}),
+                        d.ptr, level, sweeps, filled, defaulted))
+    return (sweeps = sweeps[], filled = filled[], defaulted = defaulted[])
+end
+function dataset_time_index(times::Vector{Float64}, period, time)
+    level1 = Ref{Int32}(-1); level2 = Ref{Int32}(-1); fraction = Ref{Float64}(NaN)
+    check(C_NULL, ccall((:cf_dataset_time_index, libcoflux), Cint, (Ptr{Float64}, Int32, Float64, Float64, Ref{Int32}, Ref{Int32}, Ref{Float64}),
+                        times, length(times), period, time, level1, level2, fraction))
+    return (level1[], level2[], fraction[])
+end
+evaluate!(d::CoFluxDataset, time, out) =
+    check(C_NULL, ccall((:cf_dataset_evaluate, libcoflux), Cint, (Ptr{Cvoid}, Float64, Ptr{Float64}), d.ptr, time, out))
+materialize_dataset_restoring!(b, piston_velocity, d::CoFluxDataset, time, ocean::CfOceanSurface, buffer) =
+    check(b.ctx, ccall((:cf_materialize_dataset_restoring, libcoflux), Cint,
+                       (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Float64, Ref{CfOceanSurface}, Ptr{Float64}), b.ctx, piston_velocity, d.ptr, time, ocean, buffer))
+attach_restoring_dataset!(b, d::Union{Nothing, CoFluxDataset}; time_origin = 0.0, step_seconds = 1.0) =
+    check(b.ctx, ccall((:cf_attach_restoring_dataset, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64),
+                       b.ctx, isnothing(d) ? C_NULL : d.ptr, time_origin, step_seconds))
+
 # ---- a fixed sparse surface operator on the device (visualize/cache.jl:918-937, 983-1011) ---------------------------------
 # CSR over destination rows: `row_ptr` (0-based, n_rows + 1 entries), `col` (0-based interior cell numbers j·nx + i) and
 # `weight` (≥ 0) are host arrays, copied to the device at construction — a SparseMatrixCSC of ConservativeRegridding.jl goes

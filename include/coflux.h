@@ -48,7 +48,9 @@ extern "C" {
                           * likewise the surface monitor (cf_monitor_*, cf_attach_monitor); likewise cf_debug_prefetch_stats — with it
                           * a state requested ahead is matched by its source and weights as well, and a third pending request is
                           * refused when it is made: both stated at cf_prefetch_atmosphere_state; likewise the calendar-binned
-                          * means (cf_climatology_*, cf_calendar_bin, cf_attach_climatology) */
+                          * means (cf_climatology_*, cf_calendar_bin, cf_attach_climatology); likewise the staged dataset and
+                          * the restoring that follows it (cf_dataset_*, cf_materialize_dataset_restoring,
+                          * cf_attach_restoring_dataset) */
 
 /* status codes */
 #define CF_OK 0
@@ -1546,6 +1548,94 @@ int cf_calendar_bin(const double* edges, const int32_t* bin_of_interval, int32_t
 /* Footprint: the step loops' own, and cf_climatology_collect's at every collected step.                                */
 int cf_attach_climatology(cf_ctx* ctx, cf_climatology* c, int32_t stride, double step_weight, double time_origin,
                           double step_seconds, const double* edges, const int32_t* bin_of_interval, int32_t n_edges);
+
+/* ------------------------------------------------------------------------------------------
+ * A dataset staged on the device and followed in time: what salinity_surface_restoring builds —
+ * DatasetRestoring(Metadata(:salinity; dataset = WOAMonthly()), …; time_indices_in_memory = length(Smetadata))
+ * (omip_simulation.jl:507-523): twelve monthly fields, all resident, each land-inpainted on the dataset's own
+ * latitude–longitude grid, interpolated to the ocean grid and blended linearly in time, cyclically over the year — and what
+ * set!(T_init, Metadatum(…)) does for the initial conditions (omip_simulation.jl:614-615, :634-635; n_levels = 1).
+ * Still ABI 5: additive.  A dataset owns two f64 planes of the source grid and n_levels ocean-grid f64 arrays in the usual
+ * halo layout, zero-filled at create.
+ *   Staging.  cf_dataset_stage(d, level, h_plane) takes a host float[ns_y][ns_x], NaN = missing (the caller has mapped
+ *     _FillValue to NaN), and queues on the context's stream:
+ *       convert   the plane to f64, exactly;
+ *       inpaint   [UPSTREAM-RECALL inpaint_mask!, NearestNeighborInpainting; the definition here is this library's contract]
+ *                 one sweep reads plane p and writes plane q.  A cell that is not NaN is copied.  A NaN cell looks at its donors
+ *                 in the fixed order W (i − 1), S (j − 1), E (i + 1), N (j + 1); W and E wrap when periodic_x and are absent at
+ *                 the edge otherwise, S and N are absent beyond the first and last row.  With c ≥ 1 donors that are not NaN in
+ *                 p, q = (those donors added left to right in that order, starting from the first valid one) / (double)c in
+ *                 plain IEEE arithmetic (no contraction); with none q stays NaN.  The number of sweeps is
+ *                 min(max_sweeps, depth), depth = the largest 4-connected distance of a NaN cell from the nearest cell that is
+ *                 not NaN (x wraps when periodic) — the host holds the plane and finds it by one breadth-first pass, so
+ *                 exactly that many sweeps are queued: no device counter, no test of the plane, no synchronisation.  Cells
+ *                 still NaN afterwards (beyond max_sweeps; a plane with no valid cell) become fill_value.  A plane without
+ *                 NaN launches no sweep.  (An Inf is a valid donor.  Donors that sum to NaN — infinities of both signs — leave
+ *                 a NaN the sweep count does not know of: it stays in the plane, and stage_info counts the cell as filled.)
+ *                 sweeps_per_launch: 1 = one launch per sweep over the plane; 2 … 8 = that many sweeps per launch on
+ *                 overlapped LDS tiles (core + a halo of as many cells, wrapped or cut at the plane's edges; only the core is
+ *                 written back); 0 = the library's choice.  Same bits either way, and on any max_workgroups.
+ *       regrid    bilinear interpolation of the inpainted f64 plane onto the ring window W of the level's array through
+ *                 `weights` (fi / fj index the dataset's grid: periodic x, clamped y — cf_interpolate_land_freshwater's index
+ *                 arithmetic, no time blend).  Cells outside W keep their zeros.
+ *     The only host wait is for the upload of the stage call two before, should it still be in flight (two pinned slots).
+ *   Clock.  cf_dataset_time_index is a pure host function (no context, no device).  Cyclical (period > 0):
+ *     r = fmod(time − times[0], period), + period when r < 0; τ = times[0] + r; k with times[k] ≤ τ < times[k+1] gives
+ *     (k, k+1, (τ − times[k]) / (times[k+1] − times[k])); τ ≥ times[n−1] gives (n−1, 0, (τ − times[n−1]) / (times[0] + period −
+ *     times[n−1])).  Clamped (period == 0): below times[0] (0, 0, 0.0), at or beyond times[n−1] (n−1, n−1, 0.0).  n == 1:
+ *     always (0, 0, 0.0).  CF_ERR_INVALID for a time that is not finite or a bad table (times not finite or not strictly
+ *     increasing, n < 1, a period that is negative, not finite, or > 0 but not above times[n−1] − times[0], a NULL argument).
+ *   Evaluation.  S★ at a cell is level1's value when the fraction is 0.0 (level2 is not read), else b·f + a·(1 − f) in f64.
+ *     cf_dataset_evaluate writes it on W of d_out (a Metadatum initial condition: n_levels = 1).
+ *     cf_materialize_dataset_restoring is cf_materialize_salinity_restoring with S★ formed per cell: bit for bit
+ *     cf_dataset_evaluate followed by cf_materialize_salinity_restoring on that array, without the array.
+ *   cf_attach_restoring_dataset(ctx, d, time_origin, step_seconds): while attached, step s (global index) of
+ *     cf_time_steps_coupled runs its restoring job at time_origin + s · step_seconds — the time of the ocean state it reads —
+ *     inside the preamble's one launch: one more 8-byte load per wet cell on steps between two levels, no extra launch; a step
+ *     whose fraction is 0.0 runs the static target's own form on that level.  cf_coupled_step.target_salinity must then be
+ *     NULL (both given: CF_ERR_INVALID before anything is launched); with nothing attached a NULL target is refused as before.
+ *     A block without restoring_buffer has no restoring job and does not look at the dataset.  cf_time_steps ignores the
+ *     attachment.  The clock is the global step index and the dataset has no state that moves, so a run split into
+ *     CF_PIPELINE_CONTINUING calls, or across a checkpoint and pickup, restores toward the same bits.  One dataset per context;
+ *     NULL detaches; cf_dataset_destroy detaches too.
+ *   Accessors.  cf_dataset_level: a borrowed device pointer to a level's ocean-grid array.  cf_dataset_read_source: the
+ *     inpainted f64 plane of the most recently staged level into h_out[ns_y][ns_x]; synchronises (tests and debugging).
+ *     cf_dataset_stage_info: host bookkeeping of a staged level — sweeps queued, cells filled by a sweep, cells given fill_value.
+ *   Errors (CF_ERR_INVALID, nothing allocated or launched): a wrong struct_size, ns_x or ns_y < 2 or more than 2³¹ cells,
+ *     n_levels outside 1 … CF_DATASET_MAX_LEVELS, sweeps_per_launch outside 0 … 8, max_workgroups < 0, a fill_value that is
+ *     NaN, a bad times table or period, weights without fi / fj, a NULL plane, a level out of range, a dataset of another
+ *     context, evaluation / materialisation / attachment / a coupled call before every level is staged, a non-finite clock.
+ * Slabs: each context stages its own rows through its own weights; there is nothing to combine.
+ * ---------------------------------------------------------------------------------------- */
+#define CF_DATASET_MAX_LEVELS 32
+typedef struct cf_dataset_desc {
+    int32_t struct_size;        /* sizeof(cf_dataset_desc) */
+    int32_t ns_x, ns_y;         /* the dataset's own grid, ≥ 2 each */
+    int32_t n_levels;           /* 1 … CF_DATASET_MAX_LEVELS */
+    int32_t periodic_x;         /* 1: W / E donors wrap in x */
+    int32_t max_sweeps;         /* < 0: no limit */
+    int32_t sweeps_per_launch;  /* 0: the library's choice; 1 … 8 (scheduling only: never a bit of a result) */
+    int32_t max_workgroups;     /* 0: the library's choice; > 0 caps every launch (scheduling only) */
+    double fill_value;          /* what cells no sweep reached receive */
+    double period;              /* 0: clamped; else cyclical, above times[n_levels − 1] − times[0] */
+    const double* times;        /* host, n_levels finite strictly increasing level times; copied */
+    cf_interp_weights weights;  /* this context's grid → the dataset's grid, separable or 2-D; device arrays, borrowed */
+} cf_dataset_desc;
+typedef struct cf_dataset cf_dataset;
+int cf_dataset_create(cf_ctx* ctx, const cf_dataset_desc* desc, cf_dataset** out);
+int cf_dataset_destroy(cf_dataset* d);
+/* Footprint: reads h_plane in full and fi / fj as the atmosphere does; writes the level's array on W.                  */
+int cf_dataset_stage(cf_dataset* d, int32_t level, const float* h_plane);
+int cf_dataset_level(cf_dataset* d, int32_t level, const double** d_field);
+int cf_dataset_read_source(cf_dataset* d, double* h_out);
+int cf_dataset_stage_info(cf_dataset* d, int32_t level, int32_t* sweeps, int64_t* filled, int64_t* defaulted);
+int cf_dataset_time_index(const double* times, int32_t n, double period, double time, int32_t* level1, int32_t* level2, double* fraction);
+/* Footprint: reads one or two levels on W; writes d_out on W only.                                                     */
+int cf_dataset_evaluate(cf_dataset* d, double time, double* d_out);
+/* Footprint: reads one or two levels, S, mask on I; writes d_buffer on I only (0 on land).                             */
+int cf_materialize_dataset_restoring(cf_ctx* ctx, double piston_velocity /* m/s */, cf_dataset* d, double time,
+                                     const cf_ocean_surface* ocean, double* d_buffer);
+int cf_attach_restoring_dataset(cf_ctx* ctx, cf_dataset* d, double time_origin, double step_seconds);
 
 /* ------------------------------------------------------------------------------------------
  * A fixed sparse surface operator applied on the device: the conservative regridding of surface fields onto the shared
