@@ -14,6 +14,18 @@
 static std::mutex g_peer_mutex;
 static std::map<std::string, std::pair<char*, int>> g_peer_local;  // handle bytes → (mailbox, device)
 
+// What a mailbox was exported for, carried by the mailbox itself: in the spare bytes of its first flag line (a flag line uses
+// 8 of its 64 bytes, and the kernels touch only those 8), written once at export and read back with a device-to-host copy by
+// cf_peer_halo_connect — of an IPC-mapped mailbox and of one of the same process alike.  A rank addresses its NEIGHBOUR's
+// mailbox with its OWN slot size max_fields · max_rows · sj, so the two must have been exported for one shape on one width.
+struct PeerShapeNote {
+    unsigned long long magic;
+    int max_fields, max_rows, sj, pad;
+};
+constexpr unsigned long long PEER_SHAPE_MAGIC = 0x636f666c75786d62ull;  // "cofluxmb"
+constexpr size_t PEER_SHAPE_OFFSET = 16;                                // inside flag line 0, clear of its 8-byte flag
+static_assert(PEER_SHAPE_OFFSET >= 8 && PEER_SHAPE_OFFSET + sizeof(PeerShapeNote) <= 64, "the note stays inside the first flag line");
+
 static int ensure_aux_stream(cf_ctx* ctx) {
     if (ctx->aux.stream) return CF_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -114,6 +126,8 @@ int cf_peer_halo_export(cf_ctx* ctx, int max_fields, int max_rows, void* handle_
                     hipGetErrorString(e));
     }
     HIP_TRY(ctx, hipMemset(mailbox.get(), 0, bytes));
+    const PeerShapeNote note{PEER_SHAPE_MAGIC, max_fields, max_rows, ctx->grid.sj, 0};
+    HIP_TRY(ctx, hipMemcpy(mailbox.get() + PEER_SHAPE_OFFSET, &note, sizeof note, hipMemcpyHostToDevice));
     if (!ctx->d_peer_status) {
         HIP_TRY(ctx, status.create(sizeof(int)));
         HIP_TRY(ctx, hipMemset(status.get(), 0, sizeof(int)));
@@ -171,6 +185,29 @@ static int map_mailbox(cf_ctx* ctx, const void* handle, char** out, cf::IpcMappi
     return CF_OK;
 }
 
+// the neighbour's mailbox was exported for this context's shape on this context's row length (launches nothing: one copy)
+static int check_mailbox_shape(cf_ctx* ctx, const char* mailbox, const char* which) {
+    if (!mailbox) return CF_OK;
+    PeerShapeNote theirs{};
+    HIP_TRY(ctx, hipMemcpy(&theirs, mailbox + PEER_SHAPE_OFFSET, sizeof theirs, hipMemcpyDeviceToHost));
+    if (theirs.magic != PEER_SHAPE_MAGIC)
+        return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: the %s handle is not a mailbox of cf_peer_halo_export", which);
+    if (theirs.max_fields != ctx->peer_max_fields || theirs.max_rows != ctx->peer_max_rows || theirs.sj != ctx->grid.sj)
+        return fail(ctx, CF_ERR_INVALID,
+                    "cf_peer_halo_connect: the %s neighbour's mailbox is (max_fields, max_rows, nx + 2hx) = (%d, %d, %d), this rank's "
+                    "is (%d, %d, %d): all ranks export one shape on one grid width",
+                    which, theirs.max_fields, theirs.max_rows, theirs.sj, ctx->peer_max_fields, ctx->peer_max_rows, ctx->grid.sj);
+    return CF_OK;
+}
+
+// cf_peer_halo_connect that did not succeed leaves the context without neighbours, whatever it had before
+static void disconnect_peers(cf_ctx* ctx) {
+    ctx->peer_connected = false;
+    ctx->peer.south = ctx->peer.north = nullptr;
+    ctx->peer_south_map.reset();
+    ctx->peer_north_map.reset();
+}
+
 int cf_peer_halo_connect(cf_ctx* ctx, const void* south_handle, const void* north_handle, int rank, int nranks) {
     if (!ctx || nranks <= 0 || rank < 0 || rank >= nranks) return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: bad arguments");
     if (!ctx->peer_mine) return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: call cf_peer_halo_export first");
@@ -178,8 +215,14 @@ int cf_peer_halo_connect(cf_ctx* ctx, const void* south_handle, const void* nort
         return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: rank %d of %d needs %s south and %s north handle", rank, nranks,
                     rank > 0 ? "a" : "no", rank < nranks - 1 ? "a" : "no");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    CHECK(map_mailbox(ctx, south_handle, &ctx->peer.south, &ctx->peer_south_map));
-    CHECK(map_mailbox(ctx, north_handle, &ctx->peer.north, &ctx->peer_north_map));
+    int rc = map_mailbox(ctx, south_handle, &ctx->peer.south, &ctx->peer_south_map);
+    if (rc == CF_OK) rc = map_mailbox(ctx, north_handle, &ctx->peer.north, &ctx->peer_north_map);
+    if (rc == CF_OK) rc = check_mailbox_shape(ctx, ctx->peer.south, "south");
+    if (rc == CF_OK) rc = check_mailbox_shape(ctx, ctx->peer.north, "north");
+    if (rc != CF_OK) {
+        disconnect_peers(ctx);
+        return rc;
+    }
     ctx->rank = rank;
     ctx->nranks = nranks;
     ctx->peer_connected = true;

@@ -920,7 +920,16 @@ int cf_halo_exchange_rows(cf_ctx* ctx, double* const* d_fields, int nfields, int
  *   cf_peer_halo_connect  map the south (rank−1) and north (rank+1) mailboxes; NULL at the ends of the slab ring.
  *                         On the LAST rank of a tripolar grid the north handle is NULL too: its north boundary is the
  *                         fold (one_degree_tripolar.jl:48-51), served locally by cf_fold_north_halo, not by a peer.
- *   cf_halo_exchange_rows_peer   the per-step exchange, same meaning as cf_halo_exchange_rows.
+ *                         ALL RANKS EXPORT ONE SHAPE ON ONE GRID WIDTH: a rank addresses its neighbour's mailbox with the
+ *                         slot size of its own, max_fields · max_rows · (nx + 2hx).  Every mailbox carries the triple
+ *                         (max_fields, max_rows, nx + 2hx) it was exported for, and cf_peer_halo_connect compares each
+ *                         neighbour's with this context's: on a difference it returns CF_ERR_INVALID with both triples in
+ *                         the message, launches nothing and leaves the context unconnected (cf_halo_exchange_rows_peer
+ *                         then answers as if cf_peer_halo_connect had not been called), whatever it was connected to before.
+ *   cf_halo_exchange_rows_peer   the per-step exchange, same meaning as cf_halo_exchange_rows: 1 … max_fields fields ×
+ *                         1 … min(max_rows, ny) rows per call.  Inside the mailbox slot of the call's sequence parity, field f
+ *                         lies at f · rows · (nx + 2hx) doubles with the call's own `rows`, so `nfields` and `rows` of a
+ *                         step's call ARE THE SAME ON EVERY RANK.  That is the caller's contract and is not checked.
  * A spin that exceeds its bound sets a sticky error that the next cf_sync reports (CF_ERR_COMM).            */
 #define CF_PEER_HANDLE_BYTES 64
 int cf_peer_halo_export(cf_ctx* ctx, int max_fields, int max_rows, void* handle_out);
