@@ -18,7 +18,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from .models import EARTH_RADIUS
+from .grids import EARTH_RADIUS
 
 
 @dataclass

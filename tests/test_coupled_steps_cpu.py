@@ -124,9 +124,9 @@ def test_the_two_clocks_cross_level_boundaries_at_different_steps():
 
 def test_models_clock_rebasing_reproduces_the_host_clock():
     """models.time_steps holds the device loop's clock (fraction + step · increment) to time_step!'s (t / Δt_snapshot): the
-    pair _device_clock returns gives exactly the wanted level and fraction at its step, for a Δt that is no binary fraction of
+    pair device_clock returns gives exactly the wanted level and fraction at its step, for a Δt that is no binary fraction of
     the snapshot interval, from any starting iteration."""
-    from coflux import models
+    from coflux import clocks
     dt, interval, n = 1200.0, 10800.0, 7
     inc = dt / interval
     for first in (0, 5, 1000, 26279):
@@ -136,6 +136,6 @@ def test_models_clock_rebasing_reproduces_the_host_clock():
             x = t / interval
             base = int(np.floor(x))
             want = (base % n, (base + 1) % n, x - base)
-            c = models._device_clock(want[0], want[2], n, s, inc)
+            c = clocks.device_clock(want[0], want[2], n, s, inc)
             assert c is not None, (first, s)
-            assert models._clock_at(c[0], c[1], n, s, inc) == want, (first, s)
+            assert clocks.clock_at(c[0], c[1], n, s, inc) == want, (first, s)

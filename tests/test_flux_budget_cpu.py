@@ -305,8 +305,8 @@ def fake_model(sea_ice=True):
     grid = SimpleNamespace(size=(NX, NY, 1), halo=(HX, HY, 1), longitude=(0.0, 360.0))
     itf = SimpleNamespace(context=ctx, weights=dict(latitude=z()), _grid_rotation=None, net_fluxes=SimpleNamespace(_ocean_fields={}),
                           atmosphere_ocean_interface=SimpleNamespace(_fields=dict(sensible_heat=z(), latent_heat=z(), water_vapor=z(), temperature=z())),
-                          _exchange_sets=[dict(Qs=z(), Ql=z(), Mp=z()), None], _exchange_current=0, land_freshwater=z())
-    itf.exchange_atmosphere_state = itf._exchange_sets[0]
+                          exchange=cm.ExchangeStates(ctx, dict(Qs=z(), Ql=z(), Mp=z())), land_freshwater=z())
+    itf.exchange_atmosphere_state = itf.exchange.stable
     ice = SimpleNamespace(fields=lambda: dict(concentration=conc, interface_heat=qio, x_stress=tx), frazil_heat=z()) if sea_ice else None
     conc, qio, tx = z(), z(), z()
     ocean = SimpleNamespace(grid=grid, surface_state=lambda: dict(T=z(), S=z(), u=z(), v=z(), mask=None))
@@ -332,7 +332,7 @@ def test_surface_flux_averages_groups_budget_terms_after_the_others():
     assert set(inputs["ice"]) == {"concentration", "interface_heat"}                 # the stresses are no input
     # the exchange fields are the writer's own three, filled from the current set before a collection
     assert inputs["atmos"] is w._budget_atmos and set(w._budget_atmos) == {"Qs", "Ql", "Mp"}
-    live = model.interfaces._exchange_sets[0]
+    live = model.interfaces.exchange.stable
     live["Qs"] += 3.0
     w.stage_exchange(live)
     assert torch.equal(w._budget_atmos["Qs"], live["Qs"]) and w._budget_atmos["Qs"].data_ptr() != live["Qs"].data_ptr()

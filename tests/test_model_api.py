@@ -82,7 +82,7 @@ def test_run_requests_every_next_state_and_gives_the_bits_of_the_plain_loop():
         if piped:
             held = coupled.interfaces.exchange_atmosphere_state        # what an output writer would hold on to
             cm.run(cm.Simulation(coupled, dt=50 * cm.minutes, stop_iteration=8))
-            assert coupled.interfaces._exchange_other is not None
+            assert coupled.interfaces.exchange.other is not None
             # outside run! the public field set is the one handed out before it, with the state at the model's clock in it
             assert coupled.interfaces.exchange_atmosphere_state is held
             # ... and a step taken by hand afterwards does not mistake the state run! had requested ahead for its own
@@ -93,7 +93,7 @@ def test_run_requests_every_next_state_and_gives_the_bits_of_the_plain_loop():
             for _ in range(9):
                 cm.time_step(coupled, 50 * cm.minutes)
             coupled.interfaces.context.sync()
-            assert coupled.interfaces._exchange_other is None
+            assert coupled.interfaces.exchange.other is None
         bc = ocean.model.top_boundary_conditions
         fields = dict(u=bc.u, v=bc.v, T=bc.T, S=bc.S, Qc=coupled.interfaces.atmosphere_ocean_interface.fluxes.sensible_heat,
                       **{"atmos_" + k: v for k, v in coupled.interfaces.exchange_atmosphere_state.items()})
