@@ -11,6 +11,8 @@ import numpy as np
 ABI_VERSION = 5   # 5: SKIN_LINEARISED
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
+PEER_REDUCE_MAX_RANKS = 8
+NORMALIZE_EXACT = 2   # cf_coupled_step.normalize_salinity: cf_normalize_salinity_flux_exact
 HALO_NONE, HALO_RCCL, HALO_PEER = 0, 1, 2
 FOLD_CENTER, FOLD_X_FACE, FOLD_Y_FACE = 0, 1, 2
 SKIN_EXPLICIT, SKIN_SEMI_IMPLICIT, SKIN_LINEARISED = 0, 1, 2
@@ -353,6 +355,7 @@ EXPORTED_SYMBOLS = (
     "cf_dataset_time_index", "cf_dataset_evaluate", "cf_materialize_dataset_restoring", "cf_attach_restoring_dataset",
     "cf_regrid_create", "cf_regrid_destroy", "cf_regrid_apply",
     "cf_prepare_coupled_step", "cf_time_steps_coupled",
+    "cf_normalize_salinity_flux_exact", "cf_debug_salinity_sums_exact", "cf_peer_reduce_export", "cf_peer_reduce_connect",
     "cf_checkpoint_create", "cf_checkpoint_destroy", "cf_checkpoint_add_array", "cf_checkpoint_add_average", "cf_checkpoint_add_climatology",
     "cf_checkpoint_add_integrals", "cf_checkpoint_add_monitor", "cf_checkpoint_set_host_blob", "cf_checkpoint_capture", "cf_checkpoint_wait",
     "cf_checkpoint_restore", "cf_checkpoint_verify", "cf_checkpoint_hash", "cf_checkpoint_host_blob",
@@ -440,6 +443,10 @@ def load_library(path=None):
         C.POINTER(ExchangeFields), C.POINTER(InterfaceFluxes), C.POINTER(SeaIceFields),
         C.POINTER(NetOceanFluxes)]
     lib.cf_normalize_salinity_flux.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.cf_normalize_salinity_flux_exact.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.cf_debug_salinity_sums_exact.argtypes = [vp, vp, vp, vp, vp, c_double_p, C.POINTER(C.c_ulonglong)]
+    lib.cf_peer_reduce_export.argtypes = [vp, vp]
+    lib.cf_peer_reduce_connect.argtypes = [vp, vp, C.c_int, C.c_int]
     lib.cf_default_sea_ice_params.argtypes = [C.POINTER(SeaIceParams)]
     lib.cf_set_sea_ice_formulation.argtypes = [vp, C.POINTER(FluxParams), C.POINTER(SeaIceParams)]
     lib.cf_compute_atmosphere_sea_ice_fluxes.argtypes = [

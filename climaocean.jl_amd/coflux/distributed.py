@@ -124,3 +124,31 @@ class SlabHaloExchanger:
             self.ctx.halo_exchange_rows_peer(tensors, self.rows)
         elif self.backend == "torch":
             exchange_halo_rows_torch(tensors, self.ny, self.hy, self.rows)
+
+
+def connect_coupled_slabs(ctx, max_fields=8, rows=None):
+    """What cf_time_steps_coupled needs under CF_HALO_PEER: exports this rank's halo mailbox (`max_fields` fields × `rows` rows,
+    ring + 1 by default) and its reduce mailbox, gathers the handles of both over torch.distributed and connects — the slab
+    neighbours for the halo rows, every rank for the exact sums (cf_peer_halo_connect, cf_peer_reduce_connect).  A world of one
+    (or no process group) connects to nobody: nothing ever waits.  Every rank reaches the gather whatever happened locally, and
+    every rank raises when an export failed anywhere, as SlabHaloExchanger agrees on its backend."""
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    rows = rows if rows is not None else ctx.grid.ring + 1
+    mine, failure = None, None
+    try:
+        mine = (ctx.peer_halo_export(max_fields=max_fields, max_rows=rows), ctx.peer_reduce_export())
+    except Exception as exc:  # noqa: BLE001 — reported below, on every rank
+        failure = f"rank {rank}: {exc}"
+    gathered = [(mine, failure)]
+    if world > 1:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, (mine, failure))
+    failures = [f for _, f in gathered if f is not None]
+    if failures:
+        raise RuntimeError("no peer-direct mailboxes: " + "; ".join(failures))
+    halo = [h for (h, _r), _ in gathered]
+    reduce = [r for (_h, r), _ in gathered]
+    ctx.peer_halo_connect(halo[rank - 1] if rank > 0 else None, halo[rank + 1] if rank < world - 1 else None, rank, world)
+    ctx.peer_reduce_connect(reduce, rank, world)
+    return rank, world

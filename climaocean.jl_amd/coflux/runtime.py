@@ -365,6 +365,20 @@ class FluxContext:
         self._check(self.lib.cf_normalize_salinity_flux(self._h, _ptr(flux), _ptr(additional), _ptr(area), _ptr(mask),
                                                         _ptr(mean_out)), "cf_normalize_salinity_flux")
 
+    def normalize_salinity_flux_exact(self, flux, mask, additional=None, area=None, mean_out=None):
+        """NormalizeSalinity with exact sums (cf_normalize_salinity_flux_exact): the mean's bits do not depend on how the globe is
+        cut into slabs; summed over the reduction world when one is connected on more than one rank (peer_reduce_connect)."""
+        self._check(self.lib.cf_normalize_salinity_flux_exact(self._h, _ptr(flux), _ptr(additional), _ptr(area), _ptr(mask),
+                                                              _ptr(mean_out)), "cf_normalize_salinity_flux_exact")
+
+    def debug_salinity_sums_exact(self, flux, mask, additional=None, area=None):
+        """This rank's exact sums (fl(Σ fl(fl(flux + additional) · area)), fl(Σ area)) over the wet interior and the counts of
+        NaN, +Inf and −Inf terms of the first (cf_debug_salinity_sums_exact).  Synchronises; writes nothing to `flux`."""
+        sums, counts = (C.c_double * 2)(), (C.c_ulonglong * 3)()
+        self._check(self.lib.cf_debug_salinity_sums_exact(self._h, _ptr(flux), _ptr(additional), _ptr(area), _ptr(mask), sums, counts),
+                    "cf_debug_salinity_sums_exact")
+        return (sums[0], sums[1]), tuple(int(c) for c in counts)
+
     def profile_enable(self, max_records):
         self._check(self.lib.cf_profile_enable(self._h, max_records), "cf_profile_enable")
 
@@ -477,7 +491,11 @@ class FluxContext:
             k.compute_ice_ocean, k.ice_ocean = 1, ice_ocean_params
         k.ice_ocean_fluxes = self._struct(abi.IceOceanFluxes, ice_ocean_fluxes, ("interface_heat", "salt_flux", "frazil_heat", "friction_velocity"))
         k.piston_velocity, k.target_salinity, k.restoring_buffer = float(piston_velocity), _ptr(target), _ptr(restoring_out)
-        k.normalize_salinity, k.area, k.mean_out = int(bool(normalize)), _ptr(area), _ptr(mean_out)
+        # normalize: False / True (cf_normalize_salinity_flux) / "exact" (cf_normalize_salinity_flux_exact: abi.NORMALIZE_EXACT)
+        if isinstance(normalize, str) and normalize != "exact":
+            raise ValueError(f'normalize = {normalize!r}: False, True or "exact"')
+        k.normalize_salinity = abi.NORMALIZE_EXACT if isinstance(normalize, str) and normalize == "exact" else int(bool(normalize))
+        k.area, k.mean_out = _ptr(area), _ptr(mean_out)
         k._keep = (st, ice_states, skin_temperature, ai_fluxes, net_ice, friver, licalvf, land_out, ice_ocean_fluxes, target, restoring_out,
                    area, mean_out)
         return k
@@ -635,6 +653,21 @@ class FluxContext:
         sb = C.create_string_buffer(south, abi.PEER_HANDLE_BYTES) if south is not None else None
         nb = C.create_string_buffer(north, abi.PEER_HANDLE_BYTES) if north is not None else None
         self._check(self.lib.cf_peer_halo_connect(self._h, sb, nb, rank, nranks), "cf_peer_halo_connect")
+
+    def peer_reduce_export(self):
+        """This context's reduce mailbox as a HIP IPC handle (cf_peer_reduce_export)."""
+        buf = C.create_string_buffer(abi.PEER_HANDLE_BYTES)
+        self._check(self.lib.cf_peer_reduce_export(self._h, buf), "cf_peer_reduce_export")
+        return buf.raw
+
+    def peer_reduce_connect(self, handles, rank, nranks):
+        """Join the reduction world of the exact sums (cf_peer_reduce_connect): `handles` is every rank's handle in rank order
+        (None for a world of one)."""
+        blob = None
+        if handles is not None:
+            assert len(handles) == nranks and all(len(h) == abi.PEER_HANDLE_BYTES for h in handles)
+            blob = C.create_string_buffer(b"".join(handles), nranks * abi.PEER_HANDLE_BYTES)
+        self._check(self.lib.cf_peer_reduce_connect(self._h, blob, rank, nranks), "cf_peer_reduce_connect")
 
     def peer_halo_stats(self):
         """(exchanges issued, of which as riders of a solver launch: CF_OPT_HALO_IN_SOLVER_LAUNCH)."""

@@ -487,6 +487,7 @@ int cf_destroy(cf_ctx* ctx) {
     for (hipStream_t s : {ctx->comm_lane.stream.get(), ctx->aux.stream.get(), ctx->own_stream.get()})
         if (s) (void)hipStreamSynchronize(s);
     if (ctx->peer_mine) cf_peer_forget_local(ctx->peer_mine.get());
+    if (ctx->reduce_mine) cf_peer_forget_local(ctx->reduce_mine.get());
     delete ctx;   // every member releases itself (coflux_owned.hpp)
     return CF_OK;
 }
@@ -619,13 +620,14 @@ int cf_sync(cf_ctx* ctx) {
     CHECK(cf_ahead_perform(ctx, &flush));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->aux.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux.stream.get()));
-    if (ctx->d_peer_status && ctx->peer_seq) {  // a peer-direct exchange whose neighbour never arrived
+    if (ctx->d_peer_status && (ctx->peer_seq || ctx->reduce_seq)) {  // a peer-direct exchange whose neighbour never arrived
         int st = 0;
         HIP_TRY(ctx, hipMemcpy(&st, ctx->d_peer_status.get(), sizeof st, hipMemcpyDeviceToHost));
         if (st) {
             // reported ONCE: the caller may fall back to another exchange (bench.py does) and go on with this context — the
             // mailbox protocol's sequence numbers only grow, a late arrival of the missed step disturbs nothing
             HIP_TRY(ctx, hipMemset(ctx->d_peer_status.get(), 0, sizeof st));
+            if (st == 3) return fail(ctx, CF_ERR_COMM, "exact sum over the reduction world timed out waiting for another rank's accumulators");
             return fail(ctx, CF_ERR_COMM, "peer-direct halo exchange timed out waiting for the %s neighbour's rows",
                         st == 1 ? "south" : "north");
         }
@@ -1554,6 +1556,55 @@ int cf_normalize_salinity_flux(cf_ctx* ctx, double* d_flux, const double* d_addi
     if (ctx->comm && ctx->nranks > 1)  // the only collective near the path: two doubles
         NCCL_TRY(ctx, g_rccl.AllReduce(sums, sums, 2, ncclFloat64, ncclSum, ctx->comm, ctx->stream));
     HIP_TRY(ctx, launch_salinity_subtract(ctx->stream, ctx->grid, d_flux, sums, d_mean_out));
+    return CF_OK;
+}
+
+// the accumulator pair, the sums and the counts of the exact form (zeroed once: the finishing kernel leaves the pair zero)
+static int ensure_exact_buffers(cf_ctx* ctx) {
+    if (ctx->d_exact) return CF_OK;
+    cf::DeviceBuffer<unsigned long long> b;
+    const size_t bytes = sizeof(unsigned long long) * (2 * XS_WORDS + 2 + XS_COUNTERS);
+    HIP_TRY(ctx, b.create(bytes));
+    HIP_TRY(ctx, hipMemsetAsync(b.get(), 0, bytes, ctx->stream));
+    ctx->d_exact = std::move(b);
+    return CF_OK;
+}
+
+int cf_normalize_salinity_flux_exact(cf_ctx* ctx, double* d_flux, const double* d_additional, const double* d_area,
+                                     const void* d_mask, double* d_mean_out) {
+    if (!ctx || !d_flux) return fail(ctx, CF_ERR_INVALID, "cf_normalize_salinity_flux_exact: bad arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->dev.mask_kind != CF_MASK_NONE && !d_mask)
+        return fail(ctx, CF_ERR_INVALID, "mask_kind = %d but the mask is NULL", ctx->dev.mask_kind);
+    CHECK(ensure_exact_buffers(ctx));
+    unsigned long long* pair = ctx->d_exact.get();
+    double* sums = reinterpret_cast<double*>(pair + 2 * XS_WORDS);
+    HIP_TRY(ctx, launch_exact_sums(ctx->stream, ctx->dev, ctx->grid, d_flux, d_additional, d_area, d_mask, pair));
+    // every rank counts its reductions: the same number names the same sum everywhere — counted once the kernel is queued
+    const bool world = ctx->reduce_connected && ctx->reduce.nranks > 1;
+    ReduceWorld alone{nullptr, nullptr, 0, 1};
+    HIP_TRY(ctx, launch_exact_finish(ctx->stream, pair, world ? ctx->reduce : alone, ctx->reduce_seq + 1, ctx->d_peer_status.get(), sums, nullptr));
+    if (world) ++ctx->reduce_seq;
+    HIP_TRY(ctx, launch_salinity_subtract(ctx->stream, ctx->grid, d_flux, sums, d_mean_out));
+    return CF_OK;
+}
+
+int cf_debug_salinity_sums_exact(cf_ctx* ctx, const double* d_flux, const double* d_additional, const double* d_area, const void* d_mask,
+                                 double sums_out[2], unsigned long long nonfinite_out[3]) {
+    if (!ctx || !d_flux || !sums_out || !nonfinite_out) return fail(ctx, CF_ERR_INVALID, "cf_debug_salinity_sums_exact: bad arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->dev.mask_kind != CF_MASK_NONE && !d_mask)
+        return fail(ctx, CF_ERR_INVALID, "mask_kind = %d but the mask is NULL", ctx->dev.mask_kind);
+    CHECK(ensure_exact_buffers(ctx));
+    unsigned long long* pair = ctx->d_exact.get();
+    double* sums = reinterpret_cast<double*>(pair + 2 * XS_WORDS);
+    unsigned long long* counts = pair + 2 * XS_WORDS + 2;
+    HIP_TRY(ctx, launch_exact_sums(ctx->stream, ctx->dev, ctx->grid, d_flux, d_additional, d_area, d_mask, pair));
+    const ReduceWorld alone{nullptr, nullptr, 0, 1};   // this rank's sums only: no reduction is issued
+    HIP_TRY(ctx, launch_exact_finish(ctx->stream, pair, alone, 0, nullptr, sums, counts));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(sums_out, sums, 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(nonfinite_out, counts, XS_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return CF_OK;
 }
 

@@ -181,6 +181,14 @@ struct cf_ctx {
     bool peer_connected = false;
     unsigned long long peer_seq = 0;
     cf::DeviceBuffer<int> d_peer_status;
+    // the exact sums of cf_normalize_salinity_flux_exact (coflux_exact_sum.hip) and their reduction world (cf_peer_reduce_*)
+    cf::DeviceBuffer<unsigned long long> d_exact;        // [2 · XS_WORDS: the accumulator pair][2 doubles: the sums][3: non-finite counts]
+    ReduceWorld reduce{nullptr, nullptr, 0, 1};          // raw views of the three below
+    cf::DeviceBuffer<char> reduce_mine;                  // this context's reduce mailbox (fine-grained)
+    cf::IpcMapping reduce_maps[REDUCE_MAX_RANKS];        // the other ranks', where they were opened through HIP IPC
+    cf::DeviceBuffer<char*> d_reduce_peers;              // device table of the REDUCE_MAX_RANKS mailboxes
+    bool reduce_connected = false;
+    unsigned long long reduce_seq = 0;                   // reductions issued over the world (every rank counts the same)
     // the peer-direct exchange as riders of the solver launch (CF_OPT_HALO_IN_SOLVER_LAUNCH; coflux_lean_kernel.hpp, HALO)
     int halo_in_launch = 0;
     unsigned long long halo_in_launch_count = 0;            // exchanges that rode in a solver launch (cf_peer_halo_stats)

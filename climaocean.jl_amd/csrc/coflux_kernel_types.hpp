@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "coflux_device.hpp"
+#include "coflux_exact_sum.hpp"
 
 namespace coflux {
 
@@ -126,6 +127,27 @@ struct HaloRider {
     int pad[2];
 };
 static_assert(sizeof(HaloRider) % 8 == 0, "argument bundles are made of 8-byte words");
+
+// The reduction world of the exact sums (cf_peer_reduce_*; coflux_exact_sum.hip): every rank's mailbox, mapped into every other
+// rank.  A mailbox is one 64-byte line that says what it is (ReduceNote), one flag line per (parity, rank) and one slot per
+// (parity, rank): the accumulator pair (Σ J·A, Σ A) of that rank, digits and counters, as REDUCE_SLOT_WORDS 64-bit words.
+constexpr int REDUCE_MAX_RANKS = 8;   // CF_PEER_REDUCE_MAX_RANKS
+constexpr int REDUCE_SLOT_WORDS = 2 * XS_WORDS;
+constexpr size_t REDUCE_FLAG_OFFSET = 64;
+constexpr size_t REDUCE_SLOT_OFFSET = REDUCE_FLAG_OFFSET + 2 * REDUCE_MAX_RANKS * 64;
+constexpr size_t REDUCE_MAILBOX_BYTES = REDUCE_SLOT_OFFSET + 2 * REDUCE_MAX_RANKS * REDUCE_SLOT_WORDS * sizeof(unsigned long long);
+constexpr unsigned REDUCE_LAYOUT_VERSION = 1;
+struct ReduceNote {
+    unsigned long long magic;
+    unsigned version, max_ranks, slot_words, pad;
+    unsigned long long bytes;
+};
+static_assert(sizeof(ReduceNote) <= REDUCE_FLAG_OFFSET, "the note stays inside its own line");
+struct ReduceWorld {
+    char* mine;           // this rank's mailbox (nullptr: no world)
+    char* const* peers;   // device table of REDUCE_MAX_RANKS mailboxes: entry r is rank r's (this rank's own at `rank`)
+    int rank, nranks;     // nranks = 1: nothing is sent, nothing waits
+};
 
 struct FoldFields {
     double* ptr[PEER_MAX_FIELDS];

@@ -184,6 +184,15 @@ hipError_t launch_salinity_partial_sums(hipStream_t st, const DevParams& P, cons
                                         int nblocks, double* sums);
 hipError_t launch_salinity_subtract(hipStream_t st, const GridDesc& G, double* flux, const double* sums, double* mean_out);
 hipError_t launch_debug_eval(hipStream_t st, const LaunchCfg& L, int fn, int n, const double* x, double* y);
+// cf_normalize_salinity_flux_exact (coflux_exact_sum.hip): the wet interior's Σ fl(fl(flux + additional) · area) and Σ area into the
+// accumulator pair (2 · XS_WORDS words, integer atomics), then one workgroup that joins the reduction world's pairs, rounds once
+// into sums[0 … 1] and zeroes the pair; `nonfinite` (or NULL): the NaN / +Inf / −Inf term counts of the first sum
+constexpr int EXACT_SUM_BLOCKS = 512;
+struct ReduceWorld;
+hipError_t launch_exact_sums(hipStream_t st, const DevParams& P, const GridDesc& G, const double* flux, const double* additional,
+                             const double* area, const void* mask, unsigned long long* accumulator);
+hipError_t launch_exact_finish(hipStream_t st, unsigned long long* accumulator, const ReduceWorld& W, unsigned long long seq, int* d_status,
+                               double* sums, unsigned long long* nonfinite);
 struct PeerMailbox;
 struct PeerFields;
 struct FoldFields;

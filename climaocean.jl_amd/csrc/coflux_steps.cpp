@@ -1,6 +1,7 @@
 // coflux_steps.cpp — what surrounds update_state! in a multi-step, multi-GPU run (include/coflux.h):
 //   * cf_prefetch_atmosphere_state: the next step's interpolation on an auxiliary stream,
 //   * cf_peer_halo_*: latitude-slab halo rows through HIP-IPC-mapped mailboxes (coflux_halo.hip),
+//   * cf_peer_reduce_*: the reduction world of the exact sums, every rank's mailbox mapped by every other (coflux_exact_sum.hip),
 //   * cf_fold_north_halo: the tripolar fold on the last slab,
 //   * cf_time_steps: run!(simulation) of a prescribed-ocean coupled model without returning to the host language.
 #include <map>
@@ -267,6 +268,101 @@ int cf_peer_halo_stats(cf_ctx* ctx, unsigned long long* exchanges, unsigned long
     return CF_OK;
 }
 
+// ---- the reduction world of the exact sums ------------------------------------------------------
+constexpr unsigned long long REDUCE_MAGIC = 0x636f666c75787264ull;  // "cofluxrd"
+
+int cf_peer_reduce_export(cf_ctx* ctx, void* handle_out) {
+    if (!ctx || !handle_out) return fail(ctx, CF_ERR_INVALID, "cf_peer_reduce_export: NULL argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->reduce_mine) return fail(ctx, CF_ERR_INVALID, "cf_peer_reduce_export: this context already has a reduce mailbox");
+    cf::DeviceBuffer<char> mailbox;
+    cf::DeviceBuffer<int> status;
+    // fine-grained, for the reason of the halo mailbox: the other ranks' stores and this rank's polling loads meet in memory
+    hipError_t e = mailbox.create_fine_grained(REDUCE_MAILBOX_BYTES);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, CF_ERR_COMM, "cf_peer_reduce_export: no fine-grained device memory for the reduce mailbox (%s)", hipGetErrorString(e));
+    }
+    HIP_TRY(ctx, hipMemset(mailbox.get(), 0, REDUCE_MAILBOX_BYTES));
+    const ReduceNote note{REDUCE_MAGIC, REDUCE_LAYOUT_VERSION, (unsigned)REDUCE_MAX_RANKS, (unsigned)REDUCE_SLOT_WORDS, 0, REDUCE_MAILBOX_BYTES};
+    HIP_TRY(ctx, hipMemcpy(mailbox.get(), &note, sizeof note, hipMemcpyHostToDevice));
+    if (!ctx->d_peer_status) {
+        HIP_TRY(ctx, status.create(sizeof(int)));
+        HIP_TRY(ctx, hipMemset(status.get(), 0, sizeof(int)));
+    }
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    hipIpcMemHandle_t h;
+    std::memset(&h, 0, sizeof h);
+    e = hipIpcGetMemHandle(&h, mailbox.get());
+    if (e != hipSuccess) return fail(ctx, CF_ERR_HIP, "hipIpcGetMemHandle on the reduce mailbox: %s", hipGetErrorString(e));
+    if (status) ctx->d_peer_status = std::move(status);
+    ctx->reduce_mine = std::move(mailbox);
+    std::memset(handle_out, 0, CF_PEER_HANDLE_BYTES);
+    std::memcpy(handle_out, &h, sizeof h);
+    {
+        std::lock_guard<std::mutex> lock(g_peer_mutex);
+        g_peer_local[std::string((const char*)handle_out, CF_PEER_HANDLE_BYTES)] = {ctx->reduce_mine.get(), ctx->device};
+    }
+    return CF_OK;
+}
+
+// cf_peer_reduce_connect that did not succeed leaves the context without a world, whatever it had before
+static void disconnect_reduce_world(cf_ctx* ctx) {
+    ctx->reduce_connected = false;
+    ctx->reduce = ReduceWorld{nullptr, nullptr, 0, 1};
+    for (cf::IpcMapping& m : ctx->reduce_maps) m.reset();
+}
+
+int cf_peer_reduce_connect(cf_ctx* ctx, const void* handles, int rank, int nranks) {
+    if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
+    if (!ctx->reduce_mine) return fail(ctx, CF_ERR_INVALID, "cf_peer_reduce_connect: call cf_peer_reduce_export first");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // (a kernel of an earlier world may still be queued: it reads the table this call rewrites)
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    disconnect_reduce_world(ctx);
+    if (nranks < 1 || nranks > CF_PEER_REDUCE_MAX_RANKS || rank < 0 || rank >= nranks || (nranks > 1 && !handles))
+        return fail(ctx, CF_ERR_INVALID, "cf_peer_reduce_connect: rank %d of nranks = %d (1…%d), handles %s", rank, nranks,
+                    CF_PEER_REDUCE_MAX_RANKS, handles ? "given" : "NULL");
+    if (ctx->reduce_seq)   // the sequence numbers of a world start together
+        return fail(ctx, CF_ERR_INVALID, "cf_peer_reduce_connect: this context has already reduced over a world (%llu reductions)", ctx->reduce_seq);
+    char* table[REDUCE_MAX_RANKS] = {};
+    int rc = CF_OK;
+    for (int r = 0; r < nranks && rc == CF_OK; ++r) {
+        if (r == rank) {
+            table[r] = ctx->reduce_mine.get();
+            continue;
+        }
+        rc = map_mailbox(ctx, (const char*)handles + (size_t)r * CF_PEER_HANDLE_BYTES, &table[r], &ctx->reduce_maps[r]);
+        if (rc != CF_OK) break;
+        ReduceNote theirs{};
+        hipError_t e = hipMemcpy(&theirs, table[r], sizeof theirs, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            rc = fail(ctx, CF_ERR_HIP, "cf_peer_reduce_connect: reading rank %d's mailbox: %s", r, hipGetErrorString(e));
+        else if (theirs.magic != REDUCE_MAGIC)
+            rc = fail(ctx, CF_ERR_INVALID, "cf_peer_reduce_connect: the handle of rank %d is not a mailbox of cf_peer_reduce_export", r);
+        else if (theirs.version != REDUCE_LAYOUT_VERSION || theirs.max_ranks != (unsigned)REDUCE_MAX_RANKS ||
+                 theirs.slot_words != (unsigned)REDUCE_SLOT_WORDS || theirs.bytes != REDUCE_MAILBOX_BYTES)
+            rc = fail(ctx, CF_ERR_INVALID, "cf_peer_reduce_connect: rank %d's mailbox has layout version %u, %u ranks, %u words per slot, %llu "
+                      "bytes; this library's is %u, %d, %d, %zu", r, theirs.version, theirs.max_ranks, theirs.slot_words, theirs.bytes,
+                      REDUCE_LAYOUT_VERSION, REDUCE_MAX_RANKS, REDUCE_SLOT_WORDS, REDUCE_MAILBOX_BYTES);
+    }
+    if (rc == CF_OK && !ctx->d_reduce_peers) {
+        hipError_t e = ctx->d_reduce_peers.create(sizeof table);
+        if (e != hipSuccess) rc = fail(ctx, CF_ERR_HIP, "cf_peer_reduce_connect: the table of mailboxes: %s", hipGetErrorString(e));
+    }
+    if (rc == CF_OK) {
+        hipError_t e = hipMemcpy(ctx->d_reduce_peers.get(), table, sizeof table, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = fail(ctx, CF_ERR_HIP, "cf_peer_reduce_connect: the table of mailboxes: %s", hipGetErrorString(e));
+    }
+    if (rc != CF_OK) {
+        disconnect_reduce_world(ctx);
+        return rc;
+    }
+    ctx->reduce = ReduceWorld{ctx->reduce_mine.get(), ctx->d_reduce_peers.get(), rank, nranks};
+    ctx->reduce_connected = true;
+    return CF_OK;
+}
+
 // what the fold of `rows` rows needs of the grid (cf_fold_north_halo, and cf_time_steps with fold_north before its first step)
 static int check_fold_geometry(cf_ctx* ctx, int rows) {
     const GridDesc& G = ctx->grid;
@@ -306,6 +402,36 @@ int cf_discard_prefetched_atmosphere_state(cf_ctx* ctx) {
 }
 
 // ---- run!(simulation) -------------------------------------------------------------------------
+// cf_time_steps_coupled under CF_HALO_PEER: which rows cross a slab boundary, as exchanges of at most PEER_MAX_FIELDS fields.
+// The split depends only on which optional fields are non-NULL (the same on every rank: the caller's contract, coflux.h).
+constexpr int COUPLED_MAX_EXCHANGES = 2;
+static int split_rows(double* const* fields, int n, PeerFields* F) {
+    int sets = 0;
+    for (int at = 0; at < n; at += PEER_MAX_FIELDS, ++sets) {
+        F[sets] = PeerFields{};
+        F[sets].n = std::min(PEER_MAX_FIELDS, n - at);
+        for (int f = 0; f < F[sets].n; ++f) F[sets].ptr[f] = fields[at + f];
+    }
+    return sets;
+}
+// per step: the four ocean fields, as cf_time_steps exchanges them, then the non-NULL fields of the step's ice state
+static int coupled_step_rows(const cf_ocean_surface* o, const cf_sea_ice_state* is, PeerFields* F) {
+    double* fields[10];
+    int n = 0;
+    for (const double* p : {o->T, o->S, o->u, o->v, is->concentration, is->thickness, is->snow_thickness, is->u, is->v, is->albedo})
+        if (p) fields[n++] = const_cast<double*>(p);
+    static_assert(10 <= COUPLED_MAX_EXCHANGES * PEER_MAX_FIELDS, "a step's rows fit its exchanges");
+    return split_rows(fields, n, F);
+}
+// once per call: the ice–ocean stresses (read at j + 1) and the carried skin temperature (first guess on the ring window)
+static int coupled_call_rows(const cf_sea_ice_fields* ice, const cf_coupled_step* K, PeerFields* F) {
+    double* fields[3];
+    int n = 0;
+    for (const double* p : {ice ? ice->x_stress : nullptr, ice ? ice->y_stress : nullptr, (const double*)K->skin_temperature})
+        if (p) fields[n++] = const_cast<double*>(p);
+    return split_rows(fields, n, F);
+}
+
 // cf_time_steps_coupled: what the block itself must satisfy (the schedule's scalars are checked already).  Every message names
 // the field.
 static int check_coupled_block(cf_ctx* ctx, const cf_run_schedule* S, const cf_atmos_source* src, const cf_interp_weights* w,
@@ -315,9 +441,11 @@ static int check_coupled_block(cf_ctx* ctx, const cf_run_schedule* S, const cf_a
     if (K->struct_size != (int32_t)sizeof(cf_coupled_step))
         return fail(ctx, CF_ERR_INVALID, "cf_coupled_step.struct_size = %d, library expects %zu", K->struct_size, sizeof(cf_coupled_step));
     if (!ctx->ice_ready) return fail(ctx, CF_ERR_INVALID, "%s: cf_set_sea_ice_formulation has not been called", fn);
-    if (S->halo_backend != CF_HALO_NONE)
-        return fail(ctx, CF_ERR_INVALID, "%s: halo_backend = %d, but nothing moves the ice rows between ranks yet: only CF_HALO_NONE", fn,
-                    S->halo_backend);
+    if (S->halo_backend != CF_HALO_NONE && S->halo_backend != CF_HALO_PEER)
+        return fail(ctx, CF_ERR_INVALID, "%s: halo_backend = %d, but nothing has exercised the ice rows or the global mean over RCCL: "
+                    "CF_HALO_NONE or CF_HALO_PEER", fn, S->halo_backend);
+    if (K->normalize_salinity < 0 || K->normalize_salinity > CF_NORMALIZE_EXACT)
+        return fail(ctx, CF_ERR_INVALID, "%s: normalize_salinity = %d outside 0…%d", fn, K->normalize_salinity, CF_NORMALIZE_EXACT);
     if (K->n_ice_states < 1 || !K->ice_states) return fail(ctx, CF_ERR_INVALID, "%s: n_ice_states = %d (at least 1) or ice_states is NULL", fn, K->n_ice_states);
     for (int n = 0; n < K->n_ice_states; ++n) {
         if (!K->ice_states[n].concentration || !K->ice_states[n].thickness)
@@ -328,6 +456,27 @@ static int check_coupled_block(cf_ctx* ctx, const cf_run_schedule* S, const cf_a
                         "solve would read different ice (pass NULL: every step takes its ice state's)", fn, n);
     }
     if (!K->skin_temperature) return fail(ctx, CF_ERR_INVALID, "%s: skin_temperature is NULL", fn);
+    if (S->halo_backend == CF_HALO_PEER) {
+        if (!ctx->peer_connected)
+            return fail(ctx, CF_ERR_INVALID, "%s: halo_backend = CF_HALO_PEER, but cf_peer_halo_connect has not been called", fn);
+        int most = 0;   // the largest exchange of the call: the once-per-call set, and every ice state's split
+        PeerFields F[COUPLED_MAX_EXCHANGES];
+        for (int n = -1; n < K->n_ice_states; ++n) {
+            const int sets = n < 0 ? coupled_call_rows(ice, K, F) : coupled_step_rows(&S->ocean_states[0], &K->ice_states[n], F);
+            for (int e = 0; e < sets; ++e) most = std::max(most, F[e].n);
+        }
+        if (most > ctx->peer_max_fields || S->halo_rows > ctx->peer_max_rows || S->halo_rows > ctx->grid.ny)
+            return fail(ctx, CF_ERR_INVALID, "%s: halo_backend = CF_HALO_PEER: exchanges of up to %d fields × %d rows exceed the halo mailbox "
+                        "(%d fields × %d rows) or ny = %d", fn, most, S->halo_rows, ctx->peer_max_fields, ctx->peer_max_rows, ctx->grid.ny);
+        if (S->fold_north)
+            return fail(ctx, CF_ERR_INVALID, "%s: fold_north with CF_HALO_PEER: nothing folds the ice rows on the last rank yet", fn);
+        if (K->normalize_salinity == 1)
+            return fail(ctx, CF_ERR_INVALID, "%s: normalize_salinity = 1 under CF_HALO_PEER: its summation order depends on the slab; "
+                        "CF_NORMALIZE_EXACT (2) gives the single domain's mean", fn);
+        if (K->normalize_salinity == CF_NORMALIZE_EXACT && !ctx->reduce_connected)
+            return fail(ctx, CF_ERR_INVALID, "%s: normalize_salinity = CF_NORMALIZE_EXACT under CF_HALO_PEER, but cf_peer_reduce_connect has not "
+                        "been called", fn);
+    }
     if (K->ai_fluxes.temperature && K->ai_fluxes.temperature != K->skin_temperature)
         return fail(ctx, CF_ERR_INVALID, "%s: ai_fluxes.temperature is neither NULL nor skin_temperature", fn);
     if (!K->net_ice.top_heat || !K->net_ice.bottom_heat) return fail(ctx, CF_ERR_INVALID, "%s: net_ice.top_heat or .bottom_heat is NULL", fn);
@@ -506,6 +655,12 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
     HaloRequestScope halo_request_scope(ctx);
     static const int fold_loc[4] = {CF_FOLD_CENTER, CF_FOLD_CENTER, CF_FOLD_X_FACE, CF_FOLD_Y_FACE};
     static const double fold_sign[4] = {1.0, 1.0, -1.0, -1.0};
+    const bool coupled_peer = K && S->halo_backend == CF_HALO_PEER;
+    if (coupled_peer && nsteps > 0) {   // once per call: afterwards both neighbours recompute the skin temperature's ring rows
+        PeerFields F[COUPLED_MAX_EXCHANGES];
+        const int sets = coupled_call_rows(ice, K, F);
+        for (int e = 0; e < sets; ++e) CHECK(cf_peer_halo_launch_now(ctx, &F[e], S->halo_rows));
+    }
     if (S->pipeline && nsteps > 0) {  // the first step's atmosphere, unless a previous call already started it
         const cf_atmos_source s0 = source_at(first_step);
         const cf_exchange_fields* a0 = &S->atmos[first_step % 2];
@@ -534,7 +689,12 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
                            const_cast<double*>(o->v)};
         if (S->halo_backend == CF_HALO_RCCL)
             CHECK(cf_halo_exchange_rows(ctx, rows, 4, S->halo_rows));
-        else if (S->halo_backend == CF_HALO_PEER) {
+        else if (coupled_peer) {
+            // (CF_OPT_HALO_IN_SOLVER_LAUNCH arms no request here: the coupled step's solver launch is not the one that carries riders)
+            PeerFields F[COUPLED_MAX_EXCHANGES];
+            const int sets = coupled_step_rows(o, &K->ice_states[step % K->n_ice_states], F);
+            for (int e = 0; e < sets; ++e) CHECK(cf_peer_halo_launch_now(ctx, &F[e], S->halo_rows));
+        } else if (S->halo_backend == CF_HALO_PEER) {
             if (ctx->halo_in_launch) {   // (the mailbox takes 4 fields × halo_rows: check_peer_rows above)
                 // CF_OPT_HALO_IN_SOLVER_LAUNCH: left as a request — this step's solver launch carries the exchange as rider
                 // workgroups where it can, cf_update_state issues the exchange kernel in front of the solver where it cannot
@@ -582,7 +742,9 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
             ai.temperature = K->skin_temperature;
             CHECK(cf_update_state_sea_ice(ctx, &s, w, o, a, fluxes, &partition, net, &state, &ai, K->ice_ocean_fluxes.frazil_heat,
                                           K->ice_ocean_fluxes.interface_heat, &K->net_ice));
-            if (K->normalize_salinity)
+            if (K->normalize_salinity == CF_NORMALIZE_EXACT)
+                CHECK(cf_normalize_salinity_flux_exact(ctx, net->S, K->restoring_buffer, K->area, o->mask, K->mean_out));
+            else if (K->normalize_salinity)
                 CHECK(cf_normalize_salinity_flux(ctx, net->S, K->restoring_buffer, K->area, o->mask, K->mean_out));
         } else {
             CHECK(cf_update_state(ctx, &s, w, o, a, fluxes, ice, net));

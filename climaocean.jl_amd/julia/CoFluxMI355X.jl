@@ -192,6 +192,21 @@ normalize_salinity_flux!(b::CoFluxBackend, flux::Ptr{Float64}, additional, area,
                        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}),
                        b.ctx, flux, additional, area, mask, mean_out))
 
+# NormalizeSalinity with exact sums: the mean's bits do not depend on the slab decomposition; over the reduction world when one
+# is connected on more than one rank (peer_reduce_connect!).  CF_NORMALIZE_EXACT is the value of CfCoupledStep.normalize_salinity
+const CF_NORMALIZE_EXACT = Int32(2)
+normalize_salinity_flux_exact!(b::CoFluxBackend, flux::Ptr{Float64}, additional, area, mask, mean_out = C_NULL) =
+    check(b.ctx, ccall((:cf_normalize_salinity_flux_exact, libcoflux), Cint,
+                       (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}),
+                       b.ctx, flux, additional, area, mask, mean_out))
+# test aid: this rank's exact sums (Σ J·A, Σ A) and the counts of NaN / +Inf / −Inf terms of the first; synchronises
+function debug_salinity_sums_exact(b::CoFluxBackend, flux::Ptr{Float64}, additional, area, mask)
+    sums = zeros(Float64, 2); counts = zeros(Culonglong, 3)
+    check(b.ctx, ccall((:cf_debug_salinity_sums_exact, libcoflux), Cint,
+                       (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Culonglong}),
+                       b.ctx, flux, additional, area, mask, sums, counts))
+    return (sums = (sums[1], sums[2]), nonfinite = (counts[1], counts[2], counts[3]))
+end
 # ---- atmosphere–sea-ice interface: compute_atmosphere_sea_ice_fluxes!(coupled_model) ---------------
 const CF_SKIN_EXPLICIT = Int32(0)
 const CF_SKIN_SEMI_IMPLICIT = Int32(1)
@@ -292,6 +307,14 @@ peer_halo_export!(b, max_fields = 4, max_rows = 2) = (h = zeros(UInt8, 64);
 peer_halo_connect!(b, south::Union{Nothing, Vector{UInt8}}, north::Union{Nothing, Vector{UInt8}}, rank, nranks) =
     check(b.ctx, ccall((:cf_peer_halo_connect, libcoflux), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Ptr{UInt8}, Cint, Cint), b.ctx,
                        isnothing(south) ? C_NULL : south, isnothing(north) ? C_NULL : north, rank, nranks))
+# the reduction world of the exact sums: every rank's reduce mailbox, mapped by every other rank (handles in rank order,
+# 64 bytes each; `nothing` for a world of one).  Every rank issues the same number of reductions.
+const CF_PEER_REDUCE_MAX_RANKS = 8
+peer_reduce_export!(b) = (h = zeros(UInt8, 64);
+    check(b.ctx, ccall((:cf_peer_reduce_export, libcoflux), Cint, (Ptr{Cvoid}, Ptr{UInt8}), b.ctx, h)); h)
+peer_reduce_connect!(b, handles::Union{Nothing, Vector{Vector{UInt8}}}, rank, nranks) =
+    check(b.ctx, ccall((:cf_peer_reduce_connect, libcoflux), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Cint, Cint), b.ctx,
+                       isnothing(handles) ? C_NULL : reduce(vcat, handles), rank, nranks))
 halo_exchange_rows_peer!(b, fields::Vector{Ptr{Float64}}, rows = 2) =
     check(b.ctx, ccall((:cf_halo_exchange_rows_peer, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Cint, Cint),
                        b.ctx, fields, length(fields), rows))

@@ -830,6 +830,29 @@ int cf_materialize_salinity_restoring(cf_ctx* ctx, double piston_velocity /* m/s
 int cf_normalize_salinity_flux(cf_ctx* ctx, double* d_flux, const double* d_additional, const double* d_area,
                                const void* d_mask, double* d_mean_out);
 
+/* NormalizeSalinity whose mean does not depend on how the globe is cut into slabs.  cf_normalize_salinity_flux adds in an order
+ * that is a function of the slab (grid-stride partial sums of nx · ny cells), so R ranks cannot give the bits of one domain — and
+ * the mean is subtracted from every cell.  Here both sums are EXACT: for every wet interior cell, with no fused multiply-add,
+ *     v = fl(flux + additional)   (flux alone when d_additional is NULL),   a = area (1.0 when d_area is NULL),   t = fl(v · a),
+ *     S_J = Σ t   and   S_A = Σ a   exactly,   sums = (fl(S_J), fl(S_A)) rounded once to nearest-even,
+ * then, as in cf_normalize_salinity_flux, mean = sums[1] > 0 ? sums[0] / sums[1] : 0 is subtracted from every cell of the parent
+ * array and written to *d_mean_out.  A sum is kept as 67 signed 64-bit digits, digit k of weight 2^(32k − 1088); a term adds one
+ * 32-bit piece to each of three adjacent digits with integer atomics, so the digits depend on no order, workgroup or rank
+ * (csrc/coflux_exact_sum.hpp holds the format and the rounding; it builds without HIP).  A zero sum is +0.0; beyond the largest
+ * double the sum is ±Inf; with a NaN term or both infinities among the terms it is NaN, with one infinity that infinity.  Land
+ * and halo cells are selected away and never multiplied: they may hold NaN.  At most 2³¹ terms over all ranks.
+ * With a reduction world connected on more than one rank (cf_peer_reduce_connect) the digits of all ranks are added before the
+ * rounding: every rank subtracts the bits of the single domain's mean.  The bits of this form differ from
+ * cf_normalize_salinity_flux's, which keeps its order and its bits.                                                          */
+/* Footprint: cf_normalize_salinity_flux's.                                                                                    */
+int cf_normalize_salinity_flux_exact(cf_ctx* ctx, double* d_flux, const double* d_additional, const double* d_area,
+                                     const void* d_mask, double* d_mean_out);
+/* A test aid, in the family of cf_debug_chunk_table: THIS RANK's two exact sums of cf_normalize_salinity_flux_exact (no
+ * reduction is issued, whatever is connected) and how many terms of S_J were NaN, +Inf, −Inf.  Synchronises the context's stream
+ * and answers on the host; writes nothing to d_flux.                                                                          */
+int cf_debug_salinity_sums_exact(cf_ctx* ctx, const double* d_flux, const double* d_additional, const double* d_area,
+                                 const void* d_mask, double sums_out[2], unsigned long long nonfinite_out[3]);
+
 /* The preamble of a coupled step (omip_simulation.jl:123-163, :507-523): what cf_interpolate_land_freshwater,
  * cf_compute_sea_ice_ocean_fluxes and cf_materialize_salinity_restoring do in front of cf_update_state_sea_ice, as ONE
  * launch (one thread per cell of W; the two interior jobs share one read of S and of the mask).  Every array the call
@@ -941,6 +964,28 @@ int cf_halo_exchange_rows_peer(cf_ctx* ctx, double* const* d_fields, int nfields
  * (CF_OPT_HALO_IN_SOLVER_LAUNCH) instead of the exchange kernel of their own.  A measurement / test aid.      */
 int cf_peer_halo_stats(cf_ctx* ctx, unsigned long long* exchanges, unsigned long long* in_solver_launch);
 
+/* The reduction world of the exact sums (cf_normalize_salinity_flux_exact).  Halo mailboxes connect neighbours; a global sum needs
+ * every rank, so every rank owns a second, small mailbox in fine-grained device memory that EVERY other rank maps: two parities ×
+ * CF_PEER_REDUCE_MAX_RANKS slots (the accumulators of Σ J·A and Σ A with their non-finite counters, 140 64-bit words) and one
+ * flag per parity and rank on a 64-byte line of its own.  Each reduction a context issues takes the next sequence number s: the
+ * finishing workgroup stores its accumulators into slot [s mod 2][my rank] of every other rank's mailbox, fences at system scope,
+ * publishes s in that rank's flag [s mod 2][my rank] (system-scope release), waits for the other nranks − 1 flags of its own
+ * mailbox (one lane per flag, sleeping, with the bound of the halo rows), acquires and adds digit-wise.  A rank publishes s + 1
+ * only after it has read every slot of s: two parities are enough, by the argument of the halo mailboxes.  No collective library.
+ *   cf_peer_reduce_export    allocate this rank's reduce mailbox and write its IPC handle (CF_PEER_HANDLE_BYTES).  CF_ERR_COMM
+ *                            when the device has no fine-grained memory to give, as cf_peer_halo_export.
+ *   cf_peer_reduce_connect   `handles`: nranks × CF_PEER_HANDLE_BYTES, entry r from rank r (the rank's own entry is not opened).
+ *                            nranks = 1 is valid: it maps nothing and nothing ever waits (handles may be NULL).  Every mailbox
+ *                            carries its layout's version and size; a foreign one, nranks outside 1 … CF_PEER_REDUCE_MAX_RANKS
+ *                            or a bad rank returns CF_ERR_INVALID and leaves the context unconnected, whatever it was connected to
+ *                            before.  A context that has already reduced over a world cannot join another.
+ * THE NUMBER OF REDUCTIONS IS THE SAME ON EVERY RANK — every cf_normalize_salinity_flux_exact on a connected context, every
+ * step of cf_time_steps_coupled with CF_NORMALIZE_EXACT — as for the halo rows: the caller's contract, not checked.  A wait that
+ * exceeds its bound sets the sticky error that the next cf_sync reports (CF_ERR_COMM); the kernel ends with this rank's own sums. */
+#define CF_PEER_REDUCE_MAX_RANKS 8
+int cf_peer_reduce_export(cf_ctx* ctx, void* handle_out);
+int cf_peer_reduce_connect(cf_ctx* ctx, const void* handles, int rank, int nranks);
+
 /* Tripolar fold (TripolarGrid(arch; size=(360,180,Nz)), OceanConfigurations/one_degree_tripolar.jl:48-51; the
  * fold itself lives in Oceananigans' zipper boundary condition, [UPSTREAM-RECALL] fold_north_center_center! /
  * _face_center! / _center_face!).  The northern boundary of the global grid is folded onto itself about the LAST
@@ -1035,7 +1080,8 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
  *      `ice`'s own interface_heat / salt_flux are not read); the net sea-ice fluxes read ice_ocean_fluxes.frazil_heat /
  *      interface_heat.  skin_temperature is CARRIED: the first guess of the interface solve and the buffer its result is
  *      written to — the in-place update cf_sea_ice_state documents; ai_fluxes.temperature is NULL or that very buffer;
- *   5. normalize_salinity: cf_normalize_salinity_flux on net->S with restoring_buffer (or NULL), `area` and `mean_out`;
+ *   5. normalize_salinity = 1: cf_normalize_salinity_flux on net->S with restoring_buffer (or NULL), `area` and `mean_out`;
+ *      CF_NORMALIZE_EXACT (2): cf_normalize_salinity_flux_exact with the same arguments (single-domain callers may use it too);
  *   6. the attached averager, integrator and monitor, by cf_time_steps' rule.
  * Land cells are written at every step (CF_OPT_LAND_ZEROS does not apply to this loop).
  * CF_ERR_INVALID, with the field named, before anything is launched — the outputs are untouched — for: a NULL block or a
@@ -1044,9 +1090,30 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
  * partition and the interface solve would disagree); land_first_level outside the land source's levels, a negative or
  * non-finite land_time_fraction / _increment, a bad land shape; NULL among skin_temperature, ai_fluxes, net_ice, the
  * land_freshwater of a land job, the ice_ocean_fluxes of compute_ice_ocean, `fluxes`, `net`, the exchange sets or the
- * ocean states; an ai_fluxes.temperature that is another buffer; mean_out inside any array of the call; and
- * halo_backend != CF_HALO_NONE: nothing moves ice rows between ranks yet (the ice–ocean exchange reads the stresses' east
- * column and north row, the partition reads ℵ across faces — those halos are the caller's, also under fold_north).        */
+ * ocean states; an ai_fluxes.temperature that is another buffer; mean_out inside any array of the call; normalize_salinity
+ * outside 0 … 2; and what the next paragraph refuses.
+ * Latitude slabs: halo_backend = CF_HALO_PEER.  What crosses a slab boundary: the interface solve reads the ice state on W, the
+ * partition reads ℵ at j − 1, the ice–ocean exchange reads y_stress at j + 1, and the carried skin temperature is first guess and
+ * result on W.  So, through the exchange kernel of cf_halo_exchange_rows_peer, halo_rows rows each:
+ *   per step, in front of the fold and the preamble: the four ocean fields of the step's ocean state, as cf_time_steps exchanges
+ *     them, and the non-NULL fields of the step's ice state in the order concentration, thickness, snow_thickness, u, v, albedo.
+ *     The list is cut into exchanges of at most 8 fields: one exchange up to 8 fields, two beyond;
+ *   once per call with nsteps > 0, in front of the first step: the non-NULL ones of ice->x_stress, ice->y_stress, and
+ *     skin_temperature, as one exchange.  After that both neighbours recompute the ring rows of the skin temperature from
+ *     identical inputs: they stay the neighbour's bits (tests/test_coupled_slabs.py).
+ * cf_peer_halo_stats' exchange count therefore grows by 1 + nsteps · (1 or 2) per call.  The split depends only on which optional
+ * fields are non-NULL: THAT THOSE ARE THE SAME ON EVERY RANK, like the number of steps, is the caller's contract and is not
+ * checked.  CF_OPT_HALO_IN_SOLVER_LAUNCH arms no request in this loop: its solver launch is not the one that carries riders.  The
+ * x-halos of all these fields stay the caller's.  Attached collections collect per rank, as in cf_time_steps.
+ * Refused with CF_ERR_INVALID before the first launch, outputs and cf_peer_halo_stats unchanged, the field named:
+ *   halo_backend = CF_HALO_RCCL: nothing has exercised the ice rows or the global mean over RCCL;
+ *   halo_backend = CF_HALO_PEER on a context whose halo mailboxes are not connected (cf_peer_halo_connect) or too small for the
+ *     call's exchanges (the largest of them × halo_rows);
+ *   fold_north together with CF_HALO_PEER: folding the ice rows on the last rank is the next follow-up (under CF_HALO_NONE the
+ *     fold applies to the four ocean rows and the ice halos are the caller's);
+ *   normalize_salinity = 1 under CF_HALO_PEER: its summation order depends on the slab;
+ *   normalize_salinity = CF_NORMALIZE_EXACT under CF_HALO_PEER without a reduction world (cf_peer_reduce_connect).            */
+#define CF_NORMALIZE_EXACT 2
 typedef struct cf_coupled_step {
     int32_t struct_size;                  /* sizeof(cf_coupled_step) */
     int32_t n_ice_states;                 /* ≥ 1 */
@@ -1065,13 +1132,14 @@ typedef struct cf_coupled_step {
     double piston_velocity;               /* restoring: v_p [m/s], S★, J_add; restoring_buffer NULL ⇒ no restoring job */
     const double* target_salinity;
     double* restoring_buffer;
-    int32_t normalize_salinity;           /* 1: NormalizeSalinity after every step */
+    int32_t normalize_salinity;           /* NormalizeSalinity after every step: 0 none, 1 cf_normalize_salinity_flux, CF_NORMALIZE_EXACT */
     int32_t reserved;
     const double* area;                   /* cell areas for the normalisation (NULL ⇒ uniform) */
     double* mean_out;                     /* device double: the mean the last step subtracted (may be NULL) */
 } cf_coupled_step;
 /* Footprint: per step cf_fold_north_halo's (fold_north), cf_prepare_coupled_step's, cf_update_state_sea_ice's,
- * cf_normalize_salinity_flux's (every cell of net->S, and *mean_out) and those of the attached collections.              */
+ * cf_normalize_salinity_flux's (every cell of net->S, and *mean_out) and those of the attached collections; under CF_HALO_PEER
+ * cf_halo_exchange_rows_peer's on the exchanged fields (the ice states' and the stresses' halo rows are WRITTEN).          */
 int cf_time_steps_coupled(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_schedule* schedule,
                           const cf_atmos_source* src, const cf_interp_weights* w, const cf_interface_fluxes* fluxes,
                           const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* net, const cf_coupled_step* coupled);
