@@ -335,6 +335,7 @@ EXPORTED_SYMBOLS = (
     "cf_time_stage", "cf_time_copy", "cf_profile_enable", "cf_profile_read",
     "cf_comm_unique_id", "cf_comm_init", "cf_comm_destroy", "cf_halo_exchange_rows",
     "cf_peer_halo_export", "cf_peer_halo_connect", "cf_halo_exchange_rows_peer", "cf_peer_halo_stats", "cf_fold_north_halo",
+    "cf_debug_fold_counts",
     "cf_time_steps", "cf_prefetch_atmosphere_state",
     "cf_default_sea_ice_albedo_params", "cf_set_sea_ice_albedo", "cf_compute_sea_ice_albedo",
     "cf_default_ice_ocean_params", "cf_compute_sea_ice_ocean_fluxes",
@@ -420,6 +421,7 @@ def load_library(path=None):
     lib.cf_solver_iteration_path.argtypes = [vp, C.POINTER(C.c_int)]
     lib.cf_solver_latency_layout.argtypes = [vp, C.POINTER(C.c_int)]
     lib.cf_peer_halo_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    lib.cf_debug_fold_counts.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.cf_discard_prefetched_atmosphere_state.argtypes = [vp]
     lib.cf_debug_prefetch_stats.argtypes = [vp, C.POINTER(PrefetchStats)]
     lib.cf_comm_count.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -126,12 +126,42 @@ class SlabHaloExchanger:
             exchange_halo_rows_torch(tensors, self.ny, self.hy, self.rows)
 
 
+MAX_EXCHANGE_FIELDS = 8     # PEER_MAX_FIELDS: the most fields one exchange launch carries
+
+# What cf_time_steps_coupled exchanges under CF_HALO_PEER, in the order of include/coflux.h, and how the tripolar fold maps each
+# field on the rank that owns it: (name, location, sign).  The ice velocities lie at cell centres (cf_sea_ice_state) and change
+# sign across the fold like every vector component; the stresses lie on the faces of the ocean velocities.
+COUPLED_STEP_FIELDS = (("T", "center", 1.0), ("S", "center", 1.0), ("u", "x_face", -1.0), ("v", "y_face", -1.0),
+                       ("concentration", "center", 1.0), ("thickness", "center", 1.0), ("snow_thickness", "center", 1.0),
+                       ("ice_u", "center", -1.0), ("ice_v", "center", -1.0), ("albedo", "center", 1.0))
+COUPLED_CALL_FIELDS = (("x_stress", "x_face", -1.0), ("y_stress", "y_face", -1.0), ("skin_temperature", "center", 1.0))
+
+
+def _cut(fields, present):
+    kept = [f for f in fields if f[0] in present]
+    return [kept[at:at + MAX_EXCHANGE_FIELDS] for at in range(0, len(kept), MAX_EXCHANGE_FIELDS)]
+
+
+def coupled_fold_plan(ocean_present=("T", "S", "u", "v"), ice_present=("concentration", "thickness"), call_present=("skin_temperature",)):
+    """The exchanges of one cf_time_steps_coupled call under CF_HALO_PEER as lists of (name, location, sign), by the C cut
+    (csrc/coflux_steps.cpp: coupled_step_rows, coupled_call_rows): `per_step` — the ocean fields, then the present fields of
+    the step's ice state (names of cf_sea_ice_state, its velocities as "ice_u", "ice_v") — and `per_call` — the present ones
+    of x_stress, y_stress, skin_temperature —, each cut into exchanges of at most eight fields in that order.  On the rank
+    that passes fold_north these triples are what the north side of each exchange folds.  Returns (per_call, per_step)."""
+    step_present = set(ocean_present) | {("ice_" + k if k in ("u", "v") else k) for k in ice_present}
+    return _cut(COUPLED_CALL_FIELDS, set(call_present)), _cut(COUPLED_STEP_FIELDS, step_present)
+
+
 def connect_coupled_slabs(ctx, max_fields=8, rows=None):
     """What cf_time_steps_coupled needs under CF_HALO_PEER: exports this rank's halo mailbox (`max_fields` fields × `rows` rows,
     ring + 1 by default) and its reduce mailbox, gathers the handles of both over torch.distributed and connects — the slab
     neighbours for the halo rows, every rank for the exact sums (cf_peer_halo_connect, cf_peer_reduce_connect).  A world of one
     (or no process group) connects to nobody: nothing ever waits.  Every rank reaches the gather whatever happened locally, and
-    every rank raises when an export failed anywhere, as SlabHaloExchanger agrees on its backend."""
+    every rank raises when an export failed anywhere, as SlabHaloExchanger agrees on its backend.
+
+    On a tripolar grid the rank this returns as `world − 1` — the one without a north mailbox — passes fold_north = 1 in its
+    schedule and every other rank 0: its exchanges fold their own fields as their north side (coupled_fold_plan).  A world of
+    one is that last rank."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     rows = rows if rows is not None else ctx.grid.ring + 1

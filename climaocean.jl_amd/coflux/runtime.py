@@ -675,6 +675,13 @@ class FluxContext:
         self._check(self.lib.cf_peer_halo_stats(self._h, C.byref(a), C.byref(b)), "cf_peer_halo_stats")
         return a.value, b.value
 
+    def fold_counts(self):
+        """(fold launches of their own, exchange launches whose north side was the tripolar fold) since the context was created
+        (cf_debug_fold_counts)."""
+        a, b = C.c_longlong(), C.c_longlong()
+        self._check(self.lib.cf_debug_fold_counts(self._h, C.byref(a), C.byref(b)), "cf_debug_fold_counts")
+        return a.value, b.value
+
     def halo_exchange_rows_peer(self, tensors, rows=2):
         arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
         self._check(self.lib.cf_halo_exchange_rows_peer(self._h, arr, len(tensors), rows), "cf_halo_exchange_rows_peer")

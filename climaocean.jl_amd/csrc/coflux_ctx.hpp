@@ -181,6 +181,8 @@ struct cf_ctx {
     bool peer_connected = false;
     unsigned long long peer_seq = 0;
     cf::DeviceBuffer<int> d_peer_status;
+    // cf_debug_fold_counts: fold_north_kernel launches, and exchange launches whose north side was the fold (peer_halo_fold_kernel)
+    long long fold_launch_count = 0, fold_exchange_count = 0;
     // the exact sums of cf_normalize_salinity_flux_exact (coflux_exact_sum.hip) and their reduction world (cf_peer_reduce_*)
     cf::DeviceBuffer<unsigned long long> d_exact;        // [2 · XS_WORDS: the accumulator pair][2 doubles: the sums][3: non-finite counts]
     ReduceWorld reduce{nullptr, nullptr, 0, 1};          // raw views of the three below

@@ -6,7 +6,9 @@
 // mailbox — fine-grained device memory mapped through HIP IPC, i.e. plain stores that travel over xGMI —,
 // (ii) publish the step's sequence number with a system-scope release, (iii) wait for the neighbour's number in
 // the own mailbox (one lane polls, bounded, sleeping between polls) and (iv) copy the received rows into the halo
-// rows.  No host round trip, no second launch, nothing for the solver to wait on except stream order.
+// rows.  No host round trip, no second launch, nothing for the solver to wait on except stream order.  The steps themselves are
+// peer_halo_side (coflux_halo_device.hpp).  On the rank that owns the tripolar fold the coupled loop launches the form whose north
+// side folds the exchange's own fields instead (peer_halo_fold_kernel).
 #include <hip/hip_runtime.h>
 
 #include "coflux_halo_device.hpp"
@@ -17,58 +19,37 @@ namespace coflux {
 
 __global__ __launch_bounds__(PEER_BLOCK) void peer_halo_kernel(PeerMailbox M, PeerFields F, GridDesc G, int rows,
                                                                unsigned long long seq, int* __restrict__ status) {
-    const int dir = (int)blockIdx.x;  // 0: south neighbour, 1: north neighbour
-    char* remote = dir == 0 ? M.south : M.north;
-    if (!remote) return;  // end of the slab ring (or a fold): nothing to exchange in this direction
-    const int parity = (int)(seq & 1ull);
-    const size_t row_doubles = (size_t)G.sj, per_field = (size_t)rows * row_doubles;
-    // (i) my boundary rows → the neighbour's mailbox; seen from THERE they arrive from the opposite side
-    {
-        double* dst = mailbox_rows(M, remote, 1 - dir, parity);
-        const size_t first_row = dir == 0 ? (size_t)G.hy : (size_t)(G.hy + G.ny - rows);
-        for (int f = 0; f < F.n; ++f) {
-            const double* src = F.ptr[f] + first_row * row_doubles;
-            for (size_t n = threadIdx.x; n < per_field; n += PEER_BLOCK) dst[(size_t)f * per_field + n] = src[n];
-        }
-    }
-    // (ii) publish: every lane's stores must be visible system-wide before the flag is
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0)
-        __hip_atomic_store(mailbox_flag(remote, 1 - dir, parity), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    // (iii) wait for the neighbour's rows of the same step
     __shared__ int ok;
-    if (threadIdx.x == 0) {
-        unsigned long long* flag = mailbox_flag(M.mine, dir, parity);
-        unsigned long long spins = 0;
-        int good = 1;
-        while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < seq) {
-            __builtin_amdgcn_s_sleep(8);
-            if (++spins > PEER_SPIN_LIMIT) {
-                good = 0;
-                break;
-            }
-        }
-        ok = good;
-        if (!good) atomicExch(status, 1 + dir);  // sticky: reported by the next cf_sync
+    peer_halo_side(M, F.ptr, F.n, G, rows, seq, status, (int)blockIdx.x, &ok);  // workgroup 0: south neighbour, 1: north neighbour
+}
+
+// The exchange launch of the rank that owns the tripolar fold (cf_time_steps_coupled under CF_HALO_PEER with fold_north): that
+// rank has no north neighbour, and the north halo rows of the exchange's own fields are the fold of its own interior rows.
+// Workgroup 0 is the south exchange, the protocol of peer_halo_kernel unchanged; workgroup 1 + f · rows + (r − 1) folds north
+// halo row ny − 1 + r of field f with the field's own location and sign — cf_fold_north_halo's arithmetic, bit for bit.
+// The two sides need no ordering: check_fold_geometry admits rows ≤ ny − 1, so the fold reads only the interior rows
+// ny − 1 − rows … ny − 1 and writes only north halo rows, while the south side reads the interior rows 0 … rows − 1 and writes
+// only south halo rows; no cell one side writes is touched by the other, and neither side writes a cell the fold reads.
+__global__ __launch_bounds__(PEER_BLOCK) void peer_halo_fold_kernel(PeerMailbox M, FoldFields F, GridDesc G, int rows,
+                                                                    unsigned long long seq, int* __restrict__ status) {
+    __shared__ int ok;
+    if (blockIdx.x == 0) {
+        peer_halo_side(M, F.ptr, F.n, G, rows, seq, status, 0, &ok);
+        return;
     }
-    __syncthreads();
-    if (!ok) return;
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);  // system scope: nothing cached of the mailbox survives the flag
-    // (iv) mailbox → my halo rows
-    {
-        const double* src = mailbox_rows(M, M.mine, dir, parity);
-        const size_t first_row = dir == 0 ? (size_t)(G.hy - rows) : (size_t)(G.hy + G.ny);
-        for (int f = 0; f < F.n; ++f) {
-            double* dst = F.ptr[f] + first_row * row_doubles;
-            for (size_t n = threadIdx.x; n < per_field; n += PEER_BLOCK) dst[n] = src[(size_t)f * per_field + n];
-        }
-    }
+    const int h = (int)blockIdx.x - 1, f = h / rows, r = h - f * rows + 1;  // (uniform: the field's entry is read with scalar loads)
+    fold_north_row(F.ptr[f], G, F.location[f], F.sign[f], r, PEER_BLOCK);
 }
 
 hipError_t launch_peer_halo(hipStream_t st, const PeerMailbox& M, const PeerFields& F, const GridDesc& G, int rows,
                             unsigned long long seq, int* d_status) {
     hipLaunchKernelGGL(peer_halo_kernel, dim3(2), dim3(PEER_BLOCK), 0, st, M, F, G, rows, seq, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_peer_halo_fold(hipStream_t st, const PeerMailbox& M, const FoldFields& F, const GridDesc& G, int rows,
+                                 unsigned long long seq, int* d_status) {
+    hipLaunchKernelGGL(peer_halo_fold_kernel, dim3(1 + F.n * rows), dim3(PEER_BLOCK), 0, st, M, F, G, rows, seq, d_status);
     return hipGetLastError();
 }
 
@@ -85,25 +66,8 @@ __global__ __launch_bounds__(256) void fold_north_kernel(FoldFields F, GridDesc 
     const int i = n - (r - 1) * width - G.hx;  // interior-relative column, x-halos included
     int ip = i % G.nx;                  // periodic image inside [0, nx)
     if (ip < 0) ip += G.nx;
-    const int loc = F.location[f];
-    double sign = F.sign[f];
-    int is, js;
-    if (loc == CF_FOLD_X_FACE) {
-        is = G.nx - ip;
-        if (is >= G.nx) {  // the face on the fold axis maps onto itself
-            is -= G.nx;
-            sign = fabs(sign);
-        }
-        js = G.ny - 1 - r;
-    } else if (loc == CF_FOLD_Y_FACE) {
-        is = G.nx - 1 - ip;
-        js = G.ny - r;
-    } else {
-        is = G.nx - 1 - ip;
-        js = G.ny - 1 - r;
-    }
     double* p = F.ptr[f];
-    p[cell_index(G, i, G.ny - 1 + r)] = sign * p[cell_index(G, is, js)];
+    p[cell_index(G, i, G.ny - 1 + r)] = fold_north_value(p, G, F.location[f], F.sign[f], ip, r);
 }
 
 hipError_t launch_fold_north(hipStream_t st, const FoldFields& F, const GridDesc& G, int rows) {

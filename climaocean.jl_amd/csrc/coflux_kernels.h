@@ -198,6 +198,10 @@ struct PeerFields;
 struct FoldFields;
 hipError_t launch_peer_halo(hipStream_t st, const PeerMailbox& M, const PeerFields& F, const GridDesc& G, int rows,
                             unsigned long long seq, int* d_status);
+// the exchange launch of the rank that owns the tripolar fold: workgroup 0 exchanges with the south neighbour, 1 + F.n · rows
+// workgroups fold the north halo rows of the exchange's own fields (coflux_halo.hip: peer_halo_fold_kernel)
+hipError_t launch_peer_halo_fold(hipStream_t st, const PeerMailbox& M, const FoldFields& F, const GridDesc& G, int rows,
+                                 unsigned long long seq, int* d_status);
 hipError_t launch_fold_north(hipStream_t st, const FoldFields& F, const GridDesc& G, int rows);
 hipError_t launch_copy(hipStream_t st, void* dst, const void* src, size_t bytes);
 // cf_average_collect (coflux_average.hip): every field's interior mean m ← f (store) or m ← (m · c_prev) + (f · c_new), one launch

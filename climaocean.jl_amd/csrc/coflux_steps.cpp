@@ -389,6 +389,14 @@ int cf_fold_north_halo(cf_ctx* ctx, double* const* d_fields, const int* location
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_fold_north(ctx->stream, F, G, rows));
+    ++ctx->fold_launch_count;
+    return CF_OK;
+}
+
+int cf_debug_fold_counts(cf_ctx* ctx, long long* fold_launches, long long* exchanges_with_fold) {
+    if (!ctx) return fail(nullptr, CF_ERR_INVALID, "ctx is NULL");
+    if (fold_launches) *fold_launches = ctx->fold_launch_count;
+    if (exchanges_with_fold) *exchanges_with_fold = ctx->fold_exchange_count;
     return CF_OK;
 }
 
@@ -404,32 +412,64 @@ int cf_discard_prefetched_atmosphere_state(cf_ctx* ctx) {
 // ---- run!(simulation) -------------------------------------------------------------------------
 // cf_time_steps_coupled under CF_HALO_PEER: which rows cross a slab boundary, as exchanges of at most PEER_MAX_FIELDS fields.
 // The split depends only on which optional fields are non-NULL (the same on every rank: the caller's contract, coflux.h).
+// Every field carries how the tripolar fold maps it (location, sign): on the rank that owns the fold the exchange's north side
+// folds the very fields it exchanges (coflux/distributed.py: coupled_fold_plan is the host statement of these two tables).
 constexpr int COUPLED_MAX_EXCHANGES = 2;
-static int split_rows(double* const* fields, int n, PeerFields* F) {
-    int sets = 0;
-    for (int at = 0; at < n; at += PEER_MAX_FIELDS, ++sets) {
-        F[sets] = PeerFields{};
-        F[sets].n = std::min(PEER_MAX_FIELDS, n - at);
-        for (int f = 0; f < F[sets].n; ++f) F[sets].ptr[f] = fields[at + f];
+struct RowField {
+    const double* p;
+    int location;
+    double sign;
+};
+static int split_rows(const RowField* fields, int n, FoldFields* F) {
+    int present = 0, sets = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!fields[k].p) continue;
+        if (present % PEER_MAX_FIELDS == 0) F[sets++] = FoldFields{};
+        FoldFields& X = F[sets - 1];
+        X.ptr[X.n] = const_cast<double*>(fields[k].p);
+        X.location[X.n] = fields[k].location;
+        X.sign[X.n] = fields[k].sign;
+        ++X.n;
+        ++present;
     }
     return sets;
 }
-// per step: the four ocean fields, as cf_time_steps exchanges them, then the non-NULL fields of the step's ice state
-static int coupled_step_rows(const cf_ocean_surface* o, const cf_sea_ice_state* is, PeerFields* F) {
-    double* fields[10];
-    int n = 0;
-    for (const double* p : {o->T, o->S, o->u, o->v, is->concentration, is->thickness, is->snow_thickness, is->u, is->v, is->albedo})
-        if (p) fields[n++] = const_cast<double*>(p);
+// per step: the four ocean fields, as cf_time_steps exchanges and folds them, then the non-NULL fields of the step's ice state
+// (scalars at cell centres; the ice velocities, which cf_sea_ice_state documents at cell centres, change sign across the fold)
+static int coupled_step_rows(const cf_ocean_surface* o, const cf_sea_ice_state* is, FoldFields* F) {
+    const RowField fields[10] = {{o->T, CF_FOLD_CENTER, 1.0},
+                                 {o->S, CF_FOLD_CENTER, 1.0},
+                                 {o->u, CF_FOLD_X_FACE, -1.0},
+                                 {o->v, CF_FOLD_Y_FACE, -1.0},
+                                 {is->concentration, CF_FOLD_CENTER, 1.0},
+                                 {is->thickness, CF_FOLD_CENTER, 1.0},
+                                 {is->snow_thickness, CF_FOLD_CENTER, 1.0},
+                                 {is->u, CF_FOLD_CENTER, -1.0},
+                                 {is->v, CF_FOLD_CENTER, -1.0},
+                                 {is->albedo, CF_FOLD_CENTER, 1.0}};
     static_assert(10 <= COUPLED_MAX_EXCHANGES * PEER_MAX_FIELDS, "a step's rows fit its exchanges");
-    return split_rows(fields, n, F);
+    return split_rows(fields, 10, F);
 }
 // once per call: the ice–ocean stresses (read at j + 1) and the carried skin temperature (first guess on the ring window)
-static int coupled_call_rows(const cf_sea_ice_fields* ice, const cf_coupled_step* K, PeerFields* F) {
-    double* fields[3];
-    int n = 0;
-    for (const double* p : {ice ? ice->x_stress : nullptr, ice ? ice->y_stress : nullptr, (const double*)K->skin_temperature})
-        if (p) fields[n++] = const_cast<double*>(p);
-    return split_rows(fields, n, F);
+static int coupled_call_rows(const cf_sea_ice_fields* ice, const cf_coupled_step* K, FoldFields* F) {
+    const RowField fields[3] = {{ice ? ice->x_stress : nullptr, CF_FOLD_X_FACE, -1.0},
+                                {ice ? ice->y_stress : nullptr, CF_FOLD_Y_FACE, -1.0},
+                                {K->skin_temperature, CF_FOLD_CENTER, 1.0}};
+    return split_rows(fields, 3, F);
+}
+// one exchange of the coupled loop: the exchange kernel, or on the rank that owns the fold the form whose north side folds
+static int coupled_exchange(cf_ctx* ctx, const FoldFields* F, int rows, bool fold) {
+    if (!fold) {
+        PeerFields P{};
+        P.n = F->n;
+        for (int f = 0; f < F->n; ++f) P.ptr[f] = F->ptr[f];
+        return cf_peer_halo_launch_now(ctx, &P, rows);
+    }
+    // counted like every exchange, once the kernel is queued: the sequence number names the same step on every rank
+    HIP_TRY(ctx, launch_peer_halo_fold(ctx->stream, ctx->peer, *F, ctx->grid, rows, ctx->peer_seq + 1, ctx->d_peer_status.get()));
+    ++ctx->peer_seq;
+    ++ctx->fold_exchange_count;
+    return CF_OK;
 }
 
 // cf_time_steps_coupled: what the block itself must satisfy (the schedule's scalars are checked already).  Every message names
@@ -456,11 +496,12 @@ static int check_coupled_block(cf_ctx* ctx, const cf_run_schedule* S, const cf_a
                         "solve would read different ice (pass NULL: every step takes its ice state's)", fn, n);
     }
     if (!K->skin_temperature) return fail(ctx, CF_ERR_INVALID, "%s: skin_temperature is NULL", fn);
+    if (S->fold_north) CHECK(check_fold_geometry(ctx, ctx->grid.ring + 1));   // (its messages name cf_fold_north_halo)
     if (S->halo_backend == CF_HALO_PEER) {
         if (!ctx->peer_connected)
             return fail(ctx, CF_ERR_INVALID, "%s: halo_backend = CF_HALO_PEER, but cf_peer_halo_connect has not been called", fn);
         int most = 0;   // the largest exchange of the call: the once-per-call set, and every ice state's split
-        PeerFields F[COUPLED_MAX_EXCHANGES];
+        FoldFields F[COUPLED_MAX_EXCHANGES];
         for (int n = -1; n < K->n_ice_states; ++n) {
             const int sets = n < 0 ? coupled_call_rows(ice, K, F) : coupled_step_rows(&S->ocean_states[0], &K->ice_states[n], F);
             for (int e = 0; e < sets; ++e) most = std::max(most, F[e].n);
@@ -468,8 +509,9 @@ static int check_coupled_block(cf_ctx* ctx, const cf_run_schedule* S, const cf_a
         if (most > ctx->peer_max_fields || S->halo_rows > ctx->peer_max_rows || S->halo_rows > ctx->grid.ny)
             return fail(ctx, CF_ERR_INVALID, "%s: halo_backend = CF_HALO_PEER: exchanges of up to %d fields × %d rows exceed the halo mailbox "
                         "(%d fields × %d rows) or ny = %d", fn, most, S->halo_rows, ctx->peer_max_fields, ctx->peer_max_rows, ctx->grid.ny);
-        if (S->fold_north)
-            return fail(ctx, CF_ERR_INVALID, "%s: fold_north with CF_HALO_PEER: nothing folds the ice rows on the last rank yet", fn);
+        if (S->fold_north && ctx->peer.north)
+            return fail(ctx, CF_ERR_INVALID, "%s: fold_north with CF_HALO_PEER on a rank with a north neighbour (rank %d of %d): the fold "
+                        "is the north side of the LAST rank's exchanges", fn, ctx->rank, ctx->nranks);
         if (K->normalize_salinity == 1)
             return fail(ctx, CF_ERR_INVALID, "%s: normalize_salinity = 1 under CF_HALO_PEER: its summation order depends on the slab; "
                         "CF_NORMALIZE_EXACT (2) gives the single domain's mean", fn);
@@ -656,10 +698,13 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
     static const int fold_loc[4] = {CF_FOLD_CENTER, CF_FOLD_CENTER, CF_FOLD_X_FACE, CF_FOLD_Y_FACE};
     static const double fold_sign[4] = {1.0, 1.0, -1.0, -1.0};
     const bool coupled_peer = K && S->halo_backend == CF_HALO_PEER;
+    // on the rank that owns the fold every exchange of the coupled loop folds its own fields as its north side (the four ocean
+    // fields ride in the step's first exchange): the same number of launches per step on every rank, and no fold launch of its own
+    const bool fold_in_exchange = coupled_peer && S->fold_north;
     if (coupled_peer && nsteps > 0) {   // once per call: afterwards both neighbours recompute the skin temperature's ring rows
-        PeerFields F[COUPLED_MAX_EXCHANGES];
+        FoldFields F[COUPLED_MAX_EXCHANGES];   // (and beyond the fold the solve recomputes its north ring row from folded inputs)
         const int sets = coupled_call_rows(ice, K, F);
-        for (int e = 0; e < sets; ++e) CHECK(cf_peer_halo_launch_now(ctx, &F[e], S->halo_rows));
+        for (int e = 0; e < sets; ++e) CHECK(coupled_exchange(ctx, &F[e], S->halo_rows, fold_in_exchange));
     }
     if (S->pipeline && nsteps > 0) {  // the first step's atmosphere, unless a previous call already started it
         const cf_atmos_source s0 = source_at(first_step);
@@ -691,9 +736,9 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
             CHECK(cf_halo_exchange_rows(ctx, rows, 4, S->halo_rows));
         else if (coupled_peer) {
             // (CF_OPT_HALO_IN_SOLVER_LAUNCH arms no request here: the coupled step's solver launch is not the one that carries riders)
-            PeerFields F[COUPLED_MAX_EXCHANGES];
+            FoldFields F[COUPLED_MAX_EXCHANGES];
             const int sets = coupled_step_rows(o, &K->ice_states[step % K->n_ice_states], F);
-            for (int e = 0; e < sets; ++e) CHECK(cf_peer_halo_launch_now(ctx, &F[e], S->halo_rows));
+            for (int e = 0; e < sets; ++e) CHECK(coupled_exchange(ctx, &F[e], S->halo_rows, fold_in_exchange));
         } else if (S->halo_backend == CF_HALO_PEER) {
             if (ctx->halo_in_launch) {   // (the mailbox takes 4 fields × halo_rows: check_peer_rows above)
                 // CF_OPT_HALO_IN_SOLVER_LAUNCH: left as a request — this step's solver launch carries the exchange as rider
@@ -707,7 +752,7 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
                 CHECK(cf_halo_exchange_rows_peer(ctx, rows, 4, S->halo_rows));
             }
         }
-        if (S->fold_north) CHECK(cf_fold_north_halo(ctx, rows, fold_loc, fold_sign, 4, ctx->grid.ring + 1));
+        if (S->fold_north && !fold_in_exchange) CHECK(cf_fold_north_halo(ctx, rows, fold_loc, fold_sign, 4, ctx->grid.ring + 1));
         const cf_sea_ice_state* is = K ? &K->ice_states[step % K->n_ice_states] : nullptr;
         if (K) {
             const cf_coupled_prepare P = prepare_at(step, o, is);

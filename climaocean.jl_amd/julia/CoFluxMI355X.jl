@@ -161,6 +161,13 @@ function peer_halo_stats(b)
     check(b.ctx, ccall((:cf_peer_halo_stats, libcoflux), Cint, (Ptr{Cvoid}, Ref{Culonglong}, Ref{Culonglong}), b.ctx, n, m))
     return (exchanges = n[], in_solver_launch = m[])
 end
+# fold launches of their own, and exchange launches whose north side was the tripolar fold (the last rank of time_steps_coupled!
+# under CF_HALO_PEER with fold_north), since the context was created
+function fold_counts(b)
+    n = Ref{Clonglong}(0); m = Ref{Clonglong}(0)
+    check(b.ctx, ccall((:cf_debug_fold_counts, libcoflux), Cint, (Ptr{Cvoid}, Ref{Clonglong}, Ref{Clonglong}), b.ctx, n, m))
+    return (fold_launches = n[], exchanges_with_fold = m[])
+end
 
 # ---- the three functions of update_state! ------------------------------------------------------
 # Each body is ONE ccall; these are the methods a maintainer adds for

@@ -1005,6 +1005,10 @@ int cf_peer_reduce_connect(cf_ctx* ctx, const void* handles, int rank, int nrank
  * width nx + 2hx; no other cell.                                                                                       */
 int cf_fold_north_halo(cf_ctx* ctx, double* const* d_fields, const int* locations, const double* signs, int nfields,
                        int rows);
+/* Since the context was created: the launches of the fold's own kernel (cf_fold_north_halo, and cf_time_steps / cf_time_steps_coupled
+ * with fold_north where they issue it), and the peer-direct exchange launches whose north side was the fold (cf_time_steps_coupled
+ * under CF_HALO_PEER with fold_north).  Either pointer may be NULL.  A measurement / test aid.                                */
+int cf_debug_fold_counts(cf_ctx* ctx, long long* fold_launches, long long* exchanges_with_fold);
 
 /* ------------------------------------------------------------------------------------------
  * run!(simulation) for a coupled model whose ocean component is prescribed (README.md:76-77): `nsteps` × time_step!
@@ -1067,7 +1071,8 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
  * salinity restoring on the top boundary condition and NormalizeSalinity at IterationInterval(1) (omip_simulation.jl:123-163,
  * :385-388, :507-523) — without returning to the host language.  cf_time_steps' arguments and clock, plus this block.  Per step
  * s (global index), on the context's stream, no host synchronisation:
- *   1. fold_north: cf_fold_north_halo on the four ocean rows, as cf_time_steps does;
+ *   1. fold_north: cf_fold_north_halo on the four ocean rows, as cf_time_steps does (under CF_HALO_PEER the fold is the north
+ *      side of the step's exchanges instead: "Tripolar slabs" below);
  *   2. the preamble (cf_prepare_coupled_step; each job optional): the land freshwater at the block's own clock — levels and
  *      fraction from land_first_level, land_time_fraction, land_time_fraction_increment by cf_time_steps' arithmetic — into
  *      land_freshwater, which the net ocean fluxes then read as if handed to cf_set_land_freshwater (it stays set after the
@@ -1105,12 +1110,26 @@ int cf_time_steps(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_sche
  * fields are non-NULL: THAT THOSE ARE THE SAME ON EVERY RANK, like the number of steps, is the caller's contract and is not
  * checked.  CF_OPT_HALO_IN_SOLVER_LAUNCH arms no request in this loop: its solver launch is not the one that carries riders.  The
  * x-halos of all these fields stay the caller's.  Attached collections collect per rank, as in cf_time_steps.
+ * Tripolar slabs: the LAST rank (no north mailbox) passes fold_north = 1 with CF_HALO_PEER, the others 0.  On that rank every
+ * exchange above is the SAME launch with the fold as its north side: workgroup 0 exchanges with the south neighbour, the others
+ * fold the north halo_rows rows of the exchange's own fields by cf_fold_north_halo's arithmetic, bit for bit, each field with its
+ * own location and sign —
+ *     T, S: centre, +1      ocean u: x-face, −1      ocean v: y-face, −1      ℵ, hᵢ, hₛ, albedo: centre, +1
+ *     ice u, v: centre, −1 (cf_sea_ice_state holds them at cell centres)
+ *     x_stress: x-face, −1      y_stress: y-face, −1      skin_temperature: centre, +1
+ * (coflux/distributed.py: coupled_fold_plan states the same table).  The four ocean fields ride in the step's first exchange: the
+ * rank issues no launch of cf_fold_north_halo's kernel in this loop, every rank issues the same number of launches per step, and
+ * cf_peer_halo_stats grows as above on every rank; cf_debug_fold_counts counts the exchanges that carried a fold.  The stresses and
+ * the skin temperature are folded once per call, exactly as a neighbour delivers them once per call; afterwards the skin
+ * temperature's north ring row is the solve's own result on the ring, computed from folded inputs.  Where a neighbour's rows leave
+ * the x-halos of the written rows to the sender's, the fold writes them itself, from the periodic image.  Under CF_HALO_NONE
+ * fold_north folds the four ocean rows by a launch of its own and the ice halos stay the caller's (tests/test_coupled_fold_*.py).
  * Refused with CF_ERR_INVALID before the first launch, outputs and cf_peer_halo_stats unchanged, the field named:
  *   halo_backend = CF_HALO_RCCL: nothing has exercised the ice rows or the global mean over RCCL;
  *   halo_backend = CF_HALO_PEER on a context whose halo mailboxes are not connected (cf_peer_halo_connect) or too small for the
  *     call's exchanges (the largest of them × halo_rows);
- *   fold_north together with CF_HALO_PEER: folding the ice rows on the last rank is the next follow-up (under CF_HALO_NONE the
- *     fold applies to the four ocean rows and the ice halos are the caller's);
+ *   fold_north on a grid the fold does not apply to (odd nx, ny < ring + 2), under either backend;
+ *   fold_north together with CF_HALO_PEER on a context whose north mailbox is connected: the last rank owns the fold;
  *   normalize_salinity = 1 under CF_HALO_PEER: its summation order depends on the slab;
  *   normalize_salinity = CF_NORMALIZE_EXACT under CF_HALO_PEER without a reduction world (cf_peer_reduce_connect).            */
 #define CF_NORMALIZE_EXACT 2
@@ -1139,7 +1158,9 @@ typedef struct cf_coupled_step {
 } cf_coupled_step;
 /* Footprint: per step cf_fold_north_halo's (fold_north), cf_prepare_coupled_step's, cf_update_state_sea_ice's,
  * cf_normalize_salinity_flux's (every cell of net->S, and *mean_out) and those of the attached collections; under CF_HALO_PEER
- * cf_halo_exchange_rows_peer's on the exchanged fields (the ice states' and the stresses' halo rows are WRITTEN).          */
+ * cf_halo_exchange_rows_peer's on the exchanged fields (the ice states' and the stresses' halo rows are WRITTEN); with fold_north
+ * under CF_HALO_PEER cf_fold_north_halo's on every exchanged field: the north halo_rows rows over the full width nx + 2hx, the
+ * x-halo columns of those rows included.                                                                                    */
 int cf_time_steps_coupled(cf_ctx* ctx, int64_t first_step, int nsteps, const cf_run_schedule* schedule,
                           const cf_atmos_source* src, const cf_interp_weights* w, const cf_interface_fluxes* fluxes,
                           const cf_sea_ice_fields* ice, const cf_net_ocean_fluxes* net, const cf_coupled_step* coupled);
