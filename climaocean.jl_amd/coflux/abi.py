@@ -403,7 +403,9 @@ def load_library(path=None):
             "(hipcc --offload-arch=gfx950). The HIP library is the only compute path.")
     lib = C.CDLL(p)
     vp = C.c_void_p
+    lib.cf_version.argtypes = []
     lib.cf_version.restype = C.c_int
+    lib.cf_build_stamp.argtypes = []
     lib.cf_build_stamp.restype = C.c_char_p
     want, have = source_stamp(), lib.cf_build_stamp().decode()
     if want is not None and have != want and os.environ.get("COFLUX_ALLOW_STALE_LIBRARY") != "1":

@@ -1,6 +1,8 @@
 """CPU-side checks of the drop-in boundary: libcoflux.so loads, exports every symbol that
-include/coflux.h declares, agrees with the ctypes mirror on struct sizes, and refuses to run
-without a GPU (no CPU fallback)."""
+include/coflux.h declares, agrees with the ctypes mirror on the size and the defaults of cf_flux_params,
+and refuses to run without a GPU (no CPU fallback).  What is compared HERE is symbol names and that one
+struct; every struct's field offsets against the host C compiler, every argtypes / restype against its
+prototype and the constants are compared in tests/test_abi_conformance.py."""
 import ctypes as C
 import os
 import re
