@@ -335,7 +335,7 @@ EXPORTED_SYMBOLS = (
     "cf_time_stage", "cf_time_copy", "cf_profile_enable", "cf_profile_read",
     "cf_comm_unique_id", "cf_comm_init", "cf_comm_destroy", "cf_halo_exchange_rows",
     "cf_peer_halo_export", "cf_peer_halo_connect", "cf_halo_exchange_rows_peer", "cf_peer_halo_stats", "cf_fold_north_halo",
-    "cf_debug_fold_counts",
+    "cf_debug_fold_counts", "cf_peer_tile_export", "cf_peer_tile_connect", "cf_halo_exchange_tile_peer", "cf_peer_tile_stats",
     "cf_time_steps", "cf_prefetch_atmosphere_state",
     "cf_default_sea_ice_albedo_params", "cf_set_sea_ice_albedo", "cf_compute_sea_ice_albedo",
     "cf_default_ice_ocean_params", "cf_compute_sea_ice_ocean_fluxes",
@@ -477,6 +477,10 @@ def load_library(path=None):
     lib.cf_peer_halo_connect.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     lib.cf_halo_exchange_rows_peer.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_int]
     lib.cf_fold_north_halo.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, C.c_int]
+    lib.cf_peer_tile_export.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.cf_peer_tile_connect.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.cf_halo_exchange_tile_peer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int]
+    lib.cf_peer_tile_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     lib.cf_time_steps.argtypes = [
         vp, C.c_int64, C.c_int, C.POINTER(RunSchedule), C.POINTER(AtmosSource), C.POINTER(InterpWeights),
         C.POINTER(InterfaceFluxes), C.POINTER(SeaIceFields), C.POINTER(NetOceanFluxes)]

@@ -182,3 +182,132 @@ def connect_coupled_slabs(ctx, max_fields=8, rows=None):
     ctx.peer_halo_connect(halo[rank - 1] if rank > 0 else None, halo[rank + 1] if rank < world - 1 else None, rank, world)
     ctx.peer_reduce_connect(reduce, rank, world)
     return rank, world
+
+
+# ---------------------------------------------------------------------------------------------
+# The tile world: a px × py partition of the surface (include/coflux.h: cf_peer_tile_*; the reference's
+# Partition(2,2), examples/sixth_degree_tripolar_ocean_sea_ice.jl:22).  rank = p + px · q, x fastest.
+# ---------------------------------------------------------------------------------------------
+def tile_coords(rank, px):
+    """(p, q) of `rank`: its column and row of ranks."""
+    return rank % px, rank // px
+
+
+def tile_bounds(nx, ny, rank, px, py):
+    """(i0, i1, j0, j1): the columns [i0, i1) and rows [j0, j1) `rank` owns.  Equal tile widths (px divides nx: the fold maps a
+    tile onto a whole tile only then); row blocks as slab_bounds cuts them."""
+    if nx % px:
+        raise ValueError(f"nx = {nx} is no multiple of px = {px}: tiles are equally wide")
+    p, q = tile_coords(rank, px)
+    nxl = nx // px
+    j0, j1 = slab_bounds(ny, q, py)
+    return p * nxl, (p + 1) * nxl, j0, j1
+
+
+def fold_partner(rank, px, py):
+    """The rank whose rows fold onto `rank`'s north halo on a tripolar world: (px − 1 − p, py − 1) for a rank of the top row
+    (itself when px = 1), None for every other rank."""
+    p, q = tile_coords(rank, px)
+    return (px - 1 - p) + px * q if q == py - 1 else None
+
+
+def connect_tiles(ctx, px, py, tripolar, max_fields=4, rows=None, cols=None):
+    """What cf_time_steps needs under CF_HALO_PEER on a px × py world: exports this rank's tile mailbox (`max_fields` fields ×
+    `rows` rows × `cols` columns; ring + 1 rows and ring + 2 columns by default, which serves the top row of a tripolar world
+    too), gathers the handles over torch.distributed and connects (cf_peer_tile_connect).  The process group's rank is the tile
+    rank p + px · q.  Every rank reaches the gather whatever happened locally, and every rank raises when an export failed
+    anywhere, as connect_coupled_slabs does.  Returns (rank, p, q); the ranks with q = py − 1 of a tripolar world pass
+    fold_north = 1 in their schedules, every other rank 0."""
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    if world != px * py:
+        raise ValueError(f"a {px} x {py} tile world needs {px * py} ranks, the process group has {world}")
+    rows = rows if rows is not None else ctx.grid.ring + 1
+    cols = cols if cols is not None else ctx.grid.ring + 2
+    mine, failure = None, None
+    try:
+        mine = ctx.peer_tile_export(max_fields=max_fields, max_rows=rows, max_cols=cols)
+    except Exception as exc:  # noqa: BLE001 — reported below, on every rank
+        failure = f"rank {rank}: {exc}"
+    gathered = [(mine, failure)]
+    if world > 1:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, (mine, failure))
+    failures = [f for _, f in gathered if f is not None]
+    if failures:
+        raise RuntimeError("no tile mailboxes: " + "; ".join(failures))
+    ctx.peer_tile_connect([h for h, _ in gathered], px, py, rank, tripolar)
+    return (rank,) + tile_coords(rank, px)
+
+
+def exchange_tile_halos_reference(tiles, px, py, hx, hy, ring=1, rows=None, tripolar=False, locations=None, signs=None):
+    """The tile exchange on NumPy arrays in one process, in place: tiles[rank][f] is field f of `rank`, halo-inclusive
+    (ny_q + 2hy, nxl + 2hx).  A plain statement of what cf_halo_exchange_tile_peer leaves — footprint included — written from
+    the global picture, not from the kernels:
+
+      x-phase (px > 1): the interior rows of the ring + 1 west halo columns come from the west neighbour's last interior columns,
+        those of the east halo columns from the east neighbour's first — ring + 2 east columns on the top row of a tripolar
+        world, whose x-face fold reads one column further;
+      y-phase: the `rows` south and north halo rows, full width, from the neighbours' boundary rows as the x-phase left them;
+        on the top row of a tripolar world the north halo rows, columns −(ring + 1) … nxl + ring only, are the fold of the GLOBAL
+        rows: the value at global column g comes from global column Nx − 1 − g (centres, y-faces) or Nx − g (x-faces, |sign| where
+        g ≡ 0), read from the partner's array at the image nearest its interior.  With px = 1 the fold is the rank's own, full
+        width from the periodic image, and the x-halos stay the caller's."""
+    import numpy as np
+    rows = ring + 1 if rows is None else rows
+    cols = ring + 1
+    nfields = len(tiles[0])
+    locations = locations or ["center"] * nfields
+    signs = signs or [1.0] * nfields
+    shape = lambda r: (tiles[r][0].shape[0] - 2 * hy, tiles[r][0].shape[1] - 2 * hx)   # noqa: E731  (ny, nxl)
+    nxl = shape(0)[1]
+    Nx = px * nxl
+    if px > 1:
+        incoming = []
+        for r in range(px * py):
+            p, q = tile_coords(r, px)
+            ny = shape(r)[0]
+            east_cols = cols + (1 if tripolar and q == py - 1 else 0)
+            west, east = (p - 1) % px + px * q, (p + 1) % px + px * q
+            for f in range(nfields):
+                incoming.append((r, f, slice(hx - cols, hx), tiles[west][f][hy:hy + ny, hx + nxl - cols:hx + nxl].copy()))
+                incoming.append((r, f, slice(hx + nxl, hx + nxl + east_cols), tiles[east][f][hy:hy + ny, hx:hx + east_cols].copy()))
+        for r, f, where, values in incoming:
+            tiles[r][f][hy:hy + shape(r)[0], where] = values
+    incoming = []
+    for r in range(px * py):
+        p, q = tile_coords(r, px)
+        ny = shape(r)[0]
+        for f in range(nfields):
+            if q > 0:
+                south = tiles[p + px * (q - 1)][f]
+                incoming.append((r, f, slice(hy - rows, hy), slice(None), south[south.shape[0] - hy - rows:south.shape[0] - hy].copy()))
+            if q < py - 1:
+                incoming.append((r, f, slice(hy + ny, hy + ny + rows), slice(None), tiles[p + px * (q + 1)][f][hy:hy + rows].copy()))
+            elif tripolar and px > 1:
+                partner = tiles[fold_partner(r, px, py)][f]
+                g0_partner = (px - 1 - p) * nxl
+                i = np.arange(-cols, nxl + cols)
+                g = (p * nxl + i) % Nx                                   # the global periodic image of my column
+                block = np.empty((rows, i.size))
+                for k in range(1, rows + 1):
+                    if locations[f] == "x_face":
+                        gs, js, sg = (Nx - g) % Nx, ny - 1 - k, np.where(g == 0, abs(signs[f]), signs[f])
+                    elif locations[f] == "y_face":
+                        gs, js, sg = Nx - 1 - g, ny - k, signs[f]
+                    else:
+                        gs, js, sg = Nx - 1 - g, ny - 1 - k, signs[f]
+                    local = gs - g0_partner                               # … in the partner's columns, at the image nearest its interior
+                    images = np.stack([local - Nx, local, local + Nx])
+                    distance = np.maximum(0, np.maximum(-images, images - (nxl - 1)))
+                    local = np.take_along_axis(images, np.argmin(distance, axis=0)[None], axis=0)[0]
+                    block[k - 1] = sg * partner[hy + js, hx + local]
+                incoming.append((r, f, slice(hy + ny, hy + ny + rows), slice(hx - cols, hx + nxl + cols), block))
+    for r, f, where_j, where_i, values in incoming:
+        tiles[r][f][where_j, where_i] = values
+    if tripolar and px == 1:
+        from .synthetic import fold_north
+        r = px * py - 1
+        for f in range(nfields):
+            fold_north(tiles[r][f], nxl, shape(r)[0], hx, hy, rows, locations[f], signs[f])
+    return tiles

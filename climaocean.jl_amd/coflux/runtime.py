@@ -693,6 +693,39 @@ class FluxContext:
         sg = (C.c_double * n)(*signs)
         self._check(self.lib.cf_fold_north_halo(self._h, arr, loc, sg, n, rows), "cf_fold_north_halo")
 
+    # -- the tile world: a px × py partition (cf_peer_tile_*) -----------------------------------------
+    def peer_tile_export(self, max_fields=4, max_rows=2, max_cols=3):
+        """This context's tile mailbox as a HIP IPC handle (cf_peer_tile_export).  max_cols: ring + 1, and one more on the top
+        row of a tripolar world with px > 1."""
+        buf = C.create_string_buffer(abi.PEER_HANDLE_BYTES)
+        self._check(self.lib.cf_peer_tile_export(self._h, max_fields, max_rows, max_cols, buf), "cf_peer_tile_export")
+        return buf.raw
+
+    def peer_tile_connect(self, handles, px, py, rank, tripolar):
+        """Join the px × py tile world as rank = p + px · q (cf_peer_tile_connect): `handles` is every rank's handle in rank
+        order (None for a world of one)."""
+        blob = None
+        if handles is not None:
+            assert all(len(h) == abi.PEER_HANDLE_BYTES for h in handles)
+            blob = C.create_string_buffer(b"".join(handles), len(handles) * abi.PEER_HANDLE_BYTES)
+        self._check(self.lib.cf_peer_tile_connect(self._h, blob, px, py, rank, 1 if tripolar else 0), "cf_peer_tile_connect")
+
+    def halo_exchange_tile_peer(self, tensors, locations=None, signs=None, rows=2, fold_north=False):
+        """One tile exchange of `tensors` (cf_halo_exchange_tile_peer): locations (abi.FOLD_*) and signs are read where
+        fold_north is set — on every rank of the top row of a tripolar world."""
+        n = len(tensors)
+        arr = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
+        loc = (C.c_int * n)(*locations) if locations is not None else None
+        sg = (C.c_double * n)(*signs) if signs is not None else None
+        self._check(self.lib.cf_halo_exchange_tile_peer(self._h, arr, loc, sg, n, rows, 1 if fold_north else 0), "cf_halo_exchange_tile_peer")
+
+    def tile_stats(self):
+        """(exchanges issued, x-phase launches, exchanges that sent a fold to a partner) since the context was created
+        (cf_peer_tile_stats)."""
+        a, b, c = C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
+        self._check(self.lib.cf_peer_tile_stats(self._h, C.byref(a), C.byref(b), C.byref(c)), "cf_peer_tile_stats")
+        return a.value, b.value, c.value
+
     # -- RCCL halo rows -------------------------------------------------------------------------
     def comm_init(self, unique_id: bytes, rank, nranks):
         buf = C.create_string_buffer(unique_id, abi.COMM_ID_BYTES)

@@ -333,3 +333,38 @@ def tripolar_case(nx, ny, hx, hy, *, j0=0, j1=None, rows=2, nsx=JRA55_NX, nsy=JR
     weights = dict(separable=False, fi=np.ascontiguousarray(fi), fj=np.ascontiguousarray(fj), cos_rot=np.ascontiguousarray(COS[sl]),
                    sin_rot=np.ascontiguousarray(SIN[sl]), latitude=np.ascontiguousarray(PHI[sl]))
     return dict(nx=nx, ny=j1 - j0, hx=hx, hy=hy, ocean=out, weights=weights, src=jra55_snapshots(2, nsx, nsy, seed))
+
+
+# ---------------------------------------------------------------------------------------------
+# tile cuts: columns i0:i1 beside rows j0:j1 (coflux.distributed.tile_bounds; include/coflux.h: cf_peer_tile_*)
+# ---------------------------------------------------------------------------------------------
+def _cut_columns(a, width, i0, i1, hx):
+    """columns [i0 − hx, i1 + hx) of every trailing axis of length `width` = nx + 2hx; other arrays as they are"""
+    if isinstance(a, np.ndarray) and a.ndim >= 1 and a.shape[-1] == width:
+        return np.ascontiguousarray(a[..., i0:i1 + 2 * hx])
+    return a
+
+
+def tripolar_tile_case(nx, ny, hx, hy, *, i0, i1, j0, j1, rows=2, nsx=JRA55_NX, nsy=JRA55_NY, seed=SEED):
+    """tripolar_case for the tile of columns [i0, i1) and rows [j0, j1) of the global nx × ny grid: every halo cell holds what
+    the global halo-inclusive array holds there — periodic in x, the fold beyond the top row, the neighbours' cells on inner
+    seams.  The source snapshots are the global ones."""
+    case = tripolar_case(nx, ny, hx, hy, j0=j0, j1=j1, rows=rows, nsx=nsx, nsy=nsy, seed=seed)
+    width = nx + 2 * hx
+    return dict(case, nx=i1 - i0, ocean={k: _cut_columns(v, width, i0, i1, hx) for k, v in case["ocean"].items()},
+                weights={k: _cut_columns(v, width, i0, i1, hx) for k, v in case["weights"].items()})
+
+
+def latlon_tile_case(nx, ny, hx, hy, *, i0, i1, j0, j1, n_levels=2, step=0, seed=SEED):
+    """The latitude–longitude case (ocean_state after `step` steps of evolved_ocean_state, separable weights) for the tile of
+    columns [i0, i1) and rows [j0, j1) of the global nx × ny grid; x-halos periodic, inner seams hold the neighbours' cells."""
+    nyl = j1 - j0
+    ocean = ocean_state(nx, nyl, hx, hy, ny_global=ny, j_offset=j0, seed=seed)
+    if step:
+        first = ocean
+        ocean = evolved_ocean_state(first, nx, nyl, hx, hy, step, ny_global=ny, j_offset=j0)
+        ocean["mask"] = first["mask"]
+    fi, fj, phi = latlon_fractional_indices(nx, nyl, hx, hy, ny_global=ny, j_offset=j0)
+    width = nx + 2 * hx
+    return dict(nx=i1 - i0, ny=nyl, hx=hx, hy=hy, ocean={k: _cut_columns(v, width, i0, i1, hx) for k, v in ocean.items()},
+                weights=dict(separable=True, fi=_cut_columns(fi, width, i0, i1, hx), fj=fj, latitude=phi), src=jra55_snapshots(n_levels, seed=seed))

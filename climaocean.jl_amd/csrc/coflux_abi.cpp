@@ -332,7 +332,6 @@ static int time_launches(cf_ctx* ctx, int launches, double* ms_per_launch, Launc
     return CF_OK;
 }
 
-void cf_peer_forget_local(const char* mailbox);  // coflux_steps.cpp
 
 extern "C" {
 
@@ -488,6 +487,7 @@ int cf_destroy(cf_ctx* ctx) {
         if (s) (void)hipStreamSynchronize(s);
     if (ctx->peer_mine) cf_peer_forget_local(ctx->peer_mine.get());
     if (ctx->reduce_mine) cf_peer_forget_local(ctx->reduce_mine.get());
+    if (ctx->tile.mine) cf_peer_forget_local(ctx->tile.mine.get());
     delete ctx;   // every member releases itself (coflux_owned.hpp)
     return CF_OK;
 }
@@ -620,7 +620,7 @@ int cf_sync(cf_ctx* ctx) {
     CHECK(cf_ahead_perform(ctx, &flush));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->aux.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->aux.stream.get()));
-    if (ctx->d_peer_status && (ctx->peer_seq || ctx->reduce_seq)) {  // a peer-direct exchange whose neighbour never arrived
+    if (ctx->d_peer_status && (ctx->peer_seq || ctx->reduce_seq || ctx->tile.seq)) {  // a peer-direct exchange whose neighbour never arrived
         int st = 0;
         HIP_TRY(ctx, hipMemcpy(&st, ctx->d_peer_status.get(), sizeof st, hipMemcpyDeviceToHost));
         if (st) {
@@ -628,6 +628,9 @@ int cf_sync(cf_ctx* ctx) {
             // mailbox protocol's sequence numbers only grow, a late arrival of the missed step disturbs nothing
             HIP_TRY(ctx, hipMemset(ctx->d_peer_status.get(), 0, sizeof st));
             if (st == 3) return fail(ctx, CF_ERR_COMM, "exact sum over the reduction world timed out waiting for another rank's accumulators");
+            if (st >= 4)   // a tile world's exchange (coflux_halo_device.hpp: tile_halo_x_side, tile_halo_y_side)
+                return fail(ctx, CF_ERR_COMM, "peer-direct tile exchange timed out waiting for the %s",
+                            st == 4 ? "west neighbour's columns" : st == 5 ? "east neighbour's columns" : "fold partner's rows");
             return fail(ctx, CF_ERR_COMM, "peer-direct halo exchange timed out waiting for the %s neighbour's rows",
                         st == 1 ? "south" : "north");
         }

@@ -181,6 +181,16 @@ struct cf_ctx {
     bool peer_connected = false;
     unsigned long long peer_seq = 0;
     cf::DeviceBuffer<int> d_peer_status;
+    // the tile world (cf_peer_tile_*; coflux_tiles.cpp): a context is slab-connected (above) or tile-connected, never both
+    struct TileWorld {
+        TileMailbox M{};                                 // raw views of `mine` and `maps`
+        cf::DeviceBuffer<char> mine;                     // this context's tile mailbox (fine-grained)
+        cf::IpcMapping maps[TILE_MAX_RANKS];             // the other ranks' this rank exchanges with, opened once each, by rank
+        TileNote note{};                                 // what `mine` was exported for
+        TilePlace place{};
+        bool connected = false, tripolar = false;
+        unsigned long long seq = 0, column_launches = 0, folds_sent = 0;   // cf_peer_tile_stats
+    } tile;
     // cf_debug_fold_counts: fold_north_kernel launches, and exchange launches whose north side was the fold (peer_halo_fold_kernel)
     long long fold_launch_count = 0, fold_exchange_count = 0;
     // the exact sums of cf_normalize_salinity_flux_exact (coflux_exact_sum.hip) and their reduction world (cf_peer_reduce_*)
@@ -363,6 +373,16 @@ int cf_fail(cf_ctx* ctx, int code, const char* fmt, ...);
 
 // coflux_steps.cpp: the stand-alone peer-direct exchange kernel for `F` (counts the exchange in ctx->peer_seq)
 extern "C" __attribute__((visibility("hidden"))) int cf_peer_halo_launch_now(cf_ctx* ctx, const PeerFields* F, int rows);
+// coflux_steps.cpp, for coflux_tiles.cpp: a mailbox behind an IPC handle (this process's own are found by their handle and used
+// as they are), the book of this process's own, and what the fold of `rows` rows needs of the grid
+extern "C" __attribute__((visibility("hidden"))) int cf_peer_map_mailbox(cf_ctx* ctx, const void* handle, char** out, cf::IpcMapping* mapping);
+void cf_peer_remember_local(const void* handle, char* mailbox, int device);
+void cf_peer_forget_local(const char* mailbox);
+extern "C" __attribute__((visibility("hidden"))) int check_fold_geometry(cf_ctx* ctx, int rows);
+// coflux_tiles.cpp: what one tile exchange of `nfields` × `rows` needs of the context and of the call (`fn` names the caller),
+// and the exchange itself — the x-phase, the y-phase, on a world one tile wide the local fold (counts it in ctx->tile.seq)
+int check_tile_exchange(cf_ctx* ctx, const char* fn, int nfields, int rows, int fold_north);
+int tile_exchange_launch(cf_ctx* ctx, const FoldFields* F, int rows, int fold_north);
 // coflux_checkpoint.cpp: waits for the restores of ctx's checkpoint handles that are still unchecked and compares their hashes
 int checkpoint_settle_restores(cf_ctx* ctx);
 // coflux_steps.cpp: queues what a transition of ctx->ahead answered with (AheadLedger::Work)

@@ -54,6 +54,35 @@ hipError_t launch_peer_halo_fold(hipStream_t st, const PeerMailbox& M, const Fol
 }
 
 // ---------------------------------------------------------------------------------------------
+// The tile world (include/coflux.h: cf_peer_tile_*): two launches per exchange on the context's stream, the columns first.  The
+// y-phase sends its rows full width, x-halos included, and the fold a north side sends reads this rank's east halo column:
+// both need the columns the x-phase delivers, and stream order is all that orders them.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PEER_BLOCK) void tile_halo_x_kernel(TileMailbox M, PeerFields F, GridDesc G, int wcols, int ecols,
+                                                                 unsigned long long seq, int* __restrict__ status) {
+    __shared__ int ok;
+    tile_halo_x_side(M, F.ptr, F.n, G, wcols, ecols, seq, status, TILE_W + (int)blockIdx.x, &ok);  // workgroup 0: west, 1: east
+}
+
+__global__ __launch_bounds__(PEER_BLOCK) void tile_halo_y_kernel(TileMailbox M, FoldFields F, GridDesc G, int rows, TileFold fold,
+                                                                 unsigned long long seq, int* __restrict__ status) {
+    __shared__ int ok;
+    tile_halo_y_side(M, F, G, rows, fold, seq, status, TILE_S + (int)blockIdx.x, &ok);  // workgroup 0: south, 1: north or the fold partner
+}
+
+hipError_t launch_tile_halo_x(hipStream_t st, const TileMailbox& M, const PeerFields& F, const GridDesc& G, int wcols, int ecols,
+                              unsigned long long seq, int* d_status) {
+    hipLaunchKernelGGL(tile_halo_x_kernel, dim3(2), dim3(PEER_BLOCK), 0, st, M, F, G, wcols, ecols, seq, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_halo_y(hipStream_t st, const TileMailbox& M, const FoldFields& F, const GridDesc& G, int rows, const TileFold& fold,
+                              unsigned long long seq, int* d_status) {
+    hipLaunchKernelGGL(tile_halo_y_kernel, dim3(2), dim3(PEER_BLOCK), 0, st, M, F, G, rows, fold, seq, d_status);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Tripolar fold: the north halo rows of the last slab from its own mirrored interior rows
 // (include/coflux.h: cf_fold_north_halo; Oceananigans zipper boundary condition, UPSTREAM-RECALL).
 // ---------------------------------------------------------------------------------------------

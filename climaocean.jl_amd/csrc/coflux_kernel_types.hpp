@@ -5,6 +5,7 @@
 
 #include "coflux_device.hpp"
 #include "coflux_exact_sum.hpp"
+#include "coflux_tile_geometry.hpp"
 
 namespace coflux {
 
@@ -154,6 +155,26 @@ struct FoldFields {
     double sign[PEER_MAX_FIELDS];
     int location[PEER_MAX_FIELDS];
     int n;
+};
+
+// The tile world's halo exchange (cf_peer_tile_*; coflux_halo.hip, host side coflux_tiles.cpp).  Sides: W, E, S, N
+// (coflux_tile_geometry.hpp: TILE_W …).  Every pointer is worked out by cf_peer_tile_connect from the notes the mailboxes carry:
+// a rank addresses the slots of a neighbour by the NEIGHBOUR's layout.  On the top row of a tripolar world with px > 1 the north
+// side is the fold partner, whose NORTH slot this rank writes; everywhere else a side writes the neighbour's opposite side.
+struct TileMailbox {
+    char* mine;              // this rank's mailbox: 8 flag lines [side][parity], the note's line, then the slots
+    char* remote[4];         // per side the neighbour's mailbox mapped into this process (nullptr: nobody on that side)
+    double* remote_slot[4];  // in that mailbox, parity 0 of the slot this rank's side writes (parity 1 follows at x_slot / y_slot)
+    double* my_slot[4];      // parity 0 of this rank's own slot per side
+    int remote_side[4];      // the side of the neighbour's mailbox (flag and slot) this rank's side writes
+    size_t x_slot, y_slot;   // doubles per (side, parity) slot: max_fields · max_cols · ny for W and E, max_fields · max_rows · sj for S and N
+};
+// The fold a tile's north side sends (top row of a tripolar world, px > 1): cols = 0 on every other rank.
+struct TileFold {
+    int cols;   // the folded rows are sent and copied in over columns −cols … nx − 1 + cols of the receiver
+    int g0;     // global column of the RECEIVER's (the partner's) interior column 0
+    int Nx;     // global number of columns
+    int pad;
 };
 
 // the surface monitor (coflux_monitor.hip)

@@ -203,6 +203,14 @@ hipError_t launch_peer_halo(hipStream_t st, const PeerMailbox& M, const PeerFiel
 hipError_t launch_peer_halo_fold(hipStream_t st, const PeerMailbox& M, const FoldFields& F, const GridDesc& G, int rows,
                                  unsigned long long seq, int* d_status);
 hipError_t launch_fold_north(hipStream_t st, const FoldFields& F, const GridDesc& G, int rows);
+// the two launches of a tile world's exchange (coflux_halo.hip): the x-halo columns, then the rows full width — on the top row of
+// a tripolar world with px > 1 the north side sends the fold partner its rows mirrored and signed (fold.cols > 0)
+struct TileMailbox;
+struct TileFold;
+hipError_t launch_tile_halo_x(hipStream_t st, const TileMailbox& M, const PeerFields& F, const GridDesc& G, int wcols, int ecols,
+                              unsigned long long seq, int* d_status);
+hipError_t launch_tile_halo_y(hipStream_t st, const TileMailbox& M, const FoldFields& F, const GridDesc& G, int rows, const TileFold& fold,
+                              unsigned long long seq, int* d_status);
 hipError_t launch_copy(hipStream_t st, void* dst, const void* src, size_t bytes);
 // cf_average_collect (coflux_average.hip): every field's interior mean m ← f (store) or m ← (m · c_prev) + (f · c_new), one launch
 struct AverageFields {

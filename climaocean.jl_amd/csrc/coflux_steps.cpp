@@ -102,6 +102,12 @@ void cf_peer_forget_local(const char* mailbox) {
         it = it->second.first == mailbox ? g_peer_local.erase(it) : std::next(it);
 }
 
+// cf_peer_tile_export (coflux_tiles.cpp): a mailbox of this process, found again by cf_peer_map_mailbox
+void cf_peer_remember_local(const void* handle, char* mailbox, int device) {
+    std::lock_guard<std::mutex> lock(g_peer_mutex);
+    g_peer_local[std::string((const char*)handle, CF_PEER_HANDLE_BYTES)] = {mailbox, device};
+}
+
 extern "C" {
 
 // ---- peer-direct halo rows --------------------------------------------------------------------
@@ -156,7 +162,7 @@ int cf_peer_halo_export(cf_ctx* ctx, int max_fields, int max_rows, void* handle_
 }
 
 // `*out`: the neighbour's mailbox behind `handle` (NULL without one); `*mapping` owns it where HIP IPC had to open it
-static int map_mailbox(cf_ctx* ctx, const void* handle, char** out, cf::IpcMapping* mapping) {
+int cf_peer_map_mailbox(cf_ctx* ctx, const void* handle, char** out, cf::IpcMapping* mapping) {
     *out = nullptr;
     mapping->reset();
     if (!handle) return CF_OK;
@@ -212,12 +218,14 @@ static void disconnect_peers(cf_ctx* ctx) {
 int cf_peer_halo_connect(cf_ctx* ctx, const void* south_handle, const void* north_handle, int rank, int nranks) {
     if (!ctx || nranks <= 0 || rank < 0 || rank >= nranks) return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: bad arguments");
     if (!ctx->peer_mine) return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: call cf_peer_halo_export first");
+    if (ctx->tile.connected)
+        return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: this context is connected to a tile world (cf_peer_tile_connect): slabs or tiles");
     if ((rank > 0) != (south_handle != nullptr) || (rank < nranks - 1) != (north_handle != nullptr))
         return fail(ctx, CF_ERR_INVALID, "cf_peer_halo_connect: rank %d of %d needs %s south and %s north handle", rank, nranks,
                     rank > 0 ? "a" : "no", rank < nranks - 1 ? "a" : "no");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = map_mailbox(ctx, south_handle, &ctx->peer.south, &ctx->peer_south_map);
-    if (rc == CF_OK) rc = map_mailbox(ctx, north_handle, &ctx->peer.north, &ctx->peer_north_map);
+    int rc = cf_peer_map_mailbox(ctx, south_handle, &ctx->peer.south, &ctx->peer_south_map);
+    if (rc == CF_OK) rc = cf_peer_map_mailbox(ctx, north_handle, &ctx->peer.north, &ctx->peer_north_map);
     if (rc == CF_OK) rc = check_mailbox_shape(ctx, ctx->peer.south, "south");
     if (rc == CF_OK) rc = check_mailbox_shape(ctx, ctx->peer.north, "north");
     if (rc != CF_OK) {
@@ -332,7 +340,7 @@ int cf_peer_reduce_connect(cf_ctx* ctx, const void* handles, int rank, int nrank
             table[r] = ctx->reduce_mine.get();
             continue;
         }
-        rc = map_mailbox(ctx, (const char*)handles + (size_t)r * CF_PEER_HANDLE_BYTES, &table[r], &ctx->reduce_maps[r]);
+        rc = cf_peer_map_mailbox(ctx, (const char*)handles + (size_t)r * CF_PEER_HANDLE_BYTES, &table[r], &ctx->reduce_maps[r]);
         if (rc != CF_OK) break;
         ReduceNote theirs{};
         hipError_t e = hipMemcpy(&theirs, table[r], sizeof theirs, hipMemcpyDeviceToHost);
@@ -364,7 +372,7 @@ int cf_peer_reduce_connect(cf_ctx* ctx, const void* handles, int rank, int nrank
 }
 
 // what the fold of `rows` rows needs of the grid (cf_fold_north_halo, and cf_time_steps with fold_north before its first step)
-static int check_fold_geometry(cf_ctx* ctx, int rows) {
+int check_fold_geometry(cf_ctx* ctx, int rows) {
     const GridDesc& G = ctx->grid;
     if (rows < 1 || rows > G.hy || rows + 1 > G.ny)
         return fail(ctx, CF_ERR_INVALID, "cf_fold_north_halo: rows = %d outside [1, min(hy, ny − 1)]", rows);
@@ -655,6 +663,9 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
         return P;
     };
     if (K) {   // everything the steps' own entry points would refuse, before the first launch: the outputs stay untouched
+        if (ctx->tile.connected && ctx->tile.place.px > 1)
+            return fail(ctx, CF_ERR_INVALID, "%s: this context is connected to a tile world with px = %d: the ice rows and the stresses do not cross "
+                        "x yet; cf_time_steps steps a tile world, the coupled loop latitude slabs (px = 1, cf_peer_halo_connect)", name, ctx->tile.place.px);
         CHECK(check_coupled_block(ctx, S, src, w, fluxes, ice, net, K));
         if (dataset) {
             if (K->target_salinity)
@@ -686,10 +697,16 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
     // cf_time_steps: everything one of its steps would refuse, at whichever step, is refused here — before the first launch and
     // before anything of the context changes (the chunk table, the ledger of requested states, the halo request, the land-zero
     // scope), as check_coupled_block does for the coupled form.  Behind the attachments: which refusal a call with two gets …
+    // A tile-connected context (cf_peer_tile_connect): CF_HALO_PEER is the tile exchange of the four ocean fields, whose check
+    // covers the mailbox, the geometry and whether fold_north agrees with the rank's place in the world.
+    const bool tile_peer = ctx->tile.connected && S->halo_backend == CF_HALO_PEER;
     if (!K) {
         CHECK(check_step_arguments(ctx, src, w, S, fluxes, net));
-        if (S->fold_north) CHECK(check_fold_geometry(ctx, ctx->grid.ring + 1));
-        if (S->halo_backend == CF_HALO_PEER) CHECK(check_peer_rows(ctx, 4, S->halo_rows));
+        if (ctx->tile.connected && S->halo_backend == CF_HALO_RCCL)
+            return fail(ctx, CF_ERR_INVALID, "%s: halo_backend = CF_HALO_RCCL on a context connected to a tile world: CF_HALO_PEER", name);
+        if (tile_peer) CHECK(check_tile_exchange(ctx, name, 4, S->halo_rows, S->fold_north));
+        else if (S->fold_north) CHECK(check_fold_geometry(ctx, ctx->grid.ring + 1));
+        if (S->halo_backend == CF_HALO_PEER && !tile_peer) CHECK(check_peer_rows(ctx, 4, S->halo_rows));
     }
     CHECK(cf_ensure_chunk_table(ctx, S->ocean_states[0].mask));
     // CF_OPT_HALO_IN_SOLVER_LAUNCH: a step's request lives from its arming below to the cf_update_state of the same iteration;
@@ -739,6 +756,17 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
             FoldFields F[COUPLED_MAX_EXCHANGES];
             const int sets = coupled_step_rows(o, &K->ice_states[step % K->n_ice_states], F);
             for (int e = 0; e < sets; ++e) CHECK(coupled_exchange(ctx, &F[e], S->halo_rows, fold_in_exchange));
+        } else if (tile_peer) {
+            // (CF_OPT_HALO_IN_SOLVER_LAUNCH arms no request on a tile world: the exchange kernels run.  On a world one tile wide
+            // the exchange ends with the local fold's launch)
+            FoldFields F{};
+            F.n = 4;
+            for (int f = 0; f < 4; ++f) {
+                F.ptr[f] = rows[f];
+                F.location[f] = fold_loc[f];
+                F.sign[f] = fold_sign[f];
+            }
+            CHECK(tile_exchange_launch(ctx, &F, S->halo_rows, S->fold_north));
         } else if (S->halo_backend == CF_HALO_PEER) {
             if (ctx->halo_in_launch) {   // (the mailbox takes 4 fields × halo_rows: check_peer_rows above)
                 // CF_OPT_HALO_IN_SOLVER_LAUNCH: left as a request — this step's solver launch carries the exchange as rider
@@ -752,7 +780,7 @@ static int time_steps_loop(cf_ctx* ctx, const char* name, int64_t first_step, in
                 CHECK(cf_halo_exchange_rows_peer(ctx, rows, 4, S->halo_rows));
             }
         }
-        if (S->fold_north && !fold_in_exchange) CHECK(cf_fold_north_halo(ctx, rows, fold_loc, fold_sign, 4, ctx->grid.ring + 1));
+        if (S->fold_north && !fold_in_exchange && !tile_peer) CHECK(cf_fold_north_halo(ctx, rows, fold_loc, fold_sign, 4, ctx->grid.ring + 1));
         const cf_sea_ice_state* is = K ? &K->ice_states[step % K->n_ice_states] : nullptr;
         if (K) {
             const cf_coupled_prepare P = prepare_at(step, o, is);

@@ -329,6 +329,23 @@ halo_exchange_rows_peer!(b, fields::Vector{Ptr{Float64}}, rows = 2) =
 fold_north_halo!(b, fields::Vector{Ptr{Float64}}, locations::Vector{Cint}, signs::Vector{Float64}, rows = 2) =
     check(b.ctx, ccall((:cf_fold_north_halo, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Cint}, Ptr{Float64}, Cint, Cint),
                        b.ctx, fields, locations, signs, length(fields), rows))
+# The tile world, Distributed(GPU(), partition = Partition(px, py)): rank = p + px · q, x fastest, every tile nx columns wide.  A
+# context joins latitude slabs (peer_halo_connect!) or a tile world, not both.  max_cols: ring + 1, and one more on the top row of
+# a tripolar world with px > 1.  `handles`: every rank's handle in rank order (MPI.Allgather), `nothing` for a world of one.
+peer_tile_export!(b, max_fields = 4, max_rows = 2, max_cols = 3) = (h = zeros(UInt8, 64);
+    check(b.ctx, ccall((:cf_peer_tile_export, libcoflux), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{UInt8}), b.ctx, max_fields, max_rows, max_cols, h)); h)
+peer_tile_connect!(b, handles::Union{Nothing, Vector{Vector{UInt8}}}, px, py, rank, tripolar::Bool) =
+    check(b.ctx, ccall((:cf_peer_tile_connect, libcoflux), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Cint, Cint, Cint, Cint), b.ctx,
+                       isnothing(handles) ? C_NULL : reduce(vcat, handles), px, py, rank, tripolar ? 1 : 0))
+# fold_north: true on every rank of the top row of a tripolar world, false on every other; locations and signs as fold_north_halo!
+halo_exchange_tile_peer!(b, fields::Vector{Ptr{Float64}}, locations::Vector{Cint}, signs::Vector{Float64}, rows = 2, fold_north::Bool = false) =
+    check(b.ctx, ccall((:cf_halo_exchange_tile_peer, libcoflux), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Cint}, Ptr{Float64}, Cint, Cint, Cint),
+                       b.ctx, fields, locations, signs, length(fields), rows, fold_north ? 1 : 0))
+function peer_tile_stats(b)
+    n = Ref{Culonglong}(0); m = Ref{Culonglong}(0); k = Ref{Culonglong}(0)
+    check(b.ctx, ccall((:cf_peer_tile_stats, libcoflux), Cint, (Ptr{Cvoid}, Ref{Culonglong}, Ref{Culonglong}, Ref{Culonglong}), b.ctx, n, m, k))
+    return (exchanges = n[], column_launches = m[], folds_sent = k[])
+end
 
 # ---- pipelined update_state!: the prescribed atmosphere of the NEXT step on the auxiliary stream ---------------------
 prefetch_atmosphere_state!(b, src_next::CfAtmosSource, w::CfInterpWeights, out::CfExchangeFields) =

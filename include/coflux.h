@@ -964,6 +964,66 @@ int cf_halo_exchange_rows_peer(cf_ctx* ctx, double* const* d_fields, int nfields
  * (CF_OPT_HALO_IN_SOLVER_LAUNCH) instead of the exchange kernel of their own.  A measurement / test aid.      */
 int cf_peer_halo_stats(cf_ctx* ctx, unsigned long long* exchanges, unsigned long long* in_solver_launch);
 
+/* The tile world: the surface partitioned in BOTH directions (the reference's Distributed(GPU(), partition = Partition(2,2)),
+ * examples/sixth_degree_tripolar_ocean_sea_ice.jl:22).  A rectangular world of px × py ranks, rank = p + px · q — x FASTEST.
+ * Rank (p, q) owns columns [p · nx, (p + 1) · nx) of the global Nx = px · nx and one contiguous block of rows.  EVERY RANK HAS
+ * THE SAME nx (the fold maps a tile onto a whole tile only then); row blocks may differ between rows of ranks; the ranks of one
+ * row share ny and hy, the ranks of one column — and fold partners — share nx and hx.  x is periodic: the east neighbour of p
+ * is (p + 1) mod px; with px = 2 both x-neighbours are one rank, served by separate slots and flags.  y is not periodic.  px is
+ * 1 or even.  On the top row (q = py − 1) of a tripolar world the north side is the FOLD PARTNER (px − 1 − p, py − 1); with
+ * px = 1 that is the rank itself, nothing is mapped and cf_fold_north_halo's kernel serves.  A context is connected to latitude
+ * slabs (cf_peer_halo_connect) or to a tile world, never to both; each refuses a context the other has connected.
+ *   cf_peer_tile_export   allocates this rank's tile mailbox in fine-grained device memory (CF_ERR_COMM where the device has
+ *                         none to give) and writes its IPC handle: eight flags [side W, E, S, N][parity] on 64-byte lines of
+ *                         their own, one line that carries the tuple the mailbox was exported for — (max_fields, max_rows,
+ *                         max_cols, nx + 2hx, ny, hx, hy) —, then two parities of a slot per side: max_fields · max_cols · ny
+ *                         doubles for W and E, max_fields · max_rows · (nx + 2hx) for S and N.  1 ≤ max_fields ≤ 8,
+ *                         1 ≤ max_rows ≤ hy, 1 ≤ max_cols ≤ hx; a step needs max_rows ≥ ring + 1 and max_cols ≥ ring + 1, on the
+ *                         top row of a tripolar world with px > 1 max_cols ≥ ring + 2 (see the footprint).
+ *   cf_peer_tile_connect  `handles`: px · py × CF_PEER_HANDLE_BYTES, entry r from rank r.  Maps the W, E, S and N neighbours (each
+ *                         rank once, however many sides it serves) and compares the tuple each mailbox carries with this
+ *                         rank's: W and E in (ny, hy, max_*), S, N and the partner in (nx + 2hx, hx, max_*).  CF_ERR_INVALID —
+ *                         with both tuples in the message where tuples differ —, nothing launched and the context left
+ *                         unconnected, whatever it was connected to before, for: a difference; px, py < 1 or a rank outside
+ *                         the world; px odd and greater than 1; px · py > CF_PEER_REDUCE_MAX_RANKS; tripolar with an odd
+ *                         Nx = px · nx; a handle that is no tile mailbox; a context connected to latitude slabs.  A world of one
+ *                         (px = py = 1) maps nothing; handles may be NULL.  Every rank of a world has issued the same number
+ *                         of exchanges when it connects (zero, normally): the caller's contract, not checked.
+ *   cf_halo_exchange_tile_peer  one exchange of 1 … max_fields fields × 1 … min(max_rows, ny, hy) rows.  fold_north = 1 on EVERY
+ *                         rank of the top row of a tripolar world and 0 on every other rank (anything else is refused);
+ *                         locations[f] ∈ CF_FOLD_*, signs[f] = ±1 as for cf_fold_north_halo, read only where fold_north = 1
+ *                         (NULL otherwise).  nfields, rows and the locations ARE THE SAME ON EVERY RANK: not checked.
+ *   cf_peer_tile_stats    since the context was created: exchanges issued (one sequence number each), x-phase launches (one
+ *                         per exchange where px > 1, none where px = 1) and exchanges whose north side sent a fold to a partner
+ *                         (every exchange on the top row of a tripolar world with px > 1, none elsewhere).  A test aid.
+ * One exchange, on the context's stream, no host synchronisation, one sequence number for both phases:
+ *   1. x-phase (px > 1; with px = 1 the x-halos stay the caller's), one launch of two workgroups: each side stores its ring + 1
+ *      boundary COLUMNS of every field, interior rows 0 … ny − 1, into the x-neighbour's slot as [field][column][row] (a wave's
+ *      remote stores are one contiguous run), publishes, waits (bounded) and copies the received columns into its x-halo columns.
+ *   2. y-phase (where a south or north neighbour or a partner exists), one launch behind the first: the S and N rows travel
+ *      full width nx + 2hx by the protocol of cf_halo_exchange_rows_peer — the sender's x-halos are filled, so the corner
+ *      cells arrive without a diagonal message.  Towards the fold partner the SENDER writes the partner's north halo rows
+ *      already mirrored and signed: the partner's halo row ny − 1 + r at its column i is sign · (this rank's value) at column
+ *      nx − 1 − i, row ny − 1 − r (centres), column nx − 1 − i, row ny − r (y-faces), column nx − i, row ny − 1 − r (x-faces; sign
+ *      is |sign| exactly where the GLOBAL periodic image of the partner's column is 0): cf_fold_north_halo's rule through the
+ *      tile's global column offset, −0.0 surviving as there.  The x-face map reads this rank's east halo columns up to
+ *      nx + ring + 1, which is why the columns travel first and why the x-phase fills ring + 2 east columns on such a rank.
+ *   3. With px = 1 and fold_north the exchange ends with cf_fold_north_halo's own launch (counted by cf_debug_fold_counts).
+ * A wait that exceeds its bound copies nothing and sets the sticky error the next cf_sync reports (CF_ERR_COMM), naming the
+ * side: the west or east neighbour's columns, the south or north neighbour's rows, the fold partner's rows.
+ * Footprint: DEFINES every halo cell within ring + 1 (= rows, as cf_time_steps passes them) of the interior, corners included —
+ * what a step's kernels read.  Written beyond that: the S and N halo rows over the full width (outside the ring + 1 columns
+ * they hold whatever the sender's x-halo held there); on a rank that sends a fold, east halo column nx + ring + 1 on the
+ * interior rows.  The folded north rows are written over columns −(ring + 1) … nx + ring ONLY: the x-face map has no source for
+ * column −hx inside the partner's array, and the outer columns of those rows are left UNTOUCHED.  No other cell: the W and E halo
+ * columns of the halo rows come with the rows, never from the x-phase.  Requires nx ≥ ring + 1 and hx ≥ ring + 1 where px > 1
+ * (ring + 2 both where a fold is sent), and with fold_north ny ≥ rows + 1.                                                  */
+int cf_peer_tile_export(cf_ctx* ctx, int max_fields, int max_rows, int max_cols, void* handle_out);
+int cf_peer_tile_connect(cf_ctx* ctx, const void* handles, int px, int py, int rank, int tripolar);
+int cf_halo_exchange_tile_peer(cf_ctx* ctx, double* const* d_fields, const int* locations, const double* signs, int nfields, int rows,
+                               int fold_north);
+int cf_peer_tile_stats(cf_ctx* ctx, unsigned long long* exchanges, unsigned long long* column_launches, unsigned long long* folds_sent);
+
 /* The reduction world of the exact sums (cf_normalize_salinity_flux_exact).  Halo mailboxes connect neighbours; a global sum needs
  * every rank, so every rank owns a second, small mailbox in fine-grained device memory that EVERY other rank maps: two parities ×
  * CF_PEER_REDUCE_MAX_RANKS slots (the accumulators of Σ J·A and Σ A with their non-finite counters, 140 64-bit words) and one
@@ -1042,7 +1102,14 @@ int cf_debug_fold_counts(cf_ctx* ctx, long long* fold_launches, long long* excha
  * BEFORE the first launch and before anything of the context changes (behind the refusals of the schedule's own scalars
  * and of what is attached, in that order).  A refused call has written nothing, requested no atmosphere state ahead and
  * left nothing for a later call to trip over: the next cf_update_state or cf_time_steps on the context runs as if the
- * refused call had not been made (tests/test_refused_step_calls.py).                                           */
+ * refused call had not been made (tests/test_refused_step_calls.py).
+ * Tile worlds: on a context connected by cf_peer_tile_connect, halo_backend = CF_HALO_PEER runs cf_halo_exchange_tile_peer's
+ * exchange of T, S, u, v per step (centre, centre, x-face, y-face; signs +, +, −, −) with halo_rows rows; fold_north = 1 is
+ * passed by EVERY rank of the top row of a tripolar world and by no other.  CF_OPT_HALO_IN_SOLVER_LAUNCH arms no request
+ * there: the exchange kernels run.  Refused before the first launch, under the contract above: a tile mailbox too small for
+ * 4 fields × halo_rows rows × ring + 1 columns (ring + 2 where a fold is sent); fold_north that disagrees with the rank's place
+ * in the world; halo_backend = CF_HALO_RCCL.  cf_time_steps_coupled refuses a tile world with px > 1 by name: the ice rows and
+ * the stresses do not cross x yet (tests/test_tile_steps.py).                              */
 #define CF_PIPELINE_WITHIN_CALL 1
 #define CF_PIPELINE_CONTINUING 2
 #define CF_HALO_NONE 0
