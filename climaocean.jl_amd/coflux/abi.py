@@ -280,7 +280,7 @@ class MonitorEntry(C.Structure):
 
 class MonitorDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_entries", C.c_int32), ("mask", C.c_void_p), ("first_cell", C.c_int64),
-                ("max_workgroups", C.c_int32), ("reserved", C.c_int32), ("entries", MonitorEntry * MONITOR_MAX_ENTRIES)]
+                ("max_workgroups", C.c_int32), ("row_length", C.c_int32), ("entries", MonitorEntry * MONITOR_MAX_ENTRIES)]
 
 
 class MonitorValue(C.Structure):

@@ -311,3 +311,102 @@ def exchange_tile_halos_reference(tiles, px, py, hx, hy, ring=1, rows=None, trip
         for f in range(nfields):
             fold_north(tiles[r][f], nxl, shape(r)[0], hx, hy, rows, locations[f], signs[f])
     return tiles
+
+
+# ---------------------------------------------------------------------------------------------
+# Diagnostics on a sharded run: the host's combination of per-rank results into the single domain's (the "Slabs" sentences
+# of include/coflux.h).  NumPy only, no device code.  Running means, climatologies and their weights need no combination:
+# each rank holds its own rows and columns of the single domain's arrays.
+# ---------------------------------------------------------------------------------------------
+def _order_key(x):
+    """the IEEE total order of the non-NaN doubles as an unsigned integer (include/coflux.h, cf_monitor: "Order")"""
+    import struct
+    b = struct.unpack("<Q", struct.pack("<d", float(x)))[0]
+    return b ^ 0xFFFFFFFFFFFFFFFF if b >> 63 else b ^ (1 << 63)
+
+
+def combine_monitor_records(per_rank):
+    """The whole surface's cf_monitor_value records from the ranks' (include/coflux.h, cf_monitor: "Slabs and tiles"), every
+    rank having monitored its part with first_cell = j0·Nx + i0 and row_length = Nx.  `per_rank`: arrays of
+    abi.MONITOR_VALUE_DTYPE of one shape (a value, a record [n_entries], a series [n, n_entries]); returns that shape.
+    minimum / maximum combine in the IEEE total order (−0.0 < +0.0) with the smaller argmin / argmax on ties, −1 and ±Inf where
+    no rank has a cell; nan_count / inf_count add; first_nonfinite is the smallest that is not −1; hashes add mod 2⁶⁴."""
+    import numpy as np
+    from . import abi
+    ranks = [np.asarray(r, dtype=abi.MONITOR_VALUE_DTYPE) for r in per_rank]
+    if not ranks or any(r.shape != ranks[0].shape for r in ranks):
+        raise ValueError("combine_monitor_records: one array of records per rank, all of one shape")
+    out = np.zeros(ranks[0].shape, dtype=abi.MONITOR_VALUE_DTYPE)
+    flat = out.reshape(-1)
+    for at in range(flat.size):
+        values = [r.reshape(-1)[at] for r in ranks]
+        lo = min(((_order_key(v["minimum"]), int(v["argmin"]), v["minimum"]) for v in values if v["argmin"] >= 0), key=lambda x: x[:2], default=None)
+        hi = min(((-_order_key(v["maximum"]), int(v["argmax"]), v["maximum"]) for v in values if v["argmax"] >= 0), key=lambda x: x[:2], default=None)
+        V = flat[at]
+        V["minimum"], V["argmin"] = (lo[2], lo[1]) if lo else (np.inf, -1)
+        V["maximum"], V["argmax"] = (hi[2], hi[1]) if hi else (-np.inf, -1)
+        V["nan_count"] = sum(int(v["nan_count"]) for v in values)
+        V["inf_count"] = sum(int(v["inf_count"]) for v in values)
+        V["first_nonfinite"] = min((int(v["first_nonfinite"]) for v in values if v["first_nonfinite"] >= 0), default=-1)
+        V["hash"] = sum(int(v["hash"]) for v in values) % (1 << 64)
+    return out
+
+
+def combine_integral_records(per_rank):
+    """The whole surface's integrals from the ranks' (include/coflux.h, cf_integrals: "Slabs"): per record and entry the sum
+    over the ranks.  `per_rank`: float64 arrays of one shape; returns that shape.
+
+    Rounding: each entry is math.fsum of the ranks' values — the exact sum of the doubles given, rounded once, so the result
+    does not depend on the order of the ranks.  It is NOT the bits of the single domain's record: every rank's value already
+    carries the rounding of its own device sum (a fixed order over its own cells), and the single domain adds the same terms in
+    another order.  Both lie within γ(n − 1) · Σ|term| of the exact sum of their n terms, γ(n) = n·u / (1 − n·u), u = 2⁻⁵³;
+    the combination adds at most one more rounding, u · |result|.  A NaN or an infinity in any rank's entry gives what IEEE
+    addition gives (math.fsum raises on Inf − Inf; that entry is NaN here)."""
+    import math
+    import numpy as np
+    ranks = [np.asarray(r, dtype=np.float64) for r in per_rank]
+    if not ranks or any(r.shape != ranks[0].shape for r in ranks):
+        raise ValueError("combine_integral_records: one array of records per rank, all of one shape")
+    out = np.zeros(ranks[0].shape)
+    flat = out.reshape(-1)
+    for at in range(flat.size):
+        terms = [float(r.reshape(-1)[at]) for r in ranks]
+        try:
+            flat[at] = math.fsum(terms)
+        except (ValueError, OverflowError):   # Inf − Inf, or an intermediate overflow: plain IEEE addition
+            with np.errstate(all="ignore"):
+                flat[at] = np.add.reduce(np.array(terms))
+    return out
+
+
+def restrict_operator(op, nx_global, i0, i1, j0, j1):
+    """The operator a rank applies to its own tile (include/coflux.h, cf_regrid: "Slabs"): the same destination rows, of each
+    row the entries whose source cell c = j·nx_global + i lies in the columns [i0, i1) and rows [j0, j1), in their order,
+    renumbered to the tile's interior (j − j0)·(i1 − i0) + (i − i0).  `op`: (row_ptr, col, weight) or a SurfaceOperator; returns
+    (row_ptr int64, col int32, weight float64).  A row with no entry in the tile is an empty row."""
+    import numpy as np
+    row_ptr, col, weight = op
+    row_ptr = np.asarray(row_ptr, dtype=np.int64)
+    col, weight = np.asarray(col, dtype=np.int64), np.asarray(weight, dtype=np.float64)
+    j, i = col // nx_global, col % nx_global
+    keep = (i >= i0) & (i < i1) & (j >= j0) & (j < j1)
+    kept_before = np.concatenate([[0], np.cumsum(keep)])          # kept entries in front of each position
+    local = (j - j0) * (i1 - i0) + (i - i0)
+    return kept_before[row_ptr].astype(np.int64), local[keep].astype(np.int32), weight[keep].copy()
+
+
+def combine_regridded(numerators, coverages):
+    """The single domain's CF_REGRID_MEAN from the ranks' CF_REGRID_SUM applies of their restricted operators: Σ_ranks N / Σ_ranks D
+    per destination row, NaN where the summed coverage is 0 (no wet source cell on any rank).  `numerators`: per rank an array
+    [..., n_rows] (one field, or [n_fields, n_rows]); `coverages`: per rank [n_rows].  The sums run over the ranks in the order
+    given, one IEEE addition each."""
+    import numpy as np
+    N = [np.asarray(n, dtype=np.float64) for n in numerators]
+    D = [np.asarray(d, dtype=np.float64) for d in coverages]
+    if not N or len(N) != len(D) or any(n.shape != N[0].shape for n in N) or any(d.shape != N[0].shape[-1:] for d in D):
+        raise ValueError("combine_regridded: per rank one numerator array [..., n_rows] and one coverage [n_rows]")
+    num, cov = N[0].copy(), D[0].copy()
+    for n, d in zip(N[1:], D[1:]):
+        num, cov = num + n, cov + d
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(cov == 0, np.nan, num / np.where(cov == 0, 1.0, cov))

@@ -582,9 +582,15 @@ def _model_monitor(model, fields, capacity):
     return ctx.monitor(list(fields.values()), mask=mask, capacity=capacity)
 
 
-def _cell(c, nx):
-    """(j, i) of the interior cell numbered c = j·nx + i; (−1, −1) for none"""
-    return (int(c) // nx, int(c) % nx) if c >= 0 else (-1, -1)
+def _cell(c, row_length):
+    """(j, i) on the whole surface of the cell numbered c = j·row_length + i; (−1, −1) for none"""
+    return (int(c) // row_length, int(c) % row_length) if c >= 0 else (-1, -1)
+
+
+def _row_length(monitor, model):
+    """The row length `monitor` numbers its cells with: its own, or the model grid's nx where it left that 0 (or is a
+    monitor that knows no row length: one made with first_cell alone numbers its rows with nx)"""
+    return getattr(monitor, "row_length", 0) or model.ocean.grid.size[0]
 
 
 class SurfaceExtrema(_SeriesWriter):
@@ -598,8 +604,8 @@ class SurfaceExtrema(_SeriesWriter):
     def __init__(self, model, outputs, schedule=None, capacity=4096):
         self.model, self.names = model, list(outputs)
         self._begin(schedule)
-        self.nx = model.ocean.grid.size[0]
         self.monitor = _model_monitor(model, outputs, capacity)
+        self.row_length = _row_length(self.monitor, model)
 
     def series(self):
         """{name: {"min", "max", "argmin", "argmax", "nan_count", "inf_count", "first_nonfinite", "hash"}}: arrays of n records;
@@ -608,7 +614,7 @@ class SurfaceExtrema(_SeriesWriter):
         out = {}
         for k, name in enumerate(self.names):
             v = values[:, k]
-            pairs = lambda c: np.array([_cell(x, self.nx) for x in c], dtype=np.int64).reshape(len(c), 2)  # noqa: E731
+            pairs = lambda c: np.array([_cell(x, self.row_length) for x in c], dtype=np.int64).reshape(len(c), 2)  # noqa: E731
             out[name] = {"min": v["minimum"].copy(), "max": v["maximum"].copy(), "argmin": pairs(v["argmin"]), "argmax": pairs(v["argmax"]),
                          "nan_count": v["nan_count"].copy(), "inf_count": v["inf_count"].copy(),
                          "first_nonfinite": pairs(v["first_nonfinite"]), "hash": v["hash"].copy()}
@@ -756,7 +762,7 @@ class NaNChecker:
         e = (entries & -entries).bit_length() - 1          # the lowest entry that had one
         value = self.monitor.read()[0][0, e]
         if self.first is None:
-            self.first = (model.clock.iteration, self.names[e], _cell(value["first_nonfinite"], model.ocean.grid.size[0]))
+            self.first = (model.clock.iteration, self.names[e], _cell(value["first_nonfinite"], _row_length(self.monitor, model)))
         _log.error("NaNChecker: %s is not finite at %s, iteration %d: the simulation stops", self.names[e], self.first[2], model.clock.iteration)
         sim.running = False
 

@@ -572,11 +572,12 @@ class FluxContext:
         self._attach_series("integrals", integrator, stride, time_origin, step_seconds)
 
     # -- surface monitor --------------------------------------------------------------------------
-    def monitor(self, entries, mask=None, first_cell=0, capacity=1024, max_workgroups=0):
+    def monitor(self, entries, mask=None, first_cell=0, capacity=1024, max_workgroups=0, row_length=0):
         """A device-side time series of extrema, non-finite counts and state hashes (cf_monitor_create).  `entries`: up to
         abi.MONITOR_MAX_ENTRIES ocean-grid float64 fields or (field, "value" | "abs") pairs (abi.MONITOR_* work too);
-        `mask`: the context's wet mask; `first_cell`: the global index of this slab's interior cell (0, 0)."""
-        return SurfaceMonitor(self, entries, mask, first_cell, capacity, max_workgroups)
+        `mask`: the context's wet mask; `first_cell`: the global index j0·Nx + i0 of this slab's or tile's interior cell
+        (0, 0); `row_length`: the global row length Nx of a tile's surface (0: the context's nx)."""
+        return SurfaceMonitor(self, entries, mask, first_cell, capacity, max_workgroups, row_length)
 
     def attach_monitor(self, monitor, stride=1, time_origin=0.0, step_seconds=1.0):
         """time_steps() appends a record of `monitor` after every step s with (s + 1) % stride == 0, stamped
@@ -950,15 +951,16 @@ class SurfaceMonitor(_SeriesHandle):
     synchronisations.  The library borrows the pointers: the tensors are kept alive here."""
     _destroy, _family, _dtype = "cf_monitor_destroy", "monitor", abi.MONITOR_VALUE_DTYPE
 
-    def __init__(self, ctx, entries, mask=None, first_cell=0, capacity=1024, max_workgroups=0):
+    def __init__(self, ctx, entries, mask=None, first_cell=0, capacity=1024, max_workgroups=0, row_length=0):
         self._adopt(ctx)
         entries = [tuple(e) if isinstance(e, (tuple, list)) else (e, "value") for e in entries]
         self.n_entries, self.capacity, self.first_cell = len(entries), int(capacity), int(first_cell)
+        self.row_length = int(row_length)   # as given: 0 stands for the context's nx
         if self.n_entries > abi.MONITOR_MAX_ENTRIES:
             raise ValueError(f"{self.n_entries} entries (at most {abi.MONITOR_MAX_ENTRIES})")
         desc = abi.MonitorDesc()
         desc.struct_size, desc.n_entries, desc.max_workgroups = C.sizeof(abi.MonitorDesc), self.n_entries, int(max_workgroups)
-        desc.first_cell = self.first_cell
+        desc.first_cell, desc.row_length = self.first_cell, self.row_length
         self._keep = [mask]
         if mask is not None:
             if not _is_field(mask, ctx, None):

@@ -201,7 +201,8 @@ struct MonitorArgs {
     MonitorStatus* status;            // device
     double z_surface;
     int64_t first_cell;
-    int32_t mask_kind, n_entries, slices, pad;
+    int32_t mask_kind, n_entries, slices;
+    int32_t row_length;               // ≥ nx: cell (i, j) of the interior is numbered first_cell + j·row_length + i
 };
 
 inline SourceDesc make_source(const cf_atmos_source* s) {

@@ -22,12 +22,15 @@ int cf_monitor_create(cf_ctx* ctx, const cf_monitor_desc* desc, int32_t capacity
         if (!E.a) return fail(ctx, CF_ERR_INVALID, "cf_monitor_create: entry %d has a NULL a", e);
         entry[e] = MonitorEntry{E.a, E.kind, 0};
     }
+    if (desc->row_length < 0 || (desc->row_length > 0 && desc->row_length < ctx->grid.nx))
+        return fail(ctx, CF_ERR_INVALID, "cf_monitor_create: row_length %d (0: nx, or ≥ nx = %d)", desc->row_length, ctx->grid.nx);
     MonitorArgs K{};
     K.n_entries = desc->n_entries;
     K.mask_kind = desc->mask ? ctx->dev.mask_kind : CF_MASK_NONE;
     K.mask = K.mask_kind == CF_MASK_NONE ? nullptr : desc->mask;
     K.z_surface = ctx->dev.z_surface;
     K.first_cell = desc->first_cell;
+    K.row_length = desc->row_length > 0 ? desc->row_length : ctx->grid.nx;
     K.slices = monitor_slices(ctx->grid, K.n_entries);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // one allocation: [capacity][n_entries] series | [n_entries][slices] partials | entries | status

@@ -8,7 +8,8 @@
 // order-preserving integer key of the bits with the cell index as tie-break, integer sums, a minimum of indices, a wrapping
 // 64-bit sum — so the partition of the cells is free and is chosen for bandwidth: no fixed summation order, no
 // floating-point comparison (v_min_f64 / v_max_f64 treat NaN and ±0 by a mode), no floating-point or other atomics.
-//   1. the interior is numbered row by row, c = j·nx + i (the record holds first_cell + c), and cut into pairs (2p, 2p + 1);
+//   1. the interior is walked row by row, local cell j·nx + i, and cut into pairs (2p, 2p + 1); the record holds the global
+//      number c = first_cell + j·row_length + i of a cell (row_length = nx unless the context is a tile of a wider surface);
 //   2. the work is (entry, slice): slice s of `slices` owns the pairs p ≡ s·256 + t (mod slices·256), thread t keeps the
 //      entry's eight running values in registers over that stride;
 //   3. the 64 lanes of a wave are merged by a butterfly, the four waves through LDS → partial[entry][slice] (64 bytes);
@@ -136,12 +137,13 @@ __global__ __launch_bounds__(MONITOR_BLOCK) void monitor_pass_kernel(MonitorArgs
             const bool v1 = C.v1;
             const ulonglong2 x = load_pair_bits(E.a, C);
             const PairWet wet = pair_wet(K.mask, K.mask_kind, K.z_surface, C);
-            const int64_t c = K.first_cell + (int64_t)c0;
-            const uint64_t h0 = HASH_K * (uint64_t)(c + 1);
-            R.hash += mix64(x.x ^ h0);
+            // each cell is numbered from its own (i, j): the pair that wraps starts row j + 1 of the global numbering
+            const int64_t row = K.first_cell + (int64_t)C.j0 * (int64_t)K.row_length;
+            const int64_t c = row + (int64_t)C.i0, c1 = C.wrap ? row + (int64_t)K.row_length : c + 1;
+            R.hash += mix64(x.x ^ (HASH_K * (uint64_t)(c + 1)));
             take(R, x.x, c, wet.s0, absolute);
-            if (v1) R.hash += mix64(x.y ^ (h0 + HASH_K));
-            take(R, x.y, c + 1, wet.s1, absolute);
+            if (v1) R.hash += mix64(x.y ^ (HASH_K * (uint64_t)(c1 + 1)));
+            take(R, x.y, c1, wet.s1, absolute);
         }
         R = wave_merge(R);
         if ((t & 63u) == 0u) put_partial(&wave_part[t >> 6], R);

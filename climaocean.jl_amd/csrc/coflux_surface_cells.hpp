@@ -25,9 +25,11 @@ __device__ __forceinline__ double blend(double m, double f, double c_prev, doubl
 
 // The interior is numbered row by row, c = j·nx + i; a thread takes the cells c0 (even) and c0 + 1.  k0 / k1: their element
 // offsets in a halo-layout array, v0 / v1: whether they exist (a cell that does not is never loaded), pair: both in one row.
+// (i0, j0): the first cell's column and row; wrap: it ends its row, so the second cell is (0, j0 + 1).
 struct CellPair {
     size_t k0, k1;
-    bool v0, v1, pair;
+    unsigned i0, j0;
+    bool v0, v1, pair, wrap;
 };
 
 // GUARD = false: the caller knows c0 < n_cells
@@ -39,7 +41,7 @@ __device__ __forceinline__ CellPair cell_pair(unsigned c0, unsigned n_cells, con
     const unsigned j1 = wrap ? j0 + 1u : j0, i1 = wrap ? 0u : i0 + 1u;
     const size_t k0 = (size_t)(j0 + G.hy) * (size_t)G.sj + (size_t)(i0 + G.hx);
     const size_t k1 = v1 ? (size_t)(j1 + G.hy) * (size_t)G.sj + (size_t)(i1 + G.hx) : k0;
-    return CellPair{k0, k1, v0, v1, v1 && !wrap};
+    return CellPair{k0, k1, i0, j0, v0, v1, v1 && !wrap, wrap};
 }
 
 // The pair's two values of one array as raw bits, zero for a cell that does not exist.  Alignment only chooses the width of

@@ -589,17 +589,18 @@ struct CfMonitorDesc
     struct_size::Int32; n_entries::Int32
     mask::Ptr{Cvoid}
     first_cell::Int64
-    max_workgroups::Int32; reserved::Int32
+    max_workgroups::Int32; row_length::Int32
     entries::NTuple{16, CfMonitorEntry}
 end
-function CfMonitorDesc(entries::Vector{CfMonitorEntry}; mask = C_NULL, first_cell = 0, max_workgroups = 0)
+# first_cell = j0·Nx + i0 and row_length = Nx on a slab or tile of an Nx-wide surface; row_length = 0: the context's nx
+function CfMonitorDesc(entries::Vector{CfMonitorEntry}; mask = C_NULL, first_cell = 0, max_workgroups = 0, row_length = 0)
     length(entries) <= 16 || error("CoFluxMI355X: at most 16 monitor entries")
     padded = ntuple(k -> k <= length(entries) ? entries[k] : CfMonitorEntry(), 16)
-    return CfMonitorDesc(sizeof(CfMonitorDesc), length(entries), mask, first_cell, max_workgroups, 0, padded)
+    return CfMonitorDesc(sizeof(CfMonitorDesc), length(entries), mask, first_cell, max_workgroups, row_length, padded)
 end
 struct CfMonitorValue      # 64 bytes
     minimum::Float64; maximum::Float64
-    argmin::Int64; argmax::Int64          # global cell numbers first_cell + j·nx + i (0-based), -1: none
+    argmin::Int64; argmax::Int64          # global cell numbers first_cell + j·row_length + i (0-based), -1: none
     nan_count::Int64; inf_count::Int64
     first_nonfinite::Int64
     hash::UInt64

@@ -1541,7 +1541,9 @@ int cf_attach_integrals(cf_ctx* ctx, cf_integrals* q, int32_t stride, double tim
  * (:671-683) and the NaNChecker every Oceananigans Simulation carries.  A monitor holds up to CF_MONITOR_MAX_ENTRIES
  * entries (an ocean-grid f64 field x and a kind: y = x, or y = |x| with the sign bit cleared, so |−0| = +0, |−Inf| = +Inf)
  * and a series of `capacity` records in device memory that the library owns; one collection appends one record of
- * n_entries values of type cf_monitor_value, 64 bytes each.  Interior cells are numbered c = first_cell + j·nx + i.
+ * n_entries values of type cf_monitor_value, 64 bytes each.  Interior cell (i, j) is numbered
+ * c = first_cell + j·row_length + i, where row_length = 0 stands for the context's own nx: a context that holds a whole
+ * surface, or whole rows of one, leaves it 0.
  *   Order.  minimum / maximum are taken over the wet interior cells whose x is not NaN, in the IEEE total order of the
  *     non-NaN doubles: −0.0 < +0.0, and ±Inf take part.  A field that holds both zeros and nothing smaller has minimum
  *     −0.0 at the index of its first −0.0.  Ties go to the smallest c.  The device compares the order-preserving integer
@@ -1561,16 +1563,21 @@ int cf_attach_integrals(cf_ctx* ctx, cf_integrals* q, int32_t stride, double tim
  *     own hash, not Julia's hash(::Array); it serves the same purpose, comparing two runs without moving a field.
  *   Exactness.  Every quantity is an exact, associative and commutative reduction (integer-key min / max with an index
  *     tie-break, integer sums, a wrapping sum): the bits of a record depend only on the interior values, the mask and
- *     first_cell — not on the launch geometry or `max_workgroups`, the halo widths, where the arrays start in memory, the
- *     device's CU count, or on whether the host or cf_time_steps made the collection.  No floating-point atomics.
- *   Slabs.  Each context monitors its own slab with its first_cell.  The hash is a wrapping sum: the hashes of latitude
- *     slabs add up, mod 2⁶⁴, to the hash of the whole surface; nan_count / inf_count add; minimum / maximum combine in
- *     the same order with the smaller argmin / argmax on ties, first_nonfinite is the smallest that is not −1 — the
- *     host's combination of a few words.
+ *     first_cell and row_length — not on the launch geometry or `max_workgroups`, the halo widths, where the arrays
+ *     start in memory, the device's CU count, or on whether the host or cf_time_steps made the collection.  No
+ *     floating-point atomics.
+ *   Slabs and tiles.  Each context monitors its own part of an Nx × Ny surface: the rank whose interior cell (0, 0) is
+ *     the surface's cell (i0, j0) passes first_cell = j0·Nx + i0 and row_length = Nx (a latitude slab, i0 = 0 and
+ *     nx = Nx, may leave row_length 0), so that c is the cell's number on the whole surface on every rank.  The hash is
+ *     a wrapping sum: the hashes of the parts add up, mod 2⁶⁴, to the hash of the whole surface; nan_count / inf_count
+ *     add; minimum / maximum combine in the same order with the smaller argmin / argmax on ties, first_nonfinite is the
+ *     smallest that is not −1 — the host's combination of a few words.  With row_length = nx < Nx on a tile, c is not
+ *     the global number and none of this holds.
  *   One collection is one pass per entry over the interior plus a single-workgroup combination launch: 8 bytes per cell
  *   and entry, and the mask once per ENTRY (not once per cell): n_entries · (8 + mask bytes) per cell in all.
  *   cf_monitor_create   CF_ERR_INVALID for a wrong struct_size, n_entries outside 1…CF_MONITOR_MAX_ENTRIES, a NULL `a`, an
- *                       unknown kind, max_workgroups < 0 or capacity < 1.  The pointers are borrowed: the arrays outlive
+ *                       unknown kind, max_workgroups < 0, capacity < 1, row_length < 0 or 0 < row_length < nx (the
+ *                       message names the field); nothing is allocated.  The pointers are borrowed: the arrays outlive
  *                       the monitor.  The same array may be named by several entries.
  *   cf_monitor_destroy  detaches the monitor if it is attached; a monitor outlived by its context may still be destroyed
  *                       (every other call on it then fails).
@@ -1606,9 +1613,9 @@ typedef struct cf_monitor_desc {
     int32_t struct_size;   /* sizeof(cf_monitor_desc) */
     int32_t n_entries;     /* 1…CF_MONITOR_MAX_ENTRIES */
     const void* mask;      /* wet mask of the context's mask kind (CF_MASK_U8 / _BOTTOM_HEIGHT); NULL or CF_MASK_NONE: all wet */
-    int64_t first_cell;    /* global index of this slab's interior cell (0, 0) */
+    int64_t first_cell;    /* global index of this slab's or tile's interior cell (0, 0): j0·Nx + i0 */
     int32_t max_workgroups; /* 0: the library's choice; > 0 caps the launch (scheduling only: never a bit of a record) */
-    int32_t reserved;
+    int32_t row_length;    /* 0: nx; else the global row length Nx ≥ nx (it took the place of a reserved word: additive) */
     cf_monitor_entry entries[CF_MONITOR_MAX_ENTRIES];
 } cf_monitor_desc;
 typedef struct cf_monitor_value {   /* 64 bytes */

@@ -819,7 +819,7 @@ DEFECTS = {
     "ccall_last_type_dropped": ("ccall cf_h2d", "3 argument types where the prototype has 4", "4 arguments follow a tuple of 3"),
     "ccall_device_alloc_returns_cint": ("ccall cf_device_alloc", "return type", "i32 where the header has ptr"),
     "julia_field_is_mutable_struct": ("CfCoupledPrepare.ice_ocean", "CfIceOceanParams is a mutable struct"),
-    "ctypes_fields_swapped": ("ctypes MonitorDesc (cf_monitor_desc)", "field 4 is reserved where the header has max_workgroups"),
+    "ctypes_fields_swapped": ("ctypes MonitorDesc (cf_monitor_desc)", "field 4 is row_length where the header has max_workgroups"),
     "ctypes_cint_widened": ("ctypes cf_set_option", "argument 1 (option)", "i64 where the header has i32"),
     "ctypes_pointee_retyped": ("ctypes cf_regrid_create", "argument 1 (desc)", "struct cf_monitor_desc where the header has struct cf_regrid_desc"),
     "constant_off_by_one": ("Julia: CF_NORMALIZE_EXACT = 3 where the header has 2", "ctypes: CF_NORMALIZE_EXACT = 3 where the header has 2"),
@@ -835,8 +835,8 @@ def replace_once(text, old, new):
 
 def defective_stub(text, defect):
     if defect == "julia_fields_swapped":       # two adjacent Int32 of CfMonitorDesc
-        return replace_once(text, "max_workgroups::Int32; reserved::Int32\n    entries::NTuple{16, CfMonitorEntry}",
-                            "reserved::Int32; max_workgroups::Int32\n    entries::NTuple{16, CfMonitorEntry}")
+        return replace_once(text, "max_workgroups::Int32; row_length::Int32\n    entries::NTuple{16, CfMonitorEntry}",
+                            "row_length::Int32; max_workgroups::Int32\n    entries::NTuple{16, CfMonitorEntry}")
     if defect == "ccall_cint_widened":
         return replace_once(text, "(:cf_set_option, libcoflux), Cint, (Ptr{Cvoid}, Cint, Cint)", "(:cf_set_option, libcoflux), Cint, (Ptr{Cvoid}, Int64, Cint)")
     if defect == "ccall_last_type_dropped":

@@ -29,17 +29,27 @@ def mix64(z):
     return z ^ (z >> np.uint64(31))
 
 
-def cell_hashes(x, first_cell=0):
-    """mix64(bits(x_c) XOR K·(c + 1)) per cell, c = first_cell + position in the flattened array"""
+def cell_numbers(x, first_cell=0, row_length=0):
+    """c of every cell of `x`, flattened (int64).  row_length = 0: first_cell + position in the flattened array (any shape);
+    row_length > 0: `x` is (ny, nx) with nx ≤ row_length and c = first_cell + j·row_length + i."""
+    if row_length == 0:
+        return first_cell + np.arange(np.size(x), dtype=np.int64)
+    ny, nx = np.shape(x)
+    assert row_length >= nx, (row_length, nx)
+    return (first_cell + np.arange(ny, dtype=np.int64)[:, None] * row_length + np.arange(nx, dtype=np.int64)[None, :]).ravel()
+
+
+def cell_hashes(x, first_cell=0, row_length=0):
+    """mix64(bits(x_c) XOR K·(c + 1)) per cell, c of cell_numbers"""
     b = bits(x).ravel()
     with np.errstate(over="ignore"):
-        c1 = (np.arange(b.size, dtype=np.uint64) + np.uint64((first_cell + 1) % (1 << 64))) * K
+        c1 = (cell_numbers(x, first_cell, row_length) + 1).astype(np.uint64) * K      # (a negative c + 1 wraps mod 2⁶⁴)
     return mix64(b ^ c1)
 
 
-def state_hash(x, first_cell=0):
+def state_hash(x, first_cell=0, row_length=0):
     """Σ_c mix64(bits(x_c) XOR K·(c + 1)) mod 2⁶⁴ as a Python int"""
-    return int(np.add.reduce(cell_hashes(x, first_cell), dtype=np.uint64)) if np.size(x) else 0      # (uint64 sums wrap)
+    return int(np.add.reduce(cell_hashes(x, first_cell, row_length), dtype=np.uint64)) if np.size(x) else 0      # (uint64 sums wrap)
 
 
 def order_key(b):
@@ -53,28 +63,29 @@ def key_value(k):
     return from_bits(np.where(k >> np.uint64(63) != 0, k ^ SIGN, k ^ ALL))
 
 
-def monitor_value(x, wet=None, kind="value", first_cell=0):
+def monitor_value(x, wet=None, kind="value", first_cell=0, row_length=0):
     """One cf_monitor_value (a numpy record of abi.MONITOR_VALUE_DTYPE) of the interior array `x` (any shape, row-major cell
-    numbering) under the boolean / uint8 array `wet` (None: all wet)."""
+    numbering; (ny, nx) with row_length > 0: cell_numbers) under the boolean / uint8 array `wet` (None: all wet)."""
     b = bits(x).ravel()
+    c = cell_numbers(x, first_cell, row_length)
     w = np.ones(b.size, bool) if wet is None else np.asarray(wet).ravel() != 0
     mag = b & ~SIGN
     nan, inf = mag > EXPONENT, mag == EXPONENT
     out = np.zeros((), dtype=DTYPE)
     out["nan_count"], out["inf_count"] = int((w & nan).sum()), int((w & inf).sum())
     bad = np.flatnonzero(w & (nan | inf))
-    out["first_nonfinite"] = first_cell + int(bad[0]) if bad.size else -1
+    out["first_nonfinite"] = int(c[bad[0]]) if bad.size else -1
     keys = order_key(mag if kind in ("abs", abi.MONITOR_ABS) else b)
     sel = np.flatnonzero(w & ~nan)
     if sel.size:
         k = keys[sel]
         lo, hi = k.min(), k.max()
         out["minimum"], out["maximum"] = key_value(lo), key_value(hi)
-        out["argmin"] = first_cell + int(sel[np.flatnonzero(k == lo)[0]])      # the smallest c that holds it
-        out["argmax"] = first_cell + int(sel[np.flatnonzero(k == hi)[0]])
+        out["argmin"] = int(c[sel[np.flatnonzero(k == lo)[0]]])      # the smallest c that holds it (c grows with the position)
+        out["argmax"] = int(c[sel[np.flatnonzero(k == hi)[0]]])
     else:
         out["minimum"], out["maximum"], out["argmin"], out["argmax"] = np.inf, -np.inf, -1, -1
-    out["hash"] = state_hash(x, first_cell)
+    out["hash"] = state_hash(x, first_cell, row_length)
     return out
 
 
