@@ -118,7 +118,7 @@ __device__ __forceinline__ void lean_zero_cell(const LoopParams& L, double T_off
 // wait, after their own start phase, for the riders' counter: interior chunks never wait, and the neighbours' latency
 // passes under interior work instead of in front of the launch.  The same rows arrive by the same protocol: bitwise the step
 // with the stand-alone exchange kernel (tests/test_steps.py).
-template <bool COARE, bool FUSE, bool TAIL = false, bool CERT = false, bool LINE = false, bool HALO = false>
+template <bool COARE, bool FUSE, bool TAIL = false, bool CERT = false, bool LINE = false, bool HALO = false, bool BURST_BOUNDARY = true>
 __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
     constexpr int BLOCK = AO_BLOCK;
     using Geo = LeanGeom<BLOCK>;
@@ -381,10 +381,21 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
                 continue;
             }
         }
-        // ---- waves pull 64 wet cells at a time; the NEXT batch's inputs are requested before this batch iterates ------
-        // (a batch's eleven loads take ≈ 2 µs to come back and its ≈ 2000 FP64 instructions ≈ 6 µs to issue: requested
-        // one batch ahead, the loads cost 23 registers across the iteration and no wait)
+        // ---- waves pull 64 wet cells at a time.  A batch boundary is ONE burst of memory requests right behind the
+        // iteration (BURST: every form but CERT, whose queue logic keeps the order it was measured with, and the rider of the
+        // sea-ice interface launch, BURST_BOUNDARY = false, which measured 0.4 % slower with it): the claim of the
+        // next batch, THIS batch's epilogue loads (the fused net fluxes' inputs), the NEXT batch's eleven input loads —
+        // then the epilogue's arithmetic, ONE wait for both groups of loads, this batch's stores, the next batch's
+        // prologue.  The two groups are in flight together (one memory latency per boundary instead of two), and the wait
+        // stands in front of every store: stores count in vmcnt like loads on gfx9, so a first use of the next batch's
+        // inputs behind them would wait for their acknowledgements as well (the order until now: epilogue loads, wait,
+        // stores, claim, input loads, wait for loads AND stores — per-wave stamps put the two waits at 0.61 + 0.34 µs per
+        // batch, 3.0 µs along the longest chain of three, and the one that is left at 0.40 µs, 1.6 µs along that chain:
+        // profiles/batch_boundary_experiments.md).  Nothing is held across the iteration for it: the next batch's inputs
+        // live from the burst to their prologue, where the iteration's temporaries are dead, and what crosses the
+        // iteration is the prologue's result, as before.  Every wait is the compiler's own — no hand-written count.
         // (results the step's other launches do not read: streamed when this launch assembles the net fluxes itself — gstore_final)
+        constexpr bool BURST = BURST_BOUNDARY && !CERT;
         auto store_result = [&](double* base, unsigned byte_off, double v) {
             if constexpr (FUSE) gstore_final(base, byte_off, v);
             else gstore(base, byte_off, v);
@@ -445,6 +456,10 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
         int start = claim();
         Raw raw{};
         if (start < nwet) raw = request(start);
+        LeanCell ahead{};  // BURST: the prologue of the batch about to iterate (computed behind the previous batch's burst)
+        if constexpr (BURST) {
+            if (start < nwet) ahead = lean_prologue(P, L.kappa, tab, raw.ua, raw.va, raw.Ta, raw.pa, raw.qa, 0.5 * (raw.u0 + raw.u1), 0.5 * (raw.v0 + raw.v1), raw.To, raw.So);
+        }
         for (;;) {
             if constexpr (CERT) {
                 if (!straggling && start >= nwet) {
@@ -477,9 +492,10 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
             if constexpr (CERT) {
                 if (!straggling) Mp_now = gload(opaque(K)->E.Mp, (unsigned)cell_of(start) * 8u);
             }
-            // ℑxᶜᵃᵃ u, ℑyᵃᶜᵃ v: cell-centre ocean velocity from the two bracketing faces
-            const LeanCell c = lean_prologue(P, L.kappa, tab, raw.ua, raw.va, raw.Ta, raw.pa, raw.qa, 0.5 * (raw.u0 + raw.u1),
-                                             0.5 * (raw.v0 + raw.v1), raw.To, raw.So);
+            // ℑxᶜᵃᵃ u, ℑyᵃᶜᵃ v: cell-centre ocean velocity from the two bracketing faces (BURST: done behind the previous boundary)
+            LeanCell c;
+            if constexpr (BURST) c = ahead;
+            else c = lean_prologue(P, L.kappa, tab, raw.ua, raw.va, raw.Ta, raw.pa, raw.qa, 0.5 * (raw.u0 + raw.u1), 0.5 * (raw.v0 + raw.v1), raw.To, raw.So);
             // the interface temperature does not depend on the iteration: written now, not carried across it
             if (in_range) store_result(opaque(K)->F.Ts, (unsigned)cell_of(start) * 8u, c.Ts - T_offset);
             CertNetSalt net_salt;
@@ -532,54 +548,151 @@ __device__ __forceinline__ void ao_lean_body(LeanArgsPtr K_in, int chunk_in) {
                 if constexpr (LINE) s = mo_iterate_lean_line<COARE>(L, c, tab, in_range);
                 else s = mo_iterate_lean<COARE>(L, c, tab, in_range);
             }
-            if (finish) {
-                LeanArgsPtr Ke = opaque(K);
+            if constexpr (BURST) {
+                // (the burst's helpers live in this block: declared beside the batch loop's other lambdas they changed the
+                // code of the kernels that do not use them)
+                // FUSE: what compute_net_ocean_fluxes! reads of a cell beside the turbulent fluxes (T and S again: cheaper than four
+                // registers across the iteration).  BURST requests it for every lane of the batch — a lane beyond the list's end
+                // reads the last listed cell (position_of), a ring cell reads the fields the solver reads there anyway —
+                // so that the loads are straight-line code in front of the next batch's; only interior cells use them.
+                struct NetRaw {
+                    double To, So, Mp, Qs, Ql, conc, Qio, Jsio, land;
+                };
+                auto request_net = [&](unsigned k8) {
+                    LeanArgsPtr Ke = opaque(K);
+                    NetRaw n;
+                    n.To = gload(Ke->O.T, k8);
+                    n.So = gload(Ke->O.S, k8);
+                    n.Mp = gload(Ke->E.Mp, k8);
+                    n.Qs = gload(Ke->E.Qs, k8);
+                    n.Ql = gload(Ke->E.Ql, k8);
+                    const IceIn I = kread(&Ke->I);
+                    n.conc = I.conc ? gload(I.conc, k8) : 0.0;
+                    n.Qio = I.Qio ? gload(I.Qio, k8) : 0.0;
+                    n.Jsio = I.Jsio ? gload(I.Jsio, k8) : 0.0;
+                    n.land = I.land ? gload(I.land, k8) : 0.0;
+                    return n;
+                };
+                auto net_of = [&](const NetRaw& n, const CellFluxes& R) {
+                    const double Ts_ocean = (n.To + P.T_offset) - T_offset;  // what F.Ts holds (written before the iteration)
+                    return net_cell_local(P, P.albedo, n.conc, n.So, Ts_ocean + P.T_offset, n.Mp, n.Qs, n.Ql, R.Qc, R.Qv, R.Fv, n.Qio, n.Jsio, n.land);
+                };
+                auto store_cell = [&](LeanArgsPtr Ke, unsigned k, const CellFluxes& R) {
+                    const FluxOut F = kread(&Ke->F);
+                    const unsigned k8 = k * 8u;
+                    store_result(F.Qc, k8, R.Qc);
+                    store_result(F.Qv, k8, R.Qv);
+                    store_result(F.Fv, k8, R.Fv);
+                    gstore(F.tx, k8, R.rho_tau_x);
+                    gstore(F.ty, k8, R.rho_tau_y);
+                    if (F.ustar) gstore_final(F.ustar, k8, R.ustar);
+                    if (F.tstar) gstore_final(F.tstar, k8, R.tstar);
+                    if (F.qstar) gstore_final(F.qstar, k8, R.qstar);
+                    if (F.iters) gstore_i32(F.iters, k * 4u, R.iterations);
+                };
+                auto store_net = [&](LeanArgsPtr Ke, unsigned k8, const NetCell& C) {
+                    const NetOut N = kread(&Ke->N);
+                    gstore_final(N.T, k8, C.JT);  // (store_net_cell's fields, by offset)
+                    gstore_final(N.S, k8, C.JS);
+                    if (N.sw) gstore_final(N.sw, k8, C.sw);
+                    if (N.lw_up) gstore_final(N.lw_up, k8, C.lw_up);
+                    if (N.lw_down) gstore_final(N.lw_down, k8, C.lw_down);
+                    if (N.sw_down) gstore_final(N.sw_down, k8, C.sw_down);
+                };
+                // the trip-count hint of the next call, behind the batch's stores
+                auto note_trips = [&](int q, const Scales& s) {
+                    if (sorting && have_list) {
+                        const int w = min(s.work, 255);
+                        list[q] = (list[q] & LEAN_OFFSET_MASK) | ((unsigned)w << LEAN_OFFSET_BITS);
+                        atomicAdd(&hist[lean_bin(q, w)], 1);
+                    }
+                };
+                // ---- the boundary's memory requests: claim, this batch's epilogue loads, the next batch's inputs ----
+                const int next = claim();
+                int ci, cj;
                 // (cell coordinates recomputed from the list entry: cheaper than registers held across the iteration)
-                const size_t k = cell_of(start);
+                const unsigned k = (unsigned)coords_of(start, ci, cj);
+                NetRaw mine{};
+                if constexpr (FUSE) mine = request_net(k * 8u);
+                // (a claim beyond the list's end requests the last listed cell once more — position_of — and nobody looks at
+                // it: the requests stay straight-line code)
+                raw = request(next);
                 const CellFluxes R = lean_epilogue(c, T_offset, s);
-                const FluxOut F = kread(&Ke->F);
-                const unsigned k8 = (unsigned)k * 8u;
-                store_result(F.Qc, k8, R.Qc);
-                store_result(F.Qv, k8, R.Qv);
-                store_result(F.Fv, k8, R.Fv);
-                gstore(F.tx, k8, R.rho_tau_x);
-                gstore(F.ty, k8, R.rho_tau_y);
-                if (F.ustar) gstore_final(F.ustar, k8, R.ustar);
-                if (F.tstar) gstore_final(F.tstar, k8, R.tstar);
-                if (F.qstar) gstore_final(F.qstar, k8, R.qstar);
-                if (F.iters) gstore_i32(F.iters, (unsigned)k * 4u, R.iterations);
-                if constexpr (FUSE) {
-                    // compute_net_ocean_fluxes!, the part that needs no neighbour: interior cells only
-                    const int idx = range_begin + (int)(list[position_of(start)] & LEAN_OFFSET_MASK);
-                    const int jj = row_of(idx, wx, wx_rcp);
-                    const int ci = idx - jj * wx - G.ring, cj = jj - G.ring;
-                    if (ci >= 0 && ci < G.nx && cj >= 0 && cj < G.ny) {
-                        const IceIn I = kread(&Ke->I);
-                        const NetOut N = kread(&Ke->N);
-                        const double Ts_ocean = (gload(Ke->O.T, k8) + P.T_offset) - T_offset;  // what F.Ts holds (written before the iteration)
-                        const NetCell C = net_cell_local(P, P.albedo, I.conc ? gload(I.conc, k8) : 0.0, gload(Ke->O.S, k8), Ts_ocean + P.T_offset,
-                                                         gload(Ke->E.Mp, k8), gload(Ke->E.Qs, k8), gload(Ke->E.Ql, k8), R.Qc, R.Qv, R.Fv,
-                                                         I.Qio ? gload(I.Qio, k8) : 0.0, I.Jsio ? gload(I.Jsio, k8) : 0.0,
-                                                         I.land ? gload(I.land, k8) : 0.0);
-                        gstore_final(N.T, k8, C.JT);  // (store_net_cell's fields, by offset)
-                        gstore_final(N.S, k8, C.JS);
-                        if (N.sw) gstore_final(N.sw, k8, C.sw);
-                        if (N.lw_up) gstore_final(N.lw_up, k8, C.lw_up);
-                        if (N.lw_down) gstore_final(N.lw_down, k8, C.lw_down);
-                        if (N.sw_down) gstore_final(N.sw_down, k8, C.sw_down);
+                // ---- the boundary's ONE wait: both groups of loads, and nothing else, are in flight (the interface
+                // temperature's store went out in front of the iteration).  A use of the next batch's inputs HERE, in front of
+                // every store of this batch: the next prologue finds them landed and waits for no store's acknowledgement ----
+                // (results do not depend on this statement, only the order does, and a compiler may place the loads or the wait
+                // otherwise without any test failing.  To re-verify after a compiler change: in the assembly of
+                // ao_lean_kernel<false, true, true, false> the batch loop must show the 5 + 4 + 11 global_load_dwordx2, ONE
+                // s_waitcnt vmcnt(0), the stores, and no vmcnt wait from there to the back edge — profiles/batch_boundary_experiments.md §2)
+                asm volatile("" : "+v"(raw.ua), "+v"(raw.va), "+v"(raw.Ta), "+v"(raw.pa), "+v"(raw.qa), "+v"(raw.u0), "+v"(raw.u1), "+v"(raw.v0),
+                             "+v"(raw.v1), "+v"(raw.To), "+v"(raw.So));
+                if (finish) {
+                    LeanArgsPtr Ke = opaque(K);
+                    store_cell(Ke, k, R);
+                    if constexpr (FUSE) {
+                        // compute_net_ocean_fluxes!, the part that needs no neighbour: interior cells only
+                        if (ci >= 0 && ci < G.nx && cj >= 0 && cj < G.ny) store_net(Ke, k * 8u, net_of(mine, R));
+                    }
+                    note_trips(q, s);
+                }
+                if (next < limit) ahead = lean_prologue(P, L.kappa, tab, raw.ua, raw.va, raw.Ta, raw.pa, raw.qa, 0.5 * (raw.u0 + raw.u1), 0.5 * (raw.v0 + raw.v1), raw.To, raw.So);
+                start = next;
+            } else {
+                // (TWO COPIES of the epilogue: this block and the burst above store the same fields from the same arithmetic —
+                // a change to one must be made to the other; tests/test_steps.py and tests/test_batch_boundary.py hold both to
+                // the same bits)
+                // (the plain order, in the words it was measured in: the certified path and the sea-ice launch's rider are
+                // sensitive to how this block is written — through helpers shared with the burst the sea-ice step measured 2.5 % slower)
+                if (finish) {
+                    LeanArgsPtr Ke = opaque(K);
+                    // (cell coordinates recomputed from the list entry: cheaper than registers held across the iteration)
+                    const size_t k = cell_of(start);
+                    const CellFluxes R = lean_epilogue(c, T_offset, s);
+                    const FluxOut F = kread(&Ke->F);
+                    const unsigned k8 = (unsigned)k * 8u;
+                    store_result(F.Qc, k8, R.Qc);
+                    store_result(F.Qv, k8, R.Qv);
+                    store_result(F.Fv, k8, R.Fv);
+                    gstore(F.tx, k8, R.rho_tau_x);
+                    gstore(F.ty, k8, R.rho_tau_y);
+                    if (F.ustar) gstore_final(F.ustar, k8, R.ustar);
+                    if (F.tstar) gstore_final(F.tstar, k8, R.tstar);
+                    if (F.qstar) gstore_final(F.qstar, k8, R.qstar);
+                    if (F.iters) gstore_i32(F.iters, (unsigned)k * 4u, R.iterations);
+                    if constexpr (FUSE) {
+                        // compute_net_ocean_fluxes!, the part that needs no neighbour: interior cells only
+                        const int idx = range_begin + (int)(list[position_of(start)] & LEAN_OFFSET_MASK);
+                        const int jj = row_of(idx, wx, wx_rcp);
+                        const int ci = idx - jj * wx - G.ring, cj = jj - G.ring;
+                        if (ci >= 0 && ci < G.nx && cj >= 0 && cj < G.ny) {
+                            const IceIn I = kread(&Ke->I);
+                            const NetOut N = kread(&Ke->N);
+                            const double Ts_ocean = (gload(Ke->O.T, k8) + P.T_offset) - T_offset;  // what F.Ts holds (written before the iteration)
+                            const NetCell C = net_cell_local(P, P.albedo, I.conc ? gload(I.conc, k8) : 0.0, gload(Ke->O.S, k8), Ts_ocean + P.T_offset,
+                                                             gload(Ke->E.Mp, k8), gload(Ke->E.Qs, k8), gload(Ke->E.Ql, k8), R.Qc, R.Qv, R.Fv,
+                                                             I.Qio ? gload(I.Qio, k8) : 0.0, I.Jsio ? gload(I.Jsio, k8) : 0.0,
+                                                             I.land ? gload(I.land, k8) : 0.0);
+                            gstore_final(N.T, k8, C.JT);  // (store_net_cell's fields, by offset)
+                            gstore_final(N.S, k8, C.JS);
+                            if (N.sw) gstore_final(N.sw, k8, C.sw);
+                            if (N.lw_up) gstore_final(N.lw_up, k8, C.lw_up);
+                            if (N.lw_down) gstore_final(N.lw_down, k8, C.lw_down);
+                            if (N.sw_down) gstore_final(N.sw_down, k8, C.sw_down);
+                        }
+                    }
+                    if (sorting && have_list) {
+                        const int w = min(s.work, 255);
+                        list[q] = (list[q] & LEAN_OFFSET_MASK) | ((unsigned)w << LEAN_OFFSET_BITS);
+                        atomicAdd(&hist[lean_bin(q, w)], 1);
                     }
                 }
-                if (sorting && have_list) {
-                    const int w = min(s.work, 255);
-                    list[q] = (list[q] & LEAN_OFFSET_MASK) | ((unsigned)w << LEAN_OFFSET_BITS);
-                    atomicAdd(&hist[lean_bin(q, w)], 1);
-                }
+                int next;
+                if constexpr (CERT) next = straggling ? start + 64 : claim();
+                else next = claim();
+                if (next < limit) raw = request(next);
+                start = next;
             }
-            int next;
-            if constexpr (CERT) next = straggling ? start + 64 : claim();
-            else next = claim();
-            if (next < limit) raw = request(next);
-            start = next;
         }
         if (have_list || end >= range_end) break;
         begin = end;  // classification path: the rest of the range
